@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- megapixels/s of the resample hot path (BASELINE.json metric) on N MI355X of one node.
 
-    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--workload ...]
+    python bench.py --gpus N --steps K --warmup W [--scaling weak|strong] [--workload ...] [--full] [--dump-outputs DIR]
 
 Default workload (config.workload): BASELINE config 2 -- a batch of 256 synthetic 3840x2160 BGRA8 frames per GPU, device
 resident, each resized to 200x200 with Robidoux in linear light (ReplaceSelf canvas, alpha not meaningful, as after a
@@ -21,8 +21,17 @@ scaling curves.  The warm-up steps gather as the timed ones do (RCCL's lazy peer
 `--gpus N` with no torch.distributed environment re-executes this file under `python -m torch.distributed.run` with N
 ranks; under a launcher, WORLD_SIZE must equal --gpus (anything else is an error, never a silent 1-GPU run).
 
-The default run (N = 1, cfg2) also measures BASELINE configs 5, 3 and 4 -- child runs of this file with --workload, reduced step
-counts -- and reports them as `other_configs`: time per step, the kernel-timed roofline fraction, the parity stamp, the workload.
+A plain run sets up, warms up, times the K steps and prints its line: `metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (one timed step) and the configuration.  Everything else it can measure or check runs only with --full: the
+kernel-duration probe and `roofline`, `parity_checked`, the N > 1 `selfcheck`, a second timed loop without gathers
+(`value_without_gather`, `gather_ms` at N > 1), `strong_1024`, `cpu_baseline`, `host_dropin` and, for the default run (N = 1,
+cfg2), BASELINE configs 5, 3 and 4 -- child runs of this file with --full --workload, reduced step counts -- reported as
+`other_configs`: time per step, the kernel-timed roofline fraction, the parity stamp, the workload.  A run's inputs are the
+same with or without --full.
+
+--dump-outputs DIR writes, after the timed steps, what the last one computed: the BGRA8 outputs as float32 .npy files
+(`canvas`, the pyramid's `level_*` and `jpeg_*` files, cfg4's `out`), a fixed, seeded sample of frames (`frame_index`) when
+the whole would exceed 64 MB.  The inputs are seeded: two builds given the same arguments can be compared file for file.
 
 --workload cfg3 is BASELINE config 3 as a job: the export_4_sizes pyramid 3840x2160 -> 1600x900 -> {1200x675 -> 400x225,
 800x450} (imageflow_tool/src/self_test.rs:185-198), four chained launches per batch, 58 737 600 algorithmic bytes per
@@ -45,9 +54,9 @@ DCT-domain 1/2 decode + resize on all host cores.  Images are sharded in contigu
 finished 800x450 outputs are gathered behind every step.
 
 Prints ONE JSON line (rank 0).  value = source megapixels resized per second over all ranks, inputs already in HBM.
-After the timed region (never inside it) rank 0 renders frames of the last step's output again on the CPU oracle and
-compares: `parity_checked` (BASELINE config 2: "... bit-exact check vs CPU").  N > 1 (on unless --no-selfcheck): every rank's
-first gathered frame is compared with one rendered locally on rank 0 -- catches a gather that lands at the wrong offset.
+With --full, after the timed region (never inside it) rank 0 renders frames of the last step's output again on the CPU oracle
+and compares: `parity_checked` (BASELINE config 2: "... bit-exact check vs CPU").  N > 1 (on unless --no-selfcheck): every
+rank's first gathered frame is compared with one rendered locally on rank 0 -- catches a gather that lands at the wrong offset.
 """
 import argparse
 import json
@@ -95,9 +104,10 @@ PYRAMID_BYTES_PER_IMAGE = 58_737_600                               # SURVEY.md s
 PYRAMID_WRITE_BYTES_PER_IMAGE = 10_800_000                         # of which written: the four levels (1600x900 + 1200x675 + 800x450 + 400x225) x 4 B
 
 
-def make_frames(torch, n, first_index, seed, device, pattern, in_w, in_h):
+def make_frames(torch, n, first_index, seed, device, pattern, in_w, in_h, random_from=None):
     """frame k pixel (x,y): B=(x+k)&255, G=(y+k)&255, R=(x+y+k)&255, A=255 (bench_graphics.rs:403-414 + offset);
-    the random half is uniform bytes (worst case for LUT bank conflicts and rounding)."""
+    the random half is uniform bytes (worst case for LUT bank conflicts and rounding).  pattern mixed: frames from
+    `random_from` on (default n // 2) are the random ones -- frame i is the same whatever the n of the call."""
     from imageflow_amd.graphics.bitmaps import Bitmap, get_stride
     stride = get_stride(in_w)
     data = torch.empty((n, in_h, stride), dtype=torch.uint8, device=device)
@@ -107,7 +117,7 @@ def make_frames(torch, n, first_index, seed, device, pattern, in_w, in_h):
     gen.manual_seed(1000 + seed)
     for i in range(n):
         k = first_index + i
-        use_random = pattern == "random" or (pattern == "mixed" and i >= n // 2)
+        use_random = pattern == "random" or (pattern == "mixed" and i >= (n // 2 if random_from is None else random_from))
         if use_random:
             data[i] = torch.randint(0, 256, (in_h, stride), dtype=torch.uint8, device=device, generator=gen)
             data[i, :, 3::4] = 255
@@ -118,6 +128,31 @@ def make_frames(torch, n, first_index, seed, device, pattern, in_w, in_h):
             px[..., 2] = ((x + y + k) & 255).to(torch.uint8)
             px[..., 3] = 255
     return Bitmap(data.view(n, in_h * stride), in_w, in_h, stride, alpha_meaningful=False)
+
+
+DUMP_BYTES = 64_000_000                                             # --dump-outputs: at most this much in all
+
+
+def bgra_frames(b):
+    """A batch of BGRA8 bitmaps as the uint8 tensor a caller reads, [n, h, w, 4] (the stride's padding cut off)."""
+    return b.data[:, :b.h * b.stride].view(-1, b.h, b.stride)[:, :, :4 * b.w].view(-1, b.h, b.w, 4)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: the last timed step's outputs as <out_dir>/<name>.npy in float32.  `arrays` maps names to tensors whose
+    first axis is the frame; when all of them together exceed DUMP_BYTES as float32, the same fixed, seeded sample of frames
+    is taken from each, and frame_index.npy (float64) says which."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    n = next(iter(arrays.values())).shape[0]
+    per_frame = sum(4 * (t.numel() // max(t.shape[0], 1)) for t in arrays.values())
+    k = max(1, min(n, (DUMP_BYTES - (1 << 20)) // max(per_frame, 1)))
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+    sel = torch.from_numpy(idx)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t[sel.to(t.device)].cpu().numpy().astype(np.float32))
+    np.save(os.path.join(out_dir, "frame_index.npy"), idx.astype(np.float64))
 
 
 def _usable_cpus_now():
@@ -186,7 +221,7 @@ def cpu_baseline(sample_seconds=8.0):
     total = time.perf_counter() - t0
     mp = reps * n * in_w * in_h / 1e6
     cargo = shutil.which("cargo")
-    ref_tree = os.path.isdir("/root/reference/imageflow_core")
+    ref_tree = os.path.isdir(os.path.join(os.environ.get("IMAGEFLOW_REFERENCE", ""), "imageflow_core"))   # (a reference checkout, if named)
     return {"value": round(mp / total, 2), "unit": "MP/s", "cores": cores, "kind": "port",
             "host_logical_cpus": os.cpu_count(), "single_thread_MPps": round(in_w * in_h / 1e6 / t1, 2),
             "sample": f"{reps} passes over {n} frames 3840x2160->200x200 Robidoux linear (half gradient, half random), "
@@ -456,49 +491,51 @@ def run_cfg4(args, torch, dist, world, rank, local_rank, dev, dryrun, inputs, rc
         gather_outputs("warmup")
     el, t_steps = timed(args.steps, "timed")
     elapsed = max_over_ranks(el, dev)
-    if mode == "every":
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"out": bgra_frames(out_all)[:n]})
+    if mode == "every" and not args.full:
+        compute_s = None                                # (the second loop, without gathers, is part of --full)
+    elif mode == "every":
         compute_s = max_over_ranks(timed(args.steps, None)[0], dev)
     else:
         compute_s = max_over_ranks(t_steps if mode == "final" else el, dev)
 
-    # the pixel stage + resize call alone (SURVEY 8d's unit: coefficient planes in, 800x450 out), hipEvents on its stream,
-    # one batch at a time so that nothing else shares the device
-    launches = max(10, min(args.steps, 20))
-    if elapsed < 0.6 and args.steps > 0:               # a reduced run: bring the clocks up before the probe (see the resample workloads' probe)
-        run_steps(min(400, int((0.6 - elapsed) / max(elapsed / args.steps, 1e-4)) + 1))
+    if args.full:
+        # the pixel stage + resize call alone (SURVEY 8d's unit: coefficient planes in, 800x450 out), hipEvents on its stream,
+        # one batch at a time so that nothing else shares the device
+        launches = max(10, min(args.steps, 20))
+        if elapsed < 0.6 and args.steps > 0:               # a reduced run: bring the clocks up before the probe (see the resample workloads' probe)
+            run_steps(min(400, int((0.6 - elapsed) / max(elapsed / args.steps, 1e-4)) + 1))
+            torch.cuda.synchronize()
+        px_ms, ent_ms = 0.0, 0.0
+        for c in ctx:
+            with torch.cuda.stream(c["stream"]):
+                for bt in c["batches"]:
+                    e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
+                    e0.record(c["stream"])
+                    for _ in range(launches):
+                        bt["stage"].read_frames_into(bt["coef"], bt["qt"], bt["small"], info)
+                    e1.record(c["stream"])
+                    for _ in range(launches):
+                        bt["ent"].read_coefficients(bt["coef"])
+                    e2.record(c["stream"])
+                    c["stream"].synchronize()
+                    px_ms += e0.elapsed_time(e1) / launches
+                    ent_ms += e1.elapsed_time(e2) / launches
         torch.cuda.synchronize()
-    px_ms, ent_ms = 0.0, 0.0
-    for c in ctx:
-        with torch.cuda.stream(c["stream"]):
-            for bt in c["batches"]:
-                e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
-                e0.record(c["stream"])
-                for _ in range(launches):
-                    bt["stage"].read_frames_into(bt["coef"], bt["qt"], bt["small"], info)
-                e1.record(c["stream"])
-                for _ in range(launches):
-                    bt["ent"].read_coefficients(bt["coef"])
-                e2.record(c["stream"])
-                c["stream"].synchronize()
-                px_ms += e0.elapsed_time(e1) / launches
-                ent_ms += e1.elapsed_time(e2) / launches
-    torch.cuda.synchronize()
 
     parity = None
     selfcheck = None
     if rank == 0:
-        parity = cfg4_parity(torch, files, out_all, [0, n - 1])
-        if args.selfcheck and gathered is not None and gather_ok:
-            selfcheck = cfg4_selfcheck(torch, gathered, total, world, dev, out_all)
+        if args.full:
+            parity = cfg4_parity(torch, files, out_all, [0, n - 1])
+            if args.selfcheck and gathered is not None and gather_ok:
+                selfcheck = cfg4_selfcheck(torch, gathered, total, world, dev, out_all)
         mp_per_step = total * w * h / 1e6
-        algo = n * CFG4["bytes_per_image"]
-        achieved = algo / (px_ms * 1e-3)
         out = {
             "metric": "megapixels/sec JPEG decode + resize (4K 4:2:0 q85 -> 800px)", "value": round(mp_per_step * args.steps / elapsed, 1), "unit": "MP/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(elapsed / args.steps * 1e3, 4),
             "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None, "dtype": "i32/f32", "data": "synthetic",
-            "gather_ms": round((elapsed - compute_s) / (args.steps if mode == "every" else 1) * 1e3, 4),
-            "value_without_gather": round(mp_per_step * args.steps / compute_s, 1),
             "files_per_s": round(total * args.steps / elapsed, 1),
             "config": {"workload": f"BASELINE cfg4: {total} files ({n} on rank 0) 3840x2160 4:2:0 q85 baseline JPEG -> GPU entropy decode -> 4/8 IDCT "
                                    f"(spatial sRGB luma scaler) + YCbCr -> 800x450 Robidoux, linear light; compressed scans device resident",
@@ -508,29 +545,36 @@ def run_cfg4(args, torch, dist, world, rank, local_rank, dev, dryrun, inputs, rc
                        "kernel": "jpeg entropy passes + luma / chroma IDCT kernels + the resampler reading the component planes",
                        "gather": gather_note, "gathers": gathers, "gather_mode": mode, "rccl_channels": rccl_env,
                        "rccl_ranks": dist.get_world_size() if distributed else 1,
-                       "backend": (dist.get_backend() if distributed else "none"), "ranks": ranks_info,
-                       "entropy_decode_ms_per_step": round(ent_ms, 4), "pixel_stage_and_resize_ms_per_step": round(px_ms, 4)},
-            "roofline": {"bound": "hbm", "achieved": round(achieved / 1e9, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK, 4),
-                         "frac_timed": round(algo / (compute_s / args.steps) / HBM_PEAK, 4),
-                         "traffic": None, "traffic_source": "profiles/ (rocprofv3 --pmc passes of tools/bench_jpeg.py --chain), not measured in this run",
-                         "kernel_ms": round(px_ms, 4), "algorithmic_bytes_per_launch": algo,
-                         "what": "the pixel stage + resize calls of one step (coefficient planes + quant tables in, 800x450 BGRA out: 26 323 584 B per image, "
-                                 "SURVEY 8d), batches one after the other, hipEvents on their streams; frac_timed puts the same bytes over the WHOLE "
-                                 "chain's step time, entropy decode included"},
-            "parity_checked": parity,
+                       "backend": (dist.get_backend() if distributed else "none"), "ranks": ranks_info},
         }
-        try:
-            out["roofline_entropy"] = cfg4_entropy_roofline(files, n, ent_ms)
-        except Exception as e:  # noqa: BLE001
-            out["roofline_entropy"] = {"bound": "issue", "frac": None, "error": f"{type(e).__name__}: {e}"}
-        if selfcheck is not None:
-            out["selfcheck"] = selfcheck
-        if world == 1 and not args.no_cpu_baseline:
+        if compute_s is not None:
+            out["gather_ms"] = round((elapsed - compute_s) / (args.steps if mode == "every" else 1) * 1e3, 4)
+            out["value_without_gather"] = round(mp_per_step * args.steps / compute_s, 1)
+        if args.full:
+            algo = n * CFG4["bytes_per_image"]
+            achieved = algo / (px_ms * 1e-3)
+            out["config"]["entropy_decode_ms_per_step"] = round(ent_ms, 4)
+            out["config"]["pixel_stage_and_resize_ms_per_step"] = round(px_ms, 4)
+            out["roofline"] = {"bound": "hbm", "achieved": round(achieved / 1e9, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK, 4),
+                               "frac_timed": round(algo / (compute_s / args.steps) / HBM_PEAK, 4),
+                               "traffic": None, "traffic_source": "profiles/ (rocprofv3 --pmc passes of tools/bench_jpeg.py --chain), not measured in this run",
+                               "kernel_ms": round(px_ms, 4), "algorithmic_bytes_per_launch": algo,
+                               "what": "the pixel stage + resize calls of one step (coefficient planes + quant tables in, 800x450 BGRA out: 26 323 584 B per image, "
+                                       "SURVEY 8d), batches one after the other, hipEvents on their streams; frac_timed puts the same bytes over the WHOLE "
+                                       "chain's step time, entropy decode included"}
+            out["parity_checked"] = parity
             try:
-                out["cpu_baseline"] = cfg4_cpu_baseline(files)
+                out["roofline_entropy"] = cfg4_entropy_roofline(files, n, ent_ms)
             except Exception as e:  # noqa: BLE001
-                out["cpu_baseline"] = {"value": None, "unit": "MP/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {e}"}
+                out["roofline_entropy"] = {"bound": "issue", "frac": None, "error": f"{type(e).__name__}: {e}"}
+            if selfcheck is not None:
+                out["selfcheck"] = selfcheck
+            if world == 1 and not args.no_cpu_baseline:
+                try:
+                    out["cpu_baseline"] = cfg4_cpu_baseline(files)
+                except Exception as e:  # noqa: BLE001
+                    out["cpu_baseline"] = {"value": None, "unit": "MP/s", "cores": os.cpu_count(), "kind": "port", "sample": f"failed: {e}"}
         print(json.dumps(out), flush=True)
 
 
@@ -651,7 +695,7 @@ def other_configs(budget_s):
         if left < 20:
             out[name] = {"skipped": f"time budget of {budget_s:.0f} s used up"}
             continue
-        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--no-cpu-baseline", "--no-strong-field", "--no-other-configs"] + extra
+        cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--full", "--no-cpu-baseline", "--no-strong-field", "--no-other-configs"] + extra
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=min(left, 100))
@@ -720,15 +764,29 @@ def parse_args(argv=None):
                          "(default: on whenever N > 1 and the outputs are gathered)")
     ap.add_argument("--no-selfcheck", dest="selfcheck", action="store_false")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="the default run (N = 1, cfg2) also measures BASELINE configs 5, 3 and 4 at reduced step counts, each as "
-                         "`bench.py --workload ...` in a child process, and reports them under `other_configs`; this skips them")
+                    help="a --full run of the default workload (N = 1, cfg2) also measures BASELINE configs 5, 3 and 4 at reduced step "
+                         "counts, each as `bench.py --full --workload ...` in a child process, and reports them under `other_configs`; "
+                         "this skips them")
     ap.add_argument("--other-configs-budget-s", type=float, default=150.0, help="wall-clock cap of that addition")
     ap.add_argument("--outputs", default="files", choices=["files", "bgra"],
                     help="--workload cfg3: what the job leaves and its final gather ships -- the four JPEG files per image "
                          "(libjpeg_turbo q90, coded on the device; the reference's export_4_sizes) or the raw BGRA levels")
     ap.add_argument("--no-strong-field", action="store_true",
                     help="skip the extra `strong_1024` measurement (the --total-frames job cut into N blocks) of a weak cfg2 run")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure and check everything else: the kernel probe and roofline, the parity stamp "
+                         "against the CPU oracle, the N > 1 selfcheck, the steps again without gathers, `strong_1024`, the CPU "
+                         "baselines, `host_dropin` and `other_configs` (each can still be skipped by its own --no-... option).  "
+                         "Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy (float32; a fixed, seeded sample "
+                         "of frames, DIR/frame_index.npy, when the whole exceeds 64 MB)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
+    return args
 
 
 def main():
@@ -842,6 +900,9 @@ def main():
     if strong_field and n_strong < 1:
         strong_field = False
     n_alloc = max(n, n_strong)
+    # the inputs do not depend on --full: a run that does not measure strong_1024 makes only the first n of the same frames
+    measure_strong = strong_field and args.full
+    n_make = n_alloc if measure_strong else n
 
     ranks_info = [{"rank": rank, "device": torch.cuda.get_device_name(local_rank), "local_rank": local_rank}]
     if distributed:
@@ -849,10 +910,10 @@ def main():
         dist.all_gather_object(objs, ranks_info[0])
         ranks_info = objs
 
-    inp_all = make_frames(torch, n_alloc, lo, rank, dev, args.pattern, in_w, in_h)
+    inp_all = make_frames(torch, n_make, lo, rank, dev, args.pattern, in_w, in_h, random_from=n_alloc // 2)
     inp_all.alpha_meaningful = wl[6]
-    if wl[6]:
-        inp_all.data.view(n_alloc, in_h, -1)[:, :, 3::4] = torch.randint(0, 256, (n_alloc, in_h, inp_all.stride // 4), dtype=torch.uint8, device=dev)
+    if wl[6]:                                            # (alpha workloads have no strong_1024: n_make == n_alloc)
+        inp_all.data.view(n_make, in_h, -1)[:, :, 3::4] = torch.randint(0, 256, (n_make, in_h, inp_all.stride // 4), dtype=torch.uint8, device=dev)
 
     def first_frames(b, k):
         return Bitmap(b.data[:k], b.w, b.h, b.stride, b.alpha_meaningful, b.compose, b.matte)
@@ -1022,10 +1083,11 @@ def main():
             _native.set_cu_budget(0)
             return dt, t_steps
 
-        def measure(self, steps, warmup):
+        def measure(self, steps, warmup, plain=True):
             """-> (whole-job seconds with the job's gathers, seconds of the same steps without any gather), both max over ranks.
             With gathers: every step's batch is followed by ITS gather (mode every) -- the timed region ends when the last
-            batch's outputs are on rank 0 -- or the steps by one final gather (mode final).  Without: a second timed loop."""
+            batch's outputs are on rank 0 -- or the steps by one final gather (mode final).  Without: a second timed loop
+            (None when `plain` is false)."""
             for i in range(warmup):
                 self.step(i, phase="warmup")                # RCCL sets its peer-to-peer channels up lazily on the first send / recv
             self.sync_all()                                 # between two ranks (tens of ms): the warm-up steps gather as the timed ones do
@@ -1042,13 +1104,24 @@ def main():
                 return max_over_ranks(elapsed, dev), max_over_ranks(elapsed, dev)
             if mode == "final":                              # the steps of the same loop, before its gather
                 return max_over_ranks(elapsed, dev), max_over_ranks(t_steps, dev)
-            plain, _ = self.timed(steps, None)
-            return max_over_ranks(elapsed, dev), max_over_ranks(plain, dev)
+            if not plain:
+                return max_over_ranks(elapsed, dev), None
+            plain_s, _ = self.timed(steps, None)
+            return max_over_ranks(elapsed, dev), max_over_ranks(plain_s, dev)
 
     job = Job(n, total)
-    elapsed, compute_s = job.measure(args.steps, args.warmup)
+    elapsed, compute_s = job.measure(args.steps, args.warmup, plain=args.full)
+    if args.dump_outputs and rank == 0:
+        if pyramid:
+            dumped = {"level_" + name: bgra_frames(b) for name, b in job.levels.items()}
+            for name, e in job.enc.items():                # --outputs files: the JPEG files of every level, zero-padded, and their lengths
+                dumped["jpeg_" + name] = e[3][:, :max(1, int(e[4].max().item()))]
+                dumped["jpeg_" + name + "_length"] = e[4]
+        else:
+            dumped = {"canvas": bgra_frames(job.views[(args.steps - 1) & 1])}
+        dump_outputs(args.dump_outputs, dumped)
     resize_only_ms = None
-    if files_out:                                   # what a step costs without the encoders, and what the job's files weigh
+    if files_out and args.full:                     # what a step costs without the encoders, and what the job's files weigh
         k = max(1, min(args.steps, 20))
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -1067,7 +1140,7 @@ def main():
     main_gather_calls = dict(gather_calls)
 
     strong = None
-    if strong_field:
+    if measure_strong:
         gather_calls.update(warmup=0, timed=0)
         sj = Job(n_strong, args.total_frames)
         s_steps = max(1, min(args.steps, 20))
@@ -1086,33 +1159,37 @@ def main():
                           f"after overlap.  Speed-up of the batch over 1 GPU = this value at N / this value at N = 1 (no gather there)"}
         del sj
 
-    # dominant-kernel duration: hipEvents on the launch stream around back-to-back launches of the same op
-    launches = max(20, min(args.steps, 50))
-
-    def probe_once():
-        if pyramid:
-            return [time_scale_and_render(s, d, inf, launches=launches, plan=pl) for s, d, inf, pl in chain]
-        return [time_scale_and_render(inp, views[0], info, launches=launches, plan=plan)]
-    # The probe follows the timed job; when that job was short (a reduced run: the `other_configs` children, tests) the clocks
-    # are still ramping -- measured on cfg3: level 0, probed first, 1.18 ms behind a 150 ms job and 1.10 behind a 700 ms one -- so
-    # untimed passes of the same launches first bring the work done before the probe to ~0.6 s of GPU time.
-    warmed, probe_warm_passes = elapsed, 0
-    while warmed < 0.6 and probe_warm_passes < 50:
-        warmed += sum(probe_once()) * launches * 1e-3
-        probe_warm_passes += 1
-    if pyramid:
-        level_ms = probe_once()
-        kernel_ms = sum(level_ms)
-        algo_bytes = n * PYRAMID_BYTES_PER_IMAGE
-        kernel_name = "fused_resample_kernel x4 (levels %s ms)" % "/".join(f"{m:.3f}" for m in level_ms)
+    if not args.full:
+        kernel_name = ("fused_resample_kernel x4" if pyramid else
+                       "fused_resample_kernel" if plan.kernel_kind(wl[6]) == 0 else "two-pass (banded_resample_kernel where a band's rows fit the LDS, else the generic pair)")
     else:
-        kernel_ms = probe_once()[0]
-        algo_bytes = n * (in_w * in_h * 4 + out_w * out_h * 4)
-        kernel_name = "fused_resample_kernel" if plan.kernel_kind(wl[6]) == 0 else "two-pass (banded_resample_kernel where a band's rows fit the LDS, else the generic pair)"
-    torch.cuda.synchronize()
+        # dominant-kernel duration: hipEvents on the launch stream around back-to-back launches of the same op
+        launches = max(20, min(args.steps, 50))
+
+        def probe_once():
+            if pyramid:
+                return [time_scale_and_render(s, d, inf, launches=launches, plan=pl) for s, d, inf, pl in chain]
+            return [time_scale_and_render(inp, views[0], info, launches=launches, plan=plan)]
+        # The probe follows the timed job; when that job was short (a reduced run: the `other_configs` children, tests) the clocks
+        # are still ramping -- measured on cfg3: level 0, probed first, 1.18 ms behind a 150 ms job and 1.10 behind a 700 ms one -- so
+        # untimed passes of the same launches first bring the work done before the probe to ~0.6 s of GPU time.
+        warmed, probe_warm_passes = elapsed, 0
+        while warmed < 0.6 and probe_warm_passes < 50:
+            warmed += sum(probe_once()) * launches * 1e-3
+            probe_warm_passes += 1
+        if pyramid:
+            level_ms = probe_once()
+            kernel_ms = sum(level_ms)
+            algo_bytes = n * PYRAMID_BYTES_PER_IMAGE
+            kernel_name = "fused_resample_kernel x4 (levels %s ms)" % "/".join(f"{m:.3f}" for m in level_ms)
+        else:
+            kernel_ms = probe_once()[0]
+            algo_bytes = n * (in_w * in_h * 4 + out_w * out_h * 4)
+            kernel_name = "fused_resample_kernel" if plan.kernel_kind(wl[6]) == 0 else "two-pass (banded_resample_kernel where a band's rows fit the LDS, else the generic pair)"
+        torch.cuda.synchronize()
 
     parity, selfcheck = None, None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             # (the kernel-duration probe above rewrote views[0] / the levels with the same inputs: same bytes as the last step's)
             parity = pyramid_parity(torch, job.inp, job.levels) if pyramid else resample_parity(torch, wl, job.inp, job.views[(args.steps - 1) & 1], [0, n - 1])
@@ -1137,40 +1214,6 @@ def main():
     if rank == 0:
         mp_per_step = total * in_w * in_h / 1e6
         value = mp_per_step * args.steps / elapsed
-        achieved = algo_bytes / (kernel_ms * 1e-3)
-        # HBM bytes per launch: NOT measured in this run -- the figure of the separate rocprofv3 --pmc passes kept under
-        # profiles/ (FETCH_SIZE / WRITE_SIZE with the guide's gfx950 corrections), quoted for the default job only
-        traffic, traffic_source = None, None
-        try:
-            t = json.load(open(os.path.join(ROOT, "profiles", "traffic_cfg2.json")))
-            if n == FRAMES_PER_GPU and args.workload == "cfg2":
-                traffic = t["traffic_bytes_per_launch"]
-                traffic_source = "static: profiles/traffic_cfg2.json (" + t.get("source", "rocprofv3 --pmc passes") + ")"
-        except Exception:  # noqa: BLE001
-            pass
-        measured_read = None    # same-process yardstick: a read-only streaming kernel over 4 GiB (16-byte nt loads)
-        try:
-            import ctypes
-            from imageflow_amd import _native
-            bps = ctypes.c_double(0.0)
-            _native.check(_native.lib().ifhip_measure_read_bandwidth(4 << 30, 5, ctypes.byref(bps)))
-            measured_read = bps.value
-        except Exception:  # noqa: BLE001
-            pass
-        # ... and, for workloads whose canvas stores are a real share of the bytes (every shape but the thumbnails), the same
-        # with writes mixed in at that share: reads + writes run at 5.3 - 5.5 TB/s on MI355X where reads alone reach 7
-        measured_mix, write_share = None, None
-        try:
-            wbytes = (n * PYRAMID_WRITE_BYTES_PER_IMAGE) if pyramid else n * out_w * out_h * 4
-            write_share = wbytes / algo_bytes
-            if write_share >= 0.02 and hasattr(_native.lib(), "ifhip_measure_mixed_bandwidth"):
-                every = max(1, round((algo_bytes - wbytes) / wbytes))
-                bps = ctypes.c_double(0.0)
-                _native.lib().ifhip_measure_mixed_bandwidth.argtypes = [ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
-                _native.check(_native.lib().ifhip_measure_mixed_bandwidth(4 << 30, every, 5, ctypes.byref(bps)))
-                measured_mix = bps.value
-        except Exception:  # noqa: BLE001
-            pass
         shape = (f"{in_w}x{in_h} -> 1600x900 -> {{1200x675 -> 400x225, 800x450}} (export_4_sizes), four chained launches"
                  if pyramid else f"{in_w}x{in_h} BGRA8 -> {out_w}x{out_h}")
         out = {
@@ -1178,35 +1221,71 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
             "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": args.scaling,
             "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "gather_ms": round((elapsed - compute_s) / (args.steps if mode == "every" else 1) * 1e3, 4),
-            "value_without_gather": round(mp_per_step * args.steps / compute_s, 1),
             "config": {"workload": f"BASELINE {args.workload}: {total} frames ({n} on rank 0) {shape} {wl[4]}"
                                    f"{' sharpen ' + str(wl[5]) if wl[5] else ''}, linear light, {wl[7]}, "
                                    f"alpha {'meaningful' if wl[6] else 'not meaningful'}, device resident, pattern={args.pattern}",
                        "frames_per_gpu": n, "total_frames": total, "kernel": kernel_name, "gather": gather_note,
                        "gathers": main_gather_calls, "gather_mode": mode,
-                       "gather_ms_is": ("per step: (time of the steps with their gathers - time of the same steps without) / steps" if mode == "every"
-                                        else "the one gather at the end of the timed region"),
                        "rccl_channels": rccl_env, "reserved_cus_while_gathering": job_reserve if overlapped else 0,
                        "reserve_cus_tried_ms_per_batch": job_tuned or None,
                        "rccl_ranks": dist.get_world_size() if distributed else 1,
                        "backend": (dist.get_backend() if distributed else "none"), "ranks": ranks_info},
-            "roofline": {"bound": "hbm", "achieved": round(achieved / 1e9, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK, 4),
-                         # the same bytes over the TIMED loop's step time (launch gaps, clock ramp and, at N > 1, the gather included)
-                         "frac_timed": round(algo_bytes / (compute_s / args.steps) / HBM_PEAK, 4),
-                         "traffic": traffic, "traffic_source": traffic_source,
-                         "kernel_ms": round(kernel_ms, 4), "algorithmic_bytes_per_launch": algo_bytes,
-                         "probe_launches": launches, "probe_warm_passes": probe_warm_passes,
-                         "measured_read_GBps": round(measured_read / 1e9, 1) if measured_read else None,
-                         "frac_of_measured_read": round(achieved / measured_read, 4) if measured_read else None,
-                         "write_share": round(write_share, 4) if write_share is not None else None,
-                         "measured_mix_GBps": round(measured_mix / 1e9, 1) if measured_mix else None,
-                         "frac_of_measured_mix": round(achieved / measured_mix, 4) if measured_mix else None},
         }
+        if compute_s is not None:
+            out["gather_ms"] = round((elapsed - compute_s) / (args.steps if mode == "every" else 1) * 1e3, 4)
+            out["value_without_gather"] = round(mp_per_step * args.steps / compute_s, 1)
+            out["config"]["gather_ms_is"] = ("per step: (time of the steps with their gathers - time of the same steps without) / steps" if mode == "every"
+                                             else "the one gather at the end of the timed region")
         if pyramid:
             out["config"]["outputs"] = ("four JPEG files per image (libjpeg_turbo q90 4:2:0: forward pixel stage + entropy coder on the device), "
                                         "the final gather ships the files" if files_out else "four raw BGRA levels per image, gathered as they are")
+        if args.full:
+            # HBM bytes per launch: NOT measured in this run -- the figure of the separate rocprofv3 --pmc passes kept under
+            # profiles/ (FETCH_SIZE / WRITE_SIZE with the guide's gfx950 corrections), quoted for the default job only
+            traffic, traffic_source = None, None
+            try:
+                t = json.load(open(os.path.join(ROOT, "profiles", "traffic_cfg2.json")))
+                if n == FRAMES_PER_GPU and args.workload == "cfg2":
+                    traffic = t["traffic_bytes_per_launch"]
+                    traffic_source = "static: profiles/traffic_cfg2.json (" + t.get("source", "rocprofv3 --pmc passes") + ")"
+            except Exception:  # noqa: BLE001
+                pass
+            measured_read = None    # same-process yardstick: a read-only streaming kernel over 4 GiB (16-byte nt loads)
+            try:
+                import ctypes
+                from imageflow_amd import _native
+                bps = ctypes.c_double(0.0)
+                _native.check(_native.lib().ifhip_measure_read_bandwidth(4 << 30, 5, ctypes.byref(bps)))
+                measured_read = bps.value
+            except Exception:  # noqa: BLE001
+                pass
+            # ... and, for workloads whose canvas stores are a real share of the bytes (every shape but the thumbnails), the same
+            # with writes mixed in at that share: reads + writes run at 5.3 - 5.5 TB/s on MI355X where reads alone reach 7
+            measured_mix, write_share = None, None
+            try:
+                wbytes = (n * PYRAMID_WRITE_BYTES_PER_IMAGE) if pyramid else n * out_w * out_h * 4
+                write_share = wbytes / algo_bytes
+                if write_share >= 0.02 and hasattr(_native.lib(), "ifhip_measure_mixed_bandwidth"):
+                    every = max(1, round((algo_bytes - wbytes) / wbytes))
+                    bps = ctypes.c_double(0.0)
+                    _native.lib().ifhip_measure_mixed_bandwidth.argtypes = [ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
+                    _native.check(_native.lib().ifhip_measure_mixed_bandwidth(4 << 30, every, 5, ctypes.byref(bps)))
+                    measured_mix = bps.value
+            except Exception:  # noqa: BLE001
+                pass
+            achieved = algo_bytes / (kernel_ms * 1e-3)
+            out["roofline"] = {"bound": "hbm", "achieved": round(achieved / 1e9, 1), "peak": HBM_PEAK / 1e9, "unit": "GB/s",
+                               "frac": round(achieved / HBM_PEAK, 4),
+                               # the same bytes over the TIMED loop's step time (launch gaps, clock ramp and, at N > 1, the gather included)
+                               "frac_timed": round(algo_bytes / (compute_s / args.steps) / HBM_PEAK, 4),
+                               "traffic": traffic, "traffic_source": traffic_source,
+                               "kernel_ms": round(kernel_ms, 4), "algorithmic_bytes_per_launch": algo_bytes,
+                               "probe_launches": launches, "probe_warm_passes": probe_warm_passes,
+                               "measured_read_GBps": round(measured_read / 1e9, 1) if measured_read else None,
+                               "frac_of_measured_read": round(achieved / measured_read, 4) if measured_read else None,
+                               "write_share": round(write_share, 4) if write_share is not None else None,
+                               "measured_mix_GBps": round(measured_mix / 1e9, 1) if measured_mix else None,
+                               "frac_of_measured_mix": round(achieved / measured_mix, 4) if measured_mix else None}
             if files_out:
                 out["config"]["file_bytes_per_image"] = int(job_file_bytes // max(n, 1)) if job_file_bytes else None
                 out["config"]["gathered_bytes_per_rank"] = job_gathered_sizes
@@ -1215,23 +1294,23 @@ def main():
                 out["config"]["resize_only_ms_per_step"] = round(resize_only_ms, 4)
                 out["config"]["note"] = ("value counts source megapixels through the WHOLE job (resizes + encoders); roofline is the four "
                                          "resample launches alone")
-        out["parity_checked"] = parity
-        if selfcheck is not None:
-            out["selfcheck"] = selfcheck
-        if strong is not None:
-            out["strong_1024"] = strong
-        if world == 1 and not args.no_cpu_baseline and args.workload == "cfg2":
-            try:
-                out["cpu_baseline"] = cpu_baseline()
-            except Exception as e:   # the baseline is a report, never a reason to lose the GPU number
-                out["cpu_baseline"] = {"value": None, "unit": "MP/s", "cores": os.cpu_count(), "kind": "port",
-                                       "sample": f"failed: {e}"}
-            try:
-                out["host_dropin"] = host_dropin_rate(torch, seconds=2.0)
-            except Exception as e:  # noqa: BLE001
-                out["host_dropin"] = {"images_per_s": None, "what": f"failed: {e}"}
-        if world == 1 and args.workload == "cfg2" and not args.no_other_configs and args.scaling == "weak" and args.frames is None:
-            out["other_configs"] = other_configs(args.other_configs_budget_s)
+            out["parity_checked"] = parity
+            if selfcheck is not None:
+                out["selfcheck"] = selfcheck
+            if strong is not None:
+                out["strong_1024"] = strong
+            if world == 1 and not args.no_cpu_baseline and args.workload == "cfg2":
+                try:
+                    out["cpu_baseline"] = cpu_baseline()
+                except Exception as e:   # the baseline is a report, never a reason to lose the GPU number
+                    out["cpu_baseline"] = {"value": None, "unit": "MP/s", "cores": os.cpu_count(), "kind": "port",
+                                           "sample": f"failed: {e}"}
+                try:
+                    out["host_dropin"] = host_dropin_rate(torch, seconds=2.0)
+                except Exception as e:  # noqa: BLE001
+                    out["host_dropin"] = {"images_per_s": None, "what": f"failed: {e}"}
+            if world == 1 and args.workload == "cfg2" and not args.no_other_configs and args.scaling == "weak" and args.frames is None:
+                out["other_configs"] = other_configs(args.other_configs_budget_s)
         print(json.dumps(out), flush=True)
     if distributed:
         dist.destroy_process_group()

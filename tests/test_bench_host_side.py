@@ -45,3 +45,51 @@ def test_no_cut_with_the_encode_table_adds_busy_lanes_at_twenty_waves_per_cu():
         assert r["busy_lanes_per_cu"] <= today[r["shape"]] * 1.01, r
     committed = open(os.path.join(ROOT, "profiles", "r6_five_waves_feasibility.jsonl")).read()
     assert committed == out                                        # the file under profiles/ is what the tool prints today
+
+
+def test_options_of_a_plain_run_and_of_a_full_one():
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "3"])
+    assert a.steps == 7 and a.warmup == 3 and a.full is False and a.dump_outputs is None
+    a = bench.parse_args(["--steps", "2", "--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        try:
+            bench.parse_args(bad)
+        except SystemExit as e:
+            assert e.code == 2
+        else:
+            raise AssertionError(bad)
+
+
+def test_bgra_frames_cuts_the_stride_padding():
+    import torch
+    import bench
+    from imageflow_amd.graphics.bitmaps import Bitmap, get_stride
+    n, w, h = 3, 5, 4
+    st = get_stride(w)
+    data = torch.arange(n * h * st, dtype=torch.int64).remainder(251).to(torch.uint8).view(n, h * st)
+    got = bench.bgra_frames(Bitmap(data, w, h, st))
+    assert got.shape == (n, h, w, 4)
+    assert torch.equal(got.reshape(n, h, 4 * w), data.view(n, h, st)[:, :, :4 * w])
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    import bench
+    a = torch.arange(10 * 6, dtype=torch.int32).view(10, 6).to(torch.uint8)
+    b = torch.arange(10, dtype=torch.int32)
+    bench.dump_outputs(str(tmp_path / "all"), {"a": a, "b": b})
+    assert np.array_equal(np.load(tmp_path / "all" / "a.npy"), a.numpy().astype(np.float32))
+    assert np.load(tmp_path / "all" / "b.npy").dtype == np.float32
+    assert np.array_equal(np.load(tmp_path / "all" / "frame_index.npy"), np.arange(10.0))
+    # over the budget: the same seeded sample of frames from every array, every time
+    monkeypatch.setattr(bench, "DUMP_BYTES", (1 << 20) + 4 * 7 * 3)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"a": a, "b": b})
+    idx = np.load(tmp_path / "s1" / "frame_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 3 and list(idx) == sorted(set(idx))
+    assert np.array_equal(idx, np.load(tmp_path / "s2" / "frame_index.npy"))
+    assert np.array_equal(np.load(tmp_path / "s1" / "a.npy"), a.numpy()[idx.astype(int)].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "s1" / "b.npy"), idx.astype(np.float32))

@@ -104,7 +104,7 @@ def test_bench_launches_its_own_ranks(extra, scaling, total):
     env = _clean_env()
     env["IFHIP_BENCH_DRYRUN_ONE_GPU"] = "1"
     steps = 3
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", str(steps), "--warmup", "1", "--full", "--no-cpu-baseline"]
     if "--frames" not in extra and scaling == "weak":
         cmd += ["--frames", "8"]
     r = subprocess.run(cmd + extra, env=env, capture_output=True, text=True, timeout=900)
@@ -159,7 +159,7 @@ def test_bench_cfg4_shards_files_over_ranks_and_checks_itself(world, extra, tota
     env = _clean_env()
     env["IFHIP_BENCH_DRYRUN_ONE_GPU"] = "1"
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "cfg4", "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--batches-in-flight", "2", "--no-cpu-baseline"] + extra
+           "--batches-in-flight", "2", "--full", "--no-cpu-baseline"] + extra
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -176,7 +176,7 @@ def test_bench_selfcheck_and_parity_stamp_of_the_default_workload():
     env = _clean_env()
     env["IFHIP_BENCH_DRYRUN_ONE_GPU"] = "1"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--frames", "6", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-strong-field", "--no-selfcheck"], env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline", "--no-strong-field", "--no-selfcheck"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert j["parity_checked"]["equal"] is True and j["parity_checked"]["which"] == [0, 5]
@@ -228,7 +228,7 @@ def test_bench_runs_its_per_batch_gathers_over_rccl_on_a_one_rank_group(extra):
     env = _clean_env()
     env.update({"IFHIP_BENCH_ONE_RANK_RCCL": "1", "RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0", "MASTER_PORT": str(_free_port())})
     steps = 4
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "2", "--full", "--no-cpu-baseline",
                         "--no-other-configs"] + extra, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     j = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

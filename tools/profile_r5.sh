@@ -39,8 +39,8 @@ fi
 
 # 1. headline: bench line, the same command under kernel-trace, HBM traffic + SQ counters
 if want 1; then
-python bench.py > $SUM/bench_cfg2.json 2> $SUM/bench_cfg2.err
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_cfg2 -- python bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-strong-field > $SUM/bench_cfg2_under_trace.json 2> $OUT/trace_cfg2.err
+python bench.py --full > $SUM/bench_cfg2.json 2> $SUM/bench_cfg2.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_cfg2 -- python bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-strong-field > $SUM/bench_cfg2_under_trace.json 2> $OUT/trace_cfg2.err
 find $OUT/trace_cfg2 -name '*kernel_stats.csv' -exec cp {} $SUM/cfg2_kernel_stats.csv \;
 { echo "# rocprofv3 --pmc passes (one counter group per run), python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-strong-field, kernel fused_resample"
   for C in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU" "SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY" "GRBM_GUI_ACTIVE"; do
@@ -51,7 +51,7 @@ fi
 # 2. cfg5 (BASELINE's HBM-roofline config) and cfg2 with alpha: bench line + kernel stats + counters
 if want 2; then
 for W in cfg5 cfg2-alpha; do
-  python bench.py --workload $W --steps 30 --warmup 5 --no-cpu-baseline > $SUM/bench_$W.json 2> /dev/null
+  python bench.py --full --workload $W --steps 30 --warmup 5 --no-cpu-baseline > $SUM/bench_$W.json 2> /dev/null
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$W -- python bench.py --workload $W --steps 30 --warmup 5 --no-cpu-baseline > /dev/null 2> $OUT/trace_$W.err
   find $OUT/trace_$W -name '*kernel_stats.csv' -exec sh -c "head -1 {} > $SUM/${W}_kernel_stats.csv; grep fused_resample {} >> $SUM/${W}_kernel_stats.csv" \;
   { echo "# rocprofv3 --pmc passes, python bench.py --workload $W --steps 6 --warmup 2 --no-cpu-baseline, kernel fused_resample"
@@ -65,7 +65,7 @@ fi
 # 3. the other resample shapes (this round: output columns dealt to the lane groups of ds_read_b128, two-column groups): bench line + kernel stats
 if want 3; then
 for W in cfg3-l0 cfg3-l1 cfg3-l2 cfg3-l3 cfg4-resize cfg1-resize up2-hermite up3-robidoux; do
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$W -- python bench.py --workload $W --steps 60 --warmup 5 --no-cpu-baseline > $SUM/bench_$W.json 2> $OUT/trace_$W.err
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_$W -- python bench.py --full --workload $W --steps 60 --warmup 5 --no-cpu-baseline > $SUM/bench_$W.json 2> $OUT/trace_$W.err
   find $OUT/trace_$W -name '*kernel_stats.csv' -exec sh -c "head -1 {} > $SUM/${W}_kernel_stats.csv; grep -E 'fused_resample|generic' {} >> $SUM/${W}_kernel_stats.csv" \;
   rm -rf $OUT/trace_$W
 done
@@ -80,12 +80,12 @@ fi
 
 # 4. jobs: export_4_sizes, 1024-frame strong-scaling job on one GPU
 if want 4; then
-python bench.py --workload cfg3 --steps 50 --warmup 5 --no-cpu-baseline > $SUM/bench_cfg3_job.json 2>/dev/null
-python bench.py --workload cfg3 --outputs bgra --steps 50 --warmup 5 --no-cpu-baseline > $SUM/bench_cfg3_job_bgra.json 2>/dev/null
+python bench.py --full --workload cfg3 --steps 50 --warmup 5 --no-cpu-baseline > $SUM/bench_cfg3_job.json 2>/dev/null
+python bench.py --full --workload cfg3 --outputs bgra --steps 50 --warmup 5 --no-cpu-baseline > $SUM/bench_cfg3_job_bgra.json 2>/dev/null
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_cfg3job -- python bench.py --workload cfg3 --steps 20 --warmup 3 --no-cpu-baseline > /dev/null 2> $OUT/trace_cfg3job.err
 find $OUT/trace_cfg3job -name '*kernel_stats.csv' -exec sh -c "head -14 {} | cut -c1-220 > $SUM/cfg3_job_kernel_stats.csv" \;
 rm -rf $OUT/trace_cfg3job
-python bench.py --scaling strong --total-frames 1024 --steps 30 --warmup 5 --no-cpu-baseline > $SUM/bench_strong_1024_1gpu.json 2>/dev/null
+python bench.py --full --scaling strong --total-frames 1024 --steps 30 --warmup 5 --no-cpu-baseline > $SUM/bench_strong_1024_1gpu.json 2>/dev/null
 fi
 
 # 5. JPEG: pixel stage (cfg4 chain as one call / two calls), per-kernel statistics, HBM traffic of the chain; entropy chain
@@ -117,8 +117,8 @@ fi
 
 # 7. BASELINE config 4 as a bench.py workload (files -> entropy decode -> 4/8 pixel stage -> 800x450), line + kernel statistics
 if want 7; then
-python bench.py --workload cfg4 --steps 20 --warmup 5 > $SUM/bench_cfg4.json 2> $SUM/bench_cfg4.err
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_cfg4 -- python bench.py --workload cfg4 --steps 10 --warmup 3 --no-cpu-baseline > $SUM/bench_cfg4_under_trace.json 2> $OUT/trace_cfg4.err
+python bench.py --full --workload cfg4 --steps 20 --warmup 5 > $SUM/bench_cfg4.json 2> $SUM/bench_cfg4.err
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_cfg4 -- python bench.py --full --workload cfg4 --steps 10 --warmup 3 --no-cpu-baseline > $SUM/bench_cfg4_under_trace.json 2> $OUT/trace_cfg4.err
 find $OUT/trace_cfg4 -name '*kernel_stats.csv' -exec sh -c "head -14 {} | cut -c1-220 > $SUM/cfg4_kernel_stats.csv" \;
 rm -rf $OUT/trace_cfg4
 fi
