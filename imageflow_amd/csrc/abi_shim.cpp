@@ -20,6 +20,7 @@
 #include <chrono>
 #include <climits>
 #include <condition_variable>
+#include <cerrno>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -1233,6 +1234,35 @@ struct Job {
         cv->compose = compose; cv->matte = matte;
         return cv;
     }
+    // CropWhitespace (clone_crop_fill_expand.rs:564-627): detect_content (graphics/whitespace.rs:284-334) on the device, the
+    // 16-byte rectangle back with a wait for the job's stream only -- the crop box decides the next allocation, which is why
+    // the reference's estimate is Impossible -- then the padding and the ordinary Crop, shared-parent handling included
+    FramePtr crop_whitespace(const FramePtr& in, uint32_t threshold, float percent_padding, bool in_shared) {
+        uint32_t rect[4];
+        {
+            Timed t(this, "crop_whitespace");
+            uint32_t* d_rect = nullptr;
+            hip_check(job_malloc(reinterpret_cast<void**>(&d_rect), 16), "hipMalloc(rect)");
+            struct Guard { uint32_t* p; ~Guard() { job_free(p); } } g{d_rect};
+            check(ifhip_detect_content_batch_device(dev(in), in->bytes(), 1, in->w, in->h, in->stride, in->alpha ? 1 : 0, threshold, d_rect, t_job_stream));
+            hip_check(hipMemcpyAsync(rect, d_rect, sizeof rect, hipMemcpyDeviceToHost, t_job_stream), "download(rect)");
+            hip_check(static_cast<hipError_t>(ifhip::wait_stream(t_job_stream)), "crop_whitespace");
+        }
+        if (rect[2] <= rect[0] || rect[3] <= rect[1])                                 // :585-589
+            raise(kInternalError, "InvalidState: Whitespace detection returned invalid rectangle");
+        // `(percent_padding / 100f32 * (x2 - x1 + y2 - y1) as f32 / 2f32).ceil() as i64` (:590-593), saturating
+        const float pf = std::ceil(percent_padding / 100.0f * static_cast<float>(rect[2] - rect[0] + rect[3] - rect[1]) / 2.0f);
+        const int64_t pad = pf != pf ? 0 : pf >= 9.2233720e18f ? INT64_MAX : pf <= -9.2233720e18f ? INT64_MIN : static_cast<int64_t>(pf);
+        // i64 sums wrap and `as u32` truncates, as in a release build
+        auto add = [](int64_t a, int64_t b) { return static_cast<int64_t>(static_cast<uint64_t>(a) + static_cast<uint64_t>(b)); };
+        const int64_t neg = static_cast<int64_t>(0ull - static_cast<uint64_t>(pad));
+        const uint32_t x1 = static_cast<uint32_t>(std::max<int64_t>(0, add(rect[0], neg))), y1 = static_cast<uint32_t>(std::max<int64_t>(0, add(rect[1], neg)));
+        const uint32_t x2 = static_cast<uint32_t>(std::min<int64_t>(in->w, add(rect[2], pad))), y2 = static_cast<uint32_t>(std::min<int64_t>(in->h, add(rect[3], pad)));
+        Timed t(this, "crop_mutate");
+        FramePtr cv = crop_frame(in, x1, y1, x2, y2);
+        if (in_shared) { cv->compose = IFHIP_BLEND_WITH_SELF; cv->matte = 0; }        // as the Crop node below: MutProtect
+        return cv;
+    }
     // ExpandCanvas (:224-262): CreateCanvas of the colour (Bgra32 unless the colour is opaque) + CopyRectToCanvas
     FramePtr expand_frame(const FramePtr& in, uint32_t l, uint32_t t2, uint32_t r, uint32_t b, uint32_t color, bool color_is_keyword_transparent) {
         const uint64_t nw = static_cast<uint64_t>(in->w) + l + r, nh = static_cast<uint64_t>(in->h) + t2 + b;
@@ -1254,6 +1284,9 @@ struct Job {
         std::string down_filter;                 // `down.filter` (ir4/parsing.rs:580 -> layout.rs:527 ResampleHints::down_filter)
         int quality = -1, jpeg_quality = -1;     // `quality` / `jpeg.quality` (ir4/encoder.rs:74: jpeg.quality, else quality)
         bool jpeg_out = false;                   // `format=jpg|jpeg`
+        bool trim = false;                       // `trim.threshold` (i32) given: trim; `trim.percentpadding` (f32)
+        int32_t trim_threshold = 0;
+        float trim_padding = 0.f;
         size_t i = 0;
         const std::string& q = value->s;
         while (i < q.size()) {
@@ -1282,6 +1315,20 @@ struct Job {
                 if (v != "jpg" && v != "jpeg") raise(kActionNotSupported, "ActionNotSupported: querystring format=%s (this shim writes JPEG; PNG / GIF / WebP coders are out of scope)", v.c_str());
                 jpeg_out = true;
             }
+            else if (k == "trim.threshold" || k == "trim.percentpadding") {
+                // ir4/parsing.rs:534-537: parse_i32 / parse_f32 of the trimmed value; one that does not parse is ignored
+                const size_t b = v.find_first_not_of(" \t\r\n"), e = v.find_last_not_of(" \t\r\n");
+                const std::string s = b == std::string::npos ? std::string() : v.substr(b, e - b + 1);
+                char* end = nullptr;
+                errno = 0;
+                if (k == "trim.threshold") {
+                    const long long t2 = s.empty() ? 0 : std::strtoll(s.c_str(), &end, 10);
+                    if (end && end != s.c_str() && !*end && errno == 0 && t2 >= INT32_MIN && t2 <= INT32_MAX) { trim = true; trim_threshold = static_cast<int32_t>(t2); }
+                } else if (s.find_first_of("xXpP") == std::string::npos) {         // (Rust's f32 grammar has no hex floats)
+                    const float f = s.empty() ? 0.f : std::strtof(s.c_str(), &end);
+                    if (end && end != s.c_str() && !*end && std::isfinite(f)) trim_padding = f;
+                }
+            }
             else raise(kActionNotSupported, "ActionNotSupported: querystring key '%s'", k.c_str());
         }
         if (!(qw >= 0 && qw <= 2147483647.0) || !(qh >= 0 && qh <= 2147483647.0)) raise(kArgumentInvalid, "InvalidNodeParams: querystring width/height out of range");
@@ -1294,6 +1341,13 @@ struct Job {
         if (dec && dec->t == JVal::Num) image_size(static_cast<int32_t>(want_int(p, "decode", "command_string")), &src_w, &src_h, true);
         else if (in) { src_w = in->w; src_h = in->h; }
         else raise(kGraphInvalid, "GraphInvalid: command_string has neither a decode io nor an input frame");
+        if (trim) {
+            // Ir4Expand::translate (ir4/mod.rs:97-121): a decode WITHOUT downscale hints, CropWhitespace on the decoded frame,
+            // and the rest of the querystring laid out against the trimmed frame
+            if (dec && dec->t == JVal::Num) { in = decode_oriented(static_cast<int32_t>(dec->n), 0, 0, false, false); dec = nullptr; }
+            in = crop_whitespace(in, static_cast<uint32_t>(std::max<int32_t>(0, trim_threshold)), trim_padding, false);
+            src_w = in->w; src_h = in->h;
+        }
         auto target = [&](uint32_t sw, uint32_t sh, uint32_t* ow, uint32_t* oh) {        // mode=max: fit inside, never up-scale
             constrain_size("within", sw, sh, qw >= 1, qh >= 1, static_cast<int64_t>(qw), static_cast<int64_t>(qh), ow, oh);
         };
@@ -1651,6 +1705,13 @@ struct Job {
         if (name == "constrain") return constrain(in, p);
         if (name == "watermark") return watermark(in, p);
         if (name == "encode") { encode(in, static_cast<int32_t>(want_int(p, "io_id", "encode")), p.get("preset"), in_shared); return in; }
+        if (name == "crop_whitespace") {                                              // s::Node::CropWhitespace {threshold: u32, percent_padding: f32}
+            const int64_t thr = want_int(p, "threshold", "crop_whitespace");
+            if (thr < 0 || thr > 0xFFFFFFFFll) raise(kInvalidJson, "InvalidJson: crop_whitespace.threshold out of range");
+            const JVal* pp = p.get("percent_padding");
+            if (!pp || pp->t != JVal::Num) raise(kInvalidJson, "InvalidJson: crop_whitespace.percent_padding is a number");
+            return crop_whitespace(in, static_cast<uint32_t>(thr), static_cast<float>(pp->n), in_shared);
+        }
         Timed t(this, name == "fill_rect" ? "fill_rect_mutate" : name == "crop" ? "crop_mutate" : name == "flip_v" ? "flip_vertical_mutate" : name == "flip_h" ? "flip_vertical_mutate" /* sic: rotate_flip_transpose.rs:206 */
                       : name == "color_matrix_srgb" || name == "color_filter_srgb" ? "color_matrix_srgb_mut" : name == "expand_canvas" || name == "region" || name == "region_percent" ? "expand_canvas" : name == "transpose" ? "transpose_mut"
                       : name == "rotate_90" ? "rotate_90" : name == "rotate_180" ? "rotate_180" : name == "rotate_270" ? "rotate_270" : name == "apply_orientation" ? "apply_orientation" : "node");

@@ -26,6 +26,28 @@ def crop(b: Bitmap, x1, y1, x2, y2) -> Bitmap:
     return Bitmap(b.data[:, first:last], x2 - x1, y2 - y1, b.stride, b.alpha_meaningful, b.compose, b.matte)
 
 
+def crop_whitespace_rect(w, h, rect, percent_padding):
+    """CropWhitespaceDef::expand (:571-619) after detection: an empty rectangle is the reference's InvalidState error; the
+    padding is `(percent_padding / 100 * (w + h of the box) as f32 / 2).ceil() as i64`, the result clamped to the frame."""
+    import numpy as np
+    x1, y1, x2, y2 = rect
+    if x2 <= x1 or y2 <= y1:
+        raise FlowError(ErrorKind.InvalidState, "Whitespace detection returned invalid rectangle")
+    f = np.float32
+    p = float(np.ceil(f(percent_padding) / f(100) * f(x2 - x1 + y2 - y1) / f(2)))
+    pad = 0 if p != p else int(max(min(p, 2.0 ** 63 - 1), -2.0 ** 63))
+    return max(0, x1 - pad), max(0, y1 - pad), min(w, x2 + pad), min(h, y2 + pad)
+
+
+def crop_whitespace(b: Bitmap, threshold, percent_padding) -> Bitmap:
+    """CropWhitespaceDef::expand (:564-627): detect_content on the frame, pad, then Crop -- one rectangle for the batch, so
+    the batch must hold one frame (the reference's node sees one bitmap)."""
+    from ...graphics.whitespace import detect_content
+    if b.n != 1:
+        raise FlowError(ErrorKind.InvalidArgument, "crop_whitespace works on one frame")
+    return crop(b, *crop_whitespace_rect(b.w, b.h, detect_content(b, threshold)[0], percent_padding))
+
+
 def copy_rect_to_canvas(input: Bitmap, canvas: Bitmap, from_x, from_y, w, h, x, y) -> Bitmap:
     """CopyRectNodeDef::render (:31-90)."""
     if (input.w <= from_x or input.h <= from_y or input.w < from_x + w or input.h < from_y + h

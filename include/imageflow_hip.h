@@ -477,6 +477,17 @@ IFHIP_API int ifhip_transpose_batch_device(const uint8_t* d_from, size_t from_im
                                            uint32_t to_w, uint32_t to_h, uint32_t to_stride, uint32_t n_images,
                                            void* hip_stream);
 
+/* graphics::whitespace::detect_content (graphics/whitespace.rs:284-334, the search of :336-634): the content rectangle
+ * x1, y1, x2, y2 of each frame -- exactly the reference's sequential windowed search, not a whole-frame box.  Grey as
+ * approximate_grayscale: Bgra32 when alpha_meaningful, Bgr32 otherwise.  Frames narrower or shorter than 3 px and frames
+ * without energy give the whole frame.  d_rects: 4 uint32 per frame on the device, written on hip_stream (scratch comes
+ * from the library's stream cache).  The host form stages one bitmap and returns the rectangle in rect[4]. */
+IFHIP_API int ifhip_detect_content(const uint8_t* bgra, uint32_t w, uint32_t h, uint32_t stride, int alpha_meaningful,
+                                   uint32_t threshold, uint32_t* rect);
+IFHIP_API int ifhip_detect_content_batch_device(const uint8_t* d_bgra, size_t image_bytes, uint32_t n_images, uint32_t w,
+                                                uint32_t h, uint32_t stride, int alpha_meaningful, uint32_t threshold,
+                                                uint32_t* d_rects, void* hip_stream);
+
 /* ---- measurement helpers (bench.py) -------------------------------------------------------------------- */
 /* Runs `launches` back-to-back launches of the batch op on `hip_stream` bracketed by hipEvents on that stream
  * and returns the average milliseconds per launch. */
