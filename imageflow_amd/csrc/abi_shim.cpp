@@ -20,6 +20,7 @@
 #include <chrono>
 #include <climits>
 #include <condition_variable>
+#include <cctype>
 #include <cerrno>
 #include <cmath>
 #include <cstdarg>
@@ -251,6 +252,35 @@ uint32_t parse_color(const JVal* v, const char* node) {
         if (e != part.c_str() + 2) raise(kArgumentInvalid, "InvalidNodeParams: %s: bad colour '%s'", node, hex->s.c_str());
     }
     return (ch[3] << 24) | (ch[0] << 16) | (ch[1] << 8) | ch[2];
+}
+std::string trim_ascii(const std::string& v) {
+    const size_t b = v.find_first_not_of(" \t\r\n\f\v"), e = v.find_last_not_of(" \t\r\n\f\v");
+    return b == std::string::npos ? std::string() : v.substr(b, e - b + 1);
+}
+// `str::parse::<f64>` (core dec2flt): an optional sign, then `inf`, `infinity` or `nan` in any case, or digits with an
+// optional fraction (at least one digit in all) and an optional exponent; no blanks, no hex.  The value: strtod's, which
+// rounds correctly as Rust does.
+bool rust_parse_f64(const std::string& s, double* out) {
+    size_t i = (!s.empty() && (s[0] == '+' || s[0] == '-')) ? 1 : 0;
+    std::string rest = s.substr(i);
+    for (char& ch : rest) ch = static_cast<char>(std::tolower(static_cast<unsigned char>(ch)));
+    bool ok = rest == "inf" || rest == "infinity" || rest == "nan";
+    if (!ok) {
+        size_t j = 0, digits = 0;
+        while (j < rest.size() && std::isdigit(static_cast<unsigned char>(rest[j]))) { ++j; ++digits; }
+        if (j < rest.size() && rest[j] == '.') { ++j; while (j < rest.size() && std::isdigit(static_cast<unsigned char>(rest[j]))) { ++j; ++digits; } }
+        ok = digits > 0;
+        if (ok && j < rest.size() && rest[j] == 'e') {
+            ++j;
+            if (j < rest.size() && (rest[j] == '+' || rest[j] == '-')) ++j;
+            const size_t e0 = j;
+            while (j < rest.size() && std::isdigit(static_cast<unsigned char>(rest[j]))) ++j;
+            ok = j > e0;
+        }
+        ok = ok && j == rest.size();
+    }
+    if (ok) *out = std::strtod(s.c_str(), nullptr);
+    return ok;
 }
 // s::Color::Transparent, the enum value (a missing colour reads as it): the only colour create_canvas.rs:79-82 turns into a
 // ReplaceSelf canvas -- an srgb colour whose alpha is 0 still makes a BlendWithMatte canvas
@@ -1263,6 +1293,26 @@ struct Job {
         if (in_shared) { cv->compose = IFHIP_BLEND_WITH_SELF; cv->matte = 0; }        // as the Crop node below: MutProtect
         return cv;
     }
+    // RoundImageCorners (flow/nodes/round_corners.rs:22-93): EnableTransparency first when the colour is not opaque (:30-34,
+    // enable_transparency.rs:68-95), then the MutProtect'ed mutate node -- BlendWithSelf (:72-73) and
+    // flow_bitmap_bgra_clear_around_rounded_corners (graphics/rounded_corners.rs:187-346) on the device.  radii: JSON order.
+    FramePtr round_corners(const FramePtr& in, int mode, const float radii[4], uint32_t color) {
+        if ((color >> 24) != 255u && !in->alpha) {
+            check(ifhip_normalize_unused_alpha_batch_device(dev(in), in->bytes(), 1, in->w, in->h, in->stride, 0, t_job_stream));
+            in->alpha = true;
+        }
+        Timed t(this, "round_image_corners_mut");
+        in->compose = IFHIP_BLEND_WITH_SELF; in->matte = 0;
+        check(ifhip_round_corners_batch_device(dev(in), in->bytes(), 1, in->w, in->h, in->stride, mode, radii, color, t_job_stream));
+        return in;
+    }
+    // WhiteBalanceSrgbMutDef (flow/nodes/white_balance.rs:106-122): histograms, area thresholds and maps on the device;
+    // threshold None is the f32 0.006 (:77)
+    FramePtr white_balance(const FramePtr& in, float threshold) {
+        Timed t(this, "white_balance_srgb_mut");
+        check(ifhip_white_balance_batch_device(dev(in), in->bytes(), 1, in->w, in->h, in->stride, threshold, nullptr, t_job_stream));
+        return in;
+    }
     // ExpandCanvas (:224-262): CreateCanvas of the colour (Bgra32 unless the colour is opaque) + CopyRectToCanvas
     FramePtr expand_frame(const FramePtr& in, uint32_t l, uint32_t t2, uint32_t r, uint32_t b, uint32_t color, bool color_is_keyword_transparent) {
         const uint64_t nw = static_cast<uint64_t>(in->w) + l + r, nh = static_cast<uint64_t>(in->h) + t2 + b;
@@ -1274,7 +1324,7 @@ struct Job {
     // command_string {kind: "ir4", value: "width=200&..."}: the querystring form of BASELINE config 1.  Only the sizing
     // keys that reach the hot path (width/w, height/h, mode=max default; down.colorspace) -- imageflow_riapi is out of
     // scope.  JPEG pre-shrink hint exactly as Ir4Expand::get_decode_commands (imageflow_riapi/src/ir4/mod.rs:155-210).
-    FramePtr command_string(const JVal& p, FramePtr in) {
+    FramePtr command_string(const JVal& p, FramePtr in, bool in_shared = false) {
         const JVal* kind = p.get("kind");
         const JVal* value = p.get("value");
         if (!kind || kind->t != JVal::Str || kind->s != "ir4" || !value || value->t != JVal::Str)
@@ -1284,6 +1334,10 @@ struct Job {
         std::string down_filter;                 // `down.filter` (ir4/parsing.rs:580 -> layout.rs:527 ResampleHints::down_filter)
         int quality = -1, jpeg_quality = -1;     // `quality` / `jpeg.quality` (ir4/encoder.rs:74: jpeg.quality, else quality)
         bool jpeg_out = false;                   // `format=jpg|jpeg`
+        bool format_jpeg = false;                // `format=jpg|jpeg` itself (ir4/layout.rs:492-503: white corners); not `quality=abc`
+        bool round = false;                      // `s.roundcorners` (ir4/parsing.rs:811-840): 1 or 4 f64 values
+        double round_q[4] = {0, 0, 0, 0};
+        bool balance_white = false;              // `a.balancewhite=true|area` (:563-575)
         bool trim = false;                       // `trim.threshold` (i32) given: trim; `trim.percentpadding` (f32)
         int32_t trim_threshold = 0;
         float trim_padding = 0.f;
@@ -1314,6 +1368,36 @@ struct Job {
                 for (char& ch : v) ch = static_cast<char>(std::tolower(static_cast<unsigned char>(ch)));
                 if (v != "jpg" && v != "jpeg") raise(kActionNotSupported, "ActionNotSupported: querystring format=%s (this shim writes JPEG; PNG / GIF / WebP coders are out of scope)", v.c_str());
                 jpeg_out = true;
+                format_jpeg = true;
+            }
+            else if (k == "s.roundcorners") {
+                // warning_parse (:719-743) trims the value, and an empty one is no key; each comma-separated part is trimmed and
+                // parsed as an f64; a part that does not parse, or a count other than 1 or 4, is ignored with a warning
+                const std::string s = trim_ascii(v);
+                if (!s.empty()) {
+                    std::vector<double> vals;
+                    bool ok = true;
+                    size_t b = 0;
+                    while (ok) {
+                        const size_t c = std::min(s.find(',', b), s.size());
+                        double d = 0;
+                        ok = rust_parse_f64(trim_ascii(s.substr(b, c - b)), &d);
+                        vals.push_back(d);
+                        if (c == s.size()) break;
+                        b = c + 1;
+                    }
+                    if (ok && (vals.size() == 1 || vals.size() == 4)) {
+                        round = true;
+                        for (int j = 0; j < 4; ++j) round_q[j] = vals[vals.size() == 4 ? j : 0];
+                    }
+                }
+            }
+            else if (k == "a.balancewhite") {
+                // parse_white_balance (:1022-1033): a HistogramThresholdAlgorithm name in any case; only True and Area add the
+                // node (layout.rs:587-589), Simple and Gimp are kept with a warning and add nothing, other values are ignored
+                std::string s = trim_ascii(v);
+                for (char& ch : s) ch = static_cast<char>(std::tolower(static_cast<unsigned char>(ch)));
+                if (s == "true" || s == "area") balance_white = true;
             }
             else if (k == "trim.threshold" || k == "trim.percentpadding") {
                 // ir4/parsing.rs:534-537: parse_i32 / parse_f32 of the trimmed value; one that does not parse is ignored
@@ -1376,6 +1460,15 @@ struct Job {
             hints.o.emplace_back("background_color", bg);
         }
         FramePtr out = resample(in, ow, oh, &hints);
+        if ((round || balance_white) && out == in && in_shared) out = clone(out, true);      // both nodes are MutProtect
+        if (round) {
+            // ir4/layout.rs:531-549: Percentage when all four values are equal, else PercentageCustom {tl, tr, br, bl}; the
+            // colour is bgcolor, which defaults to white only for format=jpg|jpeg (:492-503)
+            const float radii[4] = {static_cast<float>(round_q[0]), static_cast<float>(round_q[1]), static_cast<float>(round_q[2]), static_cast<float>(round_q[3])};
+            const bool all_eq = round_q[0] == round_q[1] && round_q[0] == round_q[2] && round_q[0] == round_q[3];   // iter_all_eq (NaN: never)
+            out = round_corners(out, all_eq ? IFHIP_ROUND_CORNERS_PERCENTAGE : IFHIP_ROUND_CORNERS_PERCENTAGE_CUSTOM, radii, format_jpeg ? 0xFFFFFFFFu : 0u);
+        }
+        if (balance_white) out = white_balance(out, 0.006f);                                // (:590-592) threshold None
         if (enc && enc->t == JVal::Num) {
             // The reference keeps the source's format (a JPEG stays a JPEG, ir4/encoder.rs:30-37 OutputFormat::Keep) and hands
             // `jpeg.quality`, else `quality`, to its JPEG encoder (encoder.rs:74; 90 when neither is given, codecs/auto.rs).  Here a
@@ -1699,12 +1792,43 @@ struct Job {
             return new_frame(want_u32(p, "w", "create_canvas"), want_u32(p, "h", "create_canvas"), f == "bgra_32", parse_color(p.get("color"), "create_canvas.color"), true,
                              !keyword_transparent(p.get("color")));
         }
-        if (name == "command_string") return command_string(p, in);
+        if (name == "command_string") return command_string(p, in, in_shared);
         need_input();
         if (name == "resample_2d") return resample(in, want_u32(p, "w", "resample_2d"), want_u32(p, "h", "resample_2d"), p.get("hints"));
         if (name == "constrain") return constrain(in, p);
         if (name == "watermark") return watermark(in, p);
         if (name == "encode") { encode(in, static_cast<int32_t>(want_int(p, "io_id", "encode")), p.get("preset"), in_shared); return in; }
+        if (name == "round_image_corners") {                                          // s::Node::RoundImageCorners {radius, background_color}
+            const JVal* r = p.get("radius");
+            const JVal* bg = p.get("background_color");
+            if (!bg || bg->is_null()) raise(kInvalidJson, "InvalidJson: round_image_corners.background_color is required");
+            float radii[4] = {0, 0, 0, 0};
+            int mode = -1;
+            auto num = [&](const JVal* v, const char* what) -> float {
+                if (!v || v->t != JVal::Num) raise(kInvalidJson, "InvalidJson: round_image_corners.radius.%s is a number", what);
+                return static_cast<float>(v->n);
+            };
+            if (r && r->t == JVal::Str && r->s == "circle") mode = IFHIP_ROUND_CORNERS_CIRCLE;
+            else if (r && r->t == JVal::Obj && r->o.size() == 1) {                     // RoundCornersMode (lib.rs:1254-1268)
+                const std::string& key = r->o[0].first;
+                const JVal& v = r->o[0].second;
+                if (key == "percentage" || key == "pixels") {
+                    mode = key == "percentage" ? IFHIP_ROUND_CORNERS_PERCENTAGE : IFHIP_ROUND_CORNERS_PIXELS;
+                    radii[0] = radii[1] = radii[2] = radii[3] = num(&v, key.c_str());
+                } else if (key == "percentage_custom" || key == "pixels_custom") {
+                    mode = key == "percentage_custom" ? IFHIP_ROUND_CORNERS_PERCENTAGE_CUSTOM : IFHIP_ROUND_CORNERS_PIXELS_CUSTOM;
+                    radii[0] = num(v.get("top_left"), "top_left"); radii[1] = num(v.get("top_right"), "top_right");
+                    radii[2] = num(v.get("bottom_right"), "bottom_right"); radii[3] = num(v.get("bottom_left"), "bottom_left");
+                }
+            }
+            if (mode < 0) raise(kInvalidJson, "InvalidJson: round_image_corners.radius is {percentage|pixels: n}, \"circle\" or {percentage_custom|pixels_custom: {top_left, top_right, bottom_right, bottom_left}}");
+            return round_corners(in, mode, radii, parse_color(bg, "round_image_corners.background_color"));
+        }
+        if (name == "white_balance_histogram_area_threshold_srgb") {                  // s::Node::WhiteBalanceHistogramAreaThresholdSrgb {threshold: Option<f32>}
+            const JVal* th = p.get("threshold");
+            if (th && !th->is_null() && th->t != JVal::Num) raise(kInvalidJson, "InvalidJson: white_balance_histogram_area_threshold_srgb.threshold is a number or null");
+            return white_balance(in, th && th->t == JVal::Num ? static_cast<float>(th->n) : 0.006f);
+        }
         if (name == "crop_whitespace") {                                              // s::Node::CropWhitespace {threshold: u32, percent_padding: f32}
             const int64_t thr = want_int(p, "threshold", "crop_whitespace");
             if (thr < 0 || thr > 0xFFFFFFFFll) raise(kInvalidJson, "InvalidJson: crop_whitespace.threshold out of range");
@@ -1816,7 +1940,7 @@ struct Job {
     }
     static bool mutates_input(const std::string& nm) {
         return nm == "fill_rect" || nm == "flip_v" || nm == "flip_h" || nm == "rotate_180" || nm == "color_matrix_srgb" || nm == "color_filter_srgb" ||
-               nm == "apply_orientation" || nm == "watermark";
+               nm == "apply_orientation" || nm == "watermark" || nm == "round_image_corners" || nm == "white_balance_histogram_area_threshold_srgb";
     }
 
     void run_framewise(const JVal& fw) {

@@ -633,6 +633,13 @@ int resample_from_ycc_planes_v(const ifhip_resample_plan* plan, const uint8_t* d
 void resample_plan_shape(const ifhip_resample_plan* plan, uint32_t* in_w, uint32_t* in_h, uint32_t* out_w, uint32_t* out_h) {
     *in_w = plan->in_w; *in_h = plan->in_h; *out_w = plan->out_w; *out_h = plan->out_h;
 }
+int device_color_tables(const float** s2l, const uint8_t** l2s) {
+    DeviceTables tb;
+    const int rc = device_tables(&tb);
+    if (rc) return rc;
+    *s2l = tb.s2l; *l2s = tb.l2s;
+    return IFHIP_OK;
+}
 }  // namespace ifhip
 
 // ======================================================================================================

@@ -86,6 +86,8 @@ struct ColorTables {
     uint16_t l2s_thr[256]; // thr[k] = smallest i with l2s[i] >= k+1 (65535 if none): l2s[i] == #{k : thr[k] <= i}
 };
 const ColorTables& color_tables();
+// the current device's copies (api.cpp; uploaded once per device, never freed): s2l 256 floats, l2s 16384 bytes
+int device_color_tables(const float** s2l, const uint8_t** l2s);
 
 // ---------------------------------------------------------------------------------------------------
 // Vertical schedule for the fused kernel (our own construct; DESIGN.md "vertical schedule")

@@ -488,6 +488,36 @@ IFHIP_API int ifhip_detect_content_batch_device(const uint8_t* d_bgra, size_t im
                                                 uint32_t h, uint32_t stride, int alpha_meaningful, uint32_t threshold,
                                                 uint32_t* d_rects, void* hip_stream);
 
+/* graphics::rounded_corners::flow_bitmap_bgra_clear_around_rounded_corners (graphics/rounded_corners.rs:187-346; the pixel
+ * work of RoundImageCornersMut, flow/nodes/round_corners.rs:56-93), in place: outside the rounded corners every pixel
+ * becomes the matte's raw bytes, the anti-aliased ring blends the matte over the stored pixel in linear light.  mode is a
+ * RoundCornersMode (imageflow_types lib.rs:1254-1268); radii[4] are in the JSON order top_left, top_right, bottom_right,
+ * bottom_left (percentage / pixels / circle read radii[0] or nothing).  get_radius and plan_quadrants (:5-137) run on the
+ * host in f32; one launch applies the four quadrants in the reference's order.  The caller sets the frame's compositing
+ * to BlendWithSelf and, for a colour that is not opaque, runs EnableTransparency first (round_corners.rs:30-34, :72-73).
+ * The host form stages one bitmap. */
+typedef enum ifhip_round_corners_mode {
+    IFHIP_ROUND_CORNERS_PERCENTAGE = 0, IFHIP_ROUND_CORNERS_PIXELS = 1, IFHIP_ROUND_CORNERS_CIRCLE = 2,
+    IFHIP_ROUND_CORNERS_PERCENTAGE_CUSTOM = 3, IFHIP_ROUND_CORNERS_PIXELS_CUSTOM = 4
+} ifhip_round_corners_mode;
+IFHIP_API int ifhip_round_corners(uint8_t* bgra, uint32_t w, uint32_t h, uint32_t stride, int mode, const float* radii,
+                                  uint32_t matte_bgra);
+IFHIP_API int ifhip_round_corners_batch_device(uint8_t* d_bgra, size_t image_bytes, uint32_t n_images, uint32_t w,
+                                               uint32_t h, uint32_t stride, int mode, const float* radii,
+                                               uint32_t matte_bgra, void* hip_stream);
+
+/* WhiteBalanceSrgbMutDef::mutate (flow/nodes/white_balance.rs:106-122, the maps of :13-93, the counts of
+ * graphics/histogram.rs), in place: per frame, the R, G and B histograms, the area thresholds in f64 and the byte maps
+ * applied to R, G and B (alpha keeps its value).  threshold: the node's Option<f32>, None being 0.006f.  d_histograms
+ * (nullable, 8-byte aligned): receives the 3 x 256 counts of each frame, R then G then B, as uint64 [n_images][3][256];
+ * otherwise the counts live in scratch from the library's stream cache.  Two launches on hip_stream, no host wait.  The
+ * host form stages one bitmap; its `histograms` (nullable) is a host array of 768 counts. */
+IFHIP_API int ifhip_white_balance(uint8_t* bgra, uint32_t w, uint32_t h, uint32_t stride, float threshold,
+                                  uint64_t* histograms);
+IFHIP_API int ifhip_white_balance_batch_device(uint8_t* d_bgra, size_t image_bytes, uint32_t n_images, uint32_t w,
+                                               uint32_t h, uint32_t stride, float threshold, uint64_t* d_histograms,
+                                               void* hip_stream);
+
 /* ---- measurement helpers (bench.py) -------------------------------------------------------------------- */
 /* Runs `launches` back-to-back launches of the batch op on `hip_stream` bracketed by hipEvents on that stream
  * and returns the average milliseconds per launch. */
