@@ -17,8 +17,8 @@
 #include <tuple>
 #include <vector>
 
-#include "common.hpp"
 #include "device.hpp"
+#include "hip_entry.hpp"
 
 namespace ifhip {
 hipError_t launch_fused(const ResampleArgs& a, int slots, bool alpha, bool per_pixel, uint32_t grid, uint32_t block,
@@ -54,13 +54,6 @@ struct DeviceBuffer {
     ~DeviceBuffer() { if (p) (void)hipFree(p); }
 };
 }  // namespace
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess)                                                                          \
-            return fail(IFHIP_GPU_ERROR, "GpuError: %s failed: %s", #expr, hipGetErrorString(e__));     \
-    } while (0)
 
 namespace {
 
@@ -1169,12 +1162,10 @@ int ifhip_apply_matte_batch_device(uint8_t* d_bgra, size_t image_bytes, uint32_t
                                    uint32_t stride, int alpha_meaningful, uint32_t matte_bgra, void* hip_stream) {
     if (!alpha_meaningful) return IFHIP_OK;                       // blend.rs:11-13
     if (w == 0 || h == 0 || n_images == 0) return IFHIP_OK;
-    if (!d_bgra) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null bitmap pointer");
-    if (static_cast<uint64_t>(w) * 4u > stride || (stride & 3u) || (image_bytes & 3u) || (reinterpret_cast<uintptr_t>(d_bgra) & 3u))
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: BGRA rows must be 4-byte aligned and stride >= 4*w");
-    DeviceTables tb;
-    int rc = device_tables(&tb);
+    int rc = check_frames(d_bgra, image_bytes, w, h, stride, "bitmap");
     if (rc) return rc;
+    DeviceTables tb;
+    if ((rc = device_tables(&tb))) return rc;
     const ColorTables& t = color_tables();
     HIP_TRY(launch_apply_matte(d_bgra, image_bytes, n_images, w, h, stride, matte_bgra, t.s2l[matte_bgra & 255u],
                                t.s2l[(matte_bgra >> 8) & 255u], t.s2l[(matte_bgra >> 16) & 255u],

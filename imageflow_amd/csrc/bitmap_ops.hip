@@ -11,16 +11,8 @@
 #include <hip/hip_runtime.h>
 
 #include <cstring>
-#include <mutex>
 
-#include "common.hpp"
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess)                                                                          \
-            return fail(IFHIP_GPU_ERROR, "GpuError: %s failed: %s", #expr, hipGetErrorString(e__));     \
-    } while (0)
+#include "hip_entry.hpp"
 
 namespace ifhip {
 
@@ -148,26 +140,9 @@ __global__ void __launch_bounds__(256) transpose_kernel(const Frames from, const
     }
 }
 
-static int require_device() {
-    static std::mutex mu;
-    static int ok_device = -1;
-    int dev = -1;
-    if (hipGetDevice(&dev) != hipSuccess)
-        return fail(IFHIP_GPU_UNAVAILABLE, "GpuUnavailable: no HIP device; this library has no CPU path");
-    std::lock_guard<std::mutex> lock(mu);
-    if (dev == ok_device) return IFHIP_OK;
-    hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, dev));
-    if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(IFHIP_GPU_UNAVAILABLE, "GpuUnavailable: device %d is %s, this library is built for gfx950 only", dev, prop.gcnArchName);
-    ok_device = dev;
-    return IFHIP_OK;
-}
-
-static int check_frames(const void* p, size_t image_bytes, uint32_t w, uint32_t h, uint32_t stride, uint32_t n, const char* what) {
-    if (!p) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null %s pointer", what);
-    if (static_cast<uint64_t>(w) * 4u > stride || (stride & 3u) || (image_bytes & 3u) || (reinterpret_cast<uintptr_t>(p) & 3u))
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: %s rows must be 4-byte aligned and stride >= 4*w", what);
+// the shared frame check and the caps of these launches: rows in grid.y, images in grid.z
+static int check_batch(const void* p, size_t image_bytes, uint32_t n, uint32_t w, uint32_t h, uint32_t stride, const char* what) {
+    if (int rc = check_frames(p, image_bytes, w, h, stride, what)) return rc;
     if (h > 65535u || n > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: more than 65535 rows/images per launch");
     return IFHIP_OK;
 }
@@ -191,31 +166,6 @@ static int set_alpha_255(const Frames& f, uint32_t n, hipStream_t st) {        /
     return launch_rect<kOrMask>(a, f.h, n, st);
 }
 
-// host-buffer drop-ins: stage one bitmap through HBM around a device call
-struct Staged {
-    uint8_t* d = nullptr;
-    size_t bytes = 0, valid = 0;
-    ~Staged() { if (d) (void)hipFree(d); }
-    int up(const uint8_t* host, uint32_t w, uint32_t h, uint32_t stride, bool copy) {
-        if (w == 0 || h == 0) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Bitmap dimensions cannot be zero");
-        if (!host) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null bitmap pointer");
-        if (static_cast<uint64_t>(w) * 4u > stride || (stride & 3u))
-            return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: stride smaller than a BGRA row or not a multiple of 4");
-        valid = static_cast<size_t>(h - 1) * stride + static_cast<size_t>(w) * 4u;
-        bytes = (static_cast<size_t>(h) * stride + 15u) & ~static_cast<size_t>(15);
-        int rc = require_device();
-        if (rc) return rc;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), bytes));
-        if (copy) HIP_TRY(hipMemcpy(d, host, valid, hipMemcpyHostToDevice));
-        return IFHIP_OK;
-    }
-    int down(uint8_t* host) {
-        HIP_TRY(hipStreamSynchronize(nullptr));
-        HIP_TRY(hipMemcpy(host, d, valid, hipMemcpyDeviceToHost));
-        return IFHIP_OK;
-    }
-};
-
 }  // namespace ifhip
 
 using namespace ifhip;
@@ -226,9 +176,9 @@ int ifhip_apply_color_matrix_batch_device(uint8_t* d_bgra, size_t image_bytes, u
                                           uint32_t stride, const float* matrix25, void* hip_stream) {
     if (!matrix25) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null matrix");
     if (w == 0 || h == 0 || n_images == 0) return IFHIP_OK;
-    int rc = check_frames(d_bgra, image_bytes, w, h, stride, n_images, "bitmap");
+    int rc = check_batch(d_bgra, image_bytes, n_images, w, h, stride, "bitmap");
     if (rc) return rc;
-    if ((rc = require_device())) return rc;
+    if ((rc = require_gfx950(nullptr))) return rc;
     Matrix5 k;
     std::memcpy(k.m, matrix25, sizeof k.m);
     const Frames f{d_bgra, image_bytes, w, h, stride};
@@ -239,10 +189,10 @@ int ifhip_apply_color_matrix_batch_device(uint8_t* d_bgra, size_t image_bytes, u
 }
 
 int ifhip_apply_color_matrix(uint8_t* bgra, uint32_t w, uint32_t h, uint32_t stride, const float* matrix25) {
-    Staged s;
-    int rc = s.up(bgra, w, h, stride, true);
+    HostFrame s;
+    int rc = s.up(bgra, w, h, stride);
     if (rc) return rc;
-    if ((rc = ifhip_apply_color_matrix_batch_device(s.d, s.bytes, 1, w, h, stride, matrix25, nullptr))) return rc;
+    if ((rc = ifhip_apply_color_matrix_batch_device(s.d, s.image_bytes, 1, w, h, stride, matrix25, nullptr))) return rc;
     return s.down(bgra);
 }
 
@@ -257,11 +207,11 @@ int ifhip_copy_rect_batch_device(uint8_t* d_in, size_t in_image_bytes, uint32_t 
         static_cast<uint64_t>(canvas_h) < static_cast<uint64_t>(to_y) + h)
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Invalid argument to copy_rect. Canvas is %ux%u, Input is %ux%u, Arguments provided: (%u, %u, %u, %u, %u, %u)",
                     canvas_w, canvas_h, in_w, in_h, from_x, from_y, to_x, to_y, w, h);
-    int rc = check_frames(d_in, in_image_bytes, in_w, in_h, in_stride, n_images, "input");
+    int rc = check_batch(d_in, in_image_bytes, n_images, in_w, in_h, in_stride, "input");
     if (rc) return rc;
-    if ((rc = check_frames(d_canvas, canvas_image_bytes, canvas_w, canvas_h, canvas_stride, n_images, "canvas"))) return rc;
+    if ((rc = check_batch(d_canvas, canvas_image_bytes, n_images, canvas_w, canvas_h, canvas_stride, "canvas"))) return rc;
     if (d_in == d_canvas) return fail(IFHIP_INVALID_ARGUMENT, "InvalidNodeConnections: Canvas and Input are the same bitmap!");
-    if ((rc = require_device())) return rc;
+    if ((rc = require_gfx950(nullptr))) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const Frames in{d_in, in_image_bytes, in_w, in_h, in_stride}, cv{d_canvas, canvas_image_bytes, canvas_w, canvas_h, canvas_stride};
     if (!*canvas_alpha_meaningful && in_alpha_meaningful) {          // copy_rect.rs:47-54
@@ -284,9 +234,9 @@ int ifhip_fill_rect_batch_device(uint8_t* d_bgra, size_t image_bytes, uint32_t n
     if (y2 == y1 || x2 == x1) return IFHIP_OK;                       // "Don't fail on zero width rect"
     if (y2 <= y1 || x2 <= x1 || x2 > w || y2 > h)
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Coordinates %u,%u %u,%u must be within image dimensions %ux%u", x1, y1, x2, y2, w, h);
-    int rc = check_frames(d_bgra, image_bytes, w, h, stride, n_images, "bitmap");
+    int rc = check_batch(d_bgra, image_bytes, n_images, w, h, stride, "bitmap");
     if (rc) return rc;
-    if ((rc = require_device())) return rc;
+    if ((rc = require_gfx950(nullptr))) return rc;
     RectArgs a{};
     a.dst = Frames{d_bgra, image_bytes, w, h, stride};
     a.dx = x1; a.dy = y1; a.w = x2 - x1; a.h = y2 - y1; a.value = color_bgra; a.vec = aligned16(a.dst, x1) ? 1u : 0u;
@@ -297,18 +247,18 @@ int ifhip_normalize_unused_alpha_batch_device(uint8_t* d_bgra, size_t image_byte
                                               uint32_t stride, int alpha_meaningful, void* hip_stream) {
     if (alpha_meaningful) return IFHIP_OK;                           // bitmaps.rs:1571-1573
     if (w == 0 || h == 0 || n_images == 0) return IFHIP_OK;
-    int rc = check_frames(d_bgra, image_bytes, w, h, stride, n_images, "bitmap");
+    int rc = check_batch(d_bgra, image_bytes, n_images, w, h, stride, "bitmap");
     if (rc) return rc;
-    if ((rc = require_device())) return rc;
+    if ((rc = require_gfx950(nullptr))) return rc;
     return set_alpha_255(Frames{d_bgra, image_bytes, w, h, stride}, n_images, static_cast<hipStream_t>(hip_stream));
 }
 
 int ifhip_flip_vertical_batch_device(uint8_t* d_bgra, size_t image_bytes, uint32_t n_images, uint32_t w, uint32_t h,
                                      uint32_t stride, void* hip_stream) {
     if (w == 0 || h == 0 || n_images == 0) return IFHIP_OK;
-    int rc = check_frames(d_bgra, image_bytes, w, h, stride, n_images, "bitmap");
+    int rc = check_batch(d_bgra, image_bytes, n_images, w, h, stride, "bitmap");
     if (rc) return rc;
-    if ((rc = require_device())) return rc;
+    if ((rc = require_gfx950(nullptr))) return rc;
     RectArgs a{};
     a.src = a.dst = Frames{d_bgra, image_bytes, w, h, stride};
     a.w = w; a.h = h / 2u;                 // row y of the top half <-> row h-1-y:  sy + (2*(h/2) - 1 - y + value) = h-1-y
@@ -320,9 +270,9 @@ int ifhip_flip_vertical_batch_device(uint8_t* d_bgra, size_t image_bytes, uint32
 int ifhip_flip_horizontal_batch_device(uint8_t* d_bgra, size_t image_bytes, uint32_t n_images, uint32_t w, uint32_t h,
                                        uint32_t stride, void* hip_stream) {
     if (w < 2u || h == 0 || n_images == 0) return IFHIP_OK;
-    int rc = check_frames(d_bgra, image_bytes, w, h, stride, n_images, "bitmap");
+    int rc = check_batch(d_bgra, image_bytes, n_images, w, h, stride, "bitmap");
     if (rc) return rc;
-    if ((rc = require_device())) return rc;
+    if ((rc = require_gfx950(nullptr))) return rc;
     const Frames f{d_bgra, image_bytes, w, h, stride};
     hipLaunchKernelGGL(flip_h_kernel, dim3((w / 2u + 255u) / 256u, h, n_images), dim3(256), 0, static_cast<hipStream_t>(hip_stream), f);
     HIP_TRY(hipGetLastError());
@@ -335,11 +285,11 @@ int ifhip_transpose_batch_device(const uint8_t* d_from, size_t from_image_bytes,
     if (from_w != to_h || from_h != to_w)
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: For transposition, canvas and input formats must be the same and dimensions must be swapped");
     if (from_w == 0 || from_h == 0 || n_images == 0) return IFHIP_OK;
-    int rc = check_frames(d_from, from_image_bytes, from_w, from_h, from_stride, n_images, "input");
+    int rc = check_batch(d_from, from_image_bytes, n_images, from_w, from_h, from_stride, "input");
     if (rc) return rc;
-    if ((rc = check_frames(d_to, to_image_bytes, to_w, to_h, to_stride, n_images, "canvas"))) return rc;
+    if ((rc = check_batch(d_to, to_image_bytes, n_images, to_w, to_h, to_stride, "canvas"))) return rc;
     if (d_from == d_to) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Canvas and input must be different bitmaps for transpose to work!");
-    if ((rc = require_device())) return rc;
+    if ((rc = require_gfx950(nullptr))) return rc;
     const Frames f{const_cast<uint8_t*>(d_from), from_image_bytes, from_w, from_h, from_stride}, t{d_to, to_image_bytes, to_w, to_h, to_stride};
     const dim3 grid((from_w + 63u) / 64u, (from_h + 63u) / 64u, n_images);
     if (grid.y > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: bitmap too tall for one launch");
@@ -352,13 +302,13 @@ int ifhip_copy_rect(uint8_t* input, uint32_t in_w, uint32_t in_h, uint32_t in_st
                     uint32_t canvas_w, uint32_t canvas_h, uint32_t canvas_stride, int* canvas_alpha_meaningful, uint32_t from_x,
                     uint32_t from_y, uint32_t to_x, uint32_t to_y, uint32_t w, uint32_t h) {
     if (!canvas_alpha_meaningful) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null canvas_alpha_meaningful");
-    Staged si, sc;
-    int rc = si.up(input, in_w, in_h, in_stride, true);
+    HostFrame si, sc;
+    int rc = si.up(input, in_w, in_h, in_stride);
     if (rc) return rc;
-    if ((rc = sc.up(canvas, canvas_w, canvas_h, canvas_stride, true))) return rc;
+    if ((rc = sc.up(canvas, canvas_w, canvas_h, canvas_stride))) return rc;
     const int in_was = in_alpha_meaningful, cv_was = *canvas_alpha_meaningful;
-    rc = ifhip_copy_rect_batch_device(si.d, si.bytes, in_w, in_h, in_stride, in_alpha_meaningful, sc.d, sc.bytes, canvas_w, canvas_h,
-                                      canvas_stride, canvas_alpha_meaningful, from_x, from_y, to_x, to_y, w, h, 1, nullptr);
+    rc = ifhip_copy_rect_batch_device(si.d, si.image_bytes, in_w, in_h, in_stride, in_alpha_meaningful, sc.d, sc.image_bytes, canvas_w,
+                                      canvas_h, canvas_stride, canvas_alpha_meaningful, from_x, from_y, to_x, to_y, w, h, 1, nullptr);
     if (rc) return rc;
     if (!in_was && (cv_was || *canvas_alpha_meaningful) && (rc = si.down(input))) return rc;      // the input was normalised
     return sc.down(canvas);
@@ -366,26 +316,26 @@ int ifhip_copy_rect(uint8_t* input, uint32_t in_w, uint32_t in_h, uint32_t in_st
 
 int ifhip_fill_rect(uint8_t* bgra, uint32_t w, uint32_t h, uint32_t stride, int compositing, uint32_t x1, uint32_t y1,
                     uint32_t x2, uint32_t y2, uint32_t color_bgra) {
-    Staged s;
-    int rc = s.up(bgra, w, h, stride, true);
+    HostFrame s;
+    int rc = s.up(bgra, w, h, stride);
     if (rc) return rc;
-    if ((rc = ifhip_fill_rect_batch_device(s.d, s.bytes, 1, w, h, stride, compositing, x1, y1, x2, y2, color_bgra, nullptr))) return rc;
+    if ((rc = ifhip_fill_rect_batch_device(s.d, s.image_bytes, 1, w, h, stride, compositing, x1, y1, x2, y2, color_bgra, nullptr))) return rc;
     return s.down(bgra);
 }
 
 int ifhip_flip_vertical(uint8_t* bgra, uint32_t w, uint32_t h, uint32_t stride) {
-    Staged s;
-    int rc = s.up(bgra, w, h, stride, true);
+    HostFrame s;
+    int rc = s.up(bgra, w, h, stride);
     if (rc) return rc;
-    if ((rc = ifhip_flip_vertical_batch_device(s.d, s.bytes, 1, w, h, stride, nullptr))) return rc;
+    if ((rc = ifhip_flip_vertical_batch_device(s.d, s.image_bytes, 1, w, h, stride, nullptr))) return rc;
     return s.down(bgra);
 }
 
 int ifhip_flip_horizontal(uint8_t* bgra, uint32_t w, uint32_t h, uint32_t stride) {
-    Staged s;
-    int rc = s.up(bgra, w, h, stride, true);
+    HostFrame s;
+    int rc = s.up(bgra, w, h, stride);
     if (rc) return rc;
-    if ((rc = ifhip_flip_horizontal_batch_device(s.d, s.bytes, 1, w, h, stride, nullptr))) return rc;
+    if ((rc = ifhip_flip_horizontal_batch_device(s.d, s.image_bytes, 1, w, h, stride, nullptr))) return rc;
     return s.down(bgra);
 }
 
@@ -393,11 +343,11 @@ int ifhip_transpose(const uint8_t* from, uint32_t from_w, uint32_t from_h, uint3
                     uint32_t to_h, uint32_t to_stride) {
     if (from_w != to_h || from_h != to_w)
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: For transposition, canvas and input formats must be the same and dimensions must be swapped");
-    Staged sf, st;
-    int rc = sf.up(from, from_w, from_h, from_stride, true);
+    HostFrame sf, st;
+    int rc = sf.up(from, from_w, from_h, from_stride);
     if (rc) return rc;
-    if ((rc = st.up(to, to_w, to_h, to_stride, true))) return rc;          // row padding of the canvas is preserved
-    if ((rc = ifhip_transpose_batch_device(sf.d, sf.bytes, from_w, from_h, from_stride, st.d, st.bytes, to_w, to_h, to_stride, 1, nullptr))) return rc;
+    if ((rc = st.up(to, to_w, to_h, to_stride))) return rc;                // row padding of the canvas is preserved
+    if ((rc = ifhip_transpose_batch_device(sf.d, sf.image_bytes, from_w, from_h, from_stride, st.d, st.image_bytes, to_w, to_h, to_stride, 1, nullptr))) return rc;
     return st.down(to);
 }
 

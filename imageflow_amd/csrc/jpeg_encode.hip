@@ -24,15 +24,8 @@
 #include <memory>
 #include <vector>
 
-#include "common.hpp"
+#include "hip_entry.hpp"
 #include "jpeg_encode_core.hpp"
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess)                                                                          \
-            return fail(IFHIP_GPU_ERROR, "GpuError: %s failed: %s", #expr, hipGetErrorString(e__));     \
-    } while (0)
 
 namespace ifhip {
 

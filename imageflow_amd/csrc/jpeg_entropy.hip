@@ -34,14 +34,7 @@
 #include <cstdio>
 #include <vector>
 
-#include "common.hpp"
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess)                                                                          \
-            return fail(IFHIP_GPU_ERROR, "GpuError: %s failed: %s", #expr, hipGetErrorString(e__));     \
-    } while (0)
+#include "hip_entry.hpp"
 
 namespace ifhip {
 

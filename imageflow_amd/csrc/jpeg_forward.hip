@@ -14,14 +14,7 @@
 #include <cstring>
 #include <memory>
 
-#include "common.hpp"
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess)                                                                          \
-            return fail(IFHIP_GPU_ERROR, "GpuError: %s failed: %s", #expr, hipGetErrorString(e__));     \
-    } while (0)
+#include "hip_entry.hpp"
 
 namespace ifhip {
 
@@ -342,8 +335,7 @@ int ifhip_jpeg_forward_batch_device(ifhip_jpeg_fwd_stage* stage, const uint8_t* 
     if (n_images == 0) return IFHIP_OK;
     if (n_images > stage->max_images) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: %u images exceed the stage capacity %u", n_images, stage->max_images);
     if (!d_bgra || !d_qt || !d_coef0 || !d_coef1 || !d_coef2) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
-    if (static_cast<uint64_t>(stage->g.width) * 4u > stride || (stride & 3u) || (image_bytes & 3u) || (reinterpret_cast<uintptr_t>(d_bgra) & 3u))
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: BGRA rows must be 4-byte aligned and stride >= 4*w");
+    if (int rc = check_frames(d_bgra, image_bytes, stage->g.width, stage->g.height, stride, "BGRA")) return rc;
     if ((reinterpret_cast<uintptr_t>(d_coef0) | reinterpret_cast<uintptr_t>(d_coef1) | reinterpret_cast<uintptr_t>(d_coef2)) & 15u)
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: coefficient planes must be 16-byte aligned");
     int dev = -1;
@@ -375,34 +367,21 @@ int ifhip_jpeg_forward(const uint8_t* bgra, uint32_t width, uint32_t height, uin
     int rc = ifhip_jpeg_fwd_stage_create(&stage, width, height, h_samp, v_samp, 1);
     if (rc) return rc;
     std::unique_ptr<ifhip_jpeg_fwd_stage> guard(stage);
-    if (static_cast<uint64_t>(width) * 4u > stride || (stride & 3u))
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: stride smaller than a BGRA row or not a multiple of 4");
-    const size_t in_bytes = static_cast<size_t>(height) * stride, in_valid = static_cast<size_t>(height - 1) * stride + static_cast<size_t>(width) * 4u;
-    uint8_t* d_in = nullptr;
-    uint16_t* d_qt = nullptr;
-    int16_t* d_c[3] = {nullptr, nullptr, nullptr};
-    int16_t* h_c[3] = {coef0, coef1, coef2};
-    size_t cb[3] = {0, 0, 0};
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_in), in_bytes);
-    if (e == hipSuccess) e = hipMemcpy(d_in, bgra, in_valid, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&d_qt), 384);
-    if (e == hipSuccess) e = hipMemcpy(d_qt, qt, 384, hipMemcpyHostToDevice);
-    for (int c = 0; c < 3 && e == hipSuccess; ++c) {
+    HostFrame in;
+    if ((rc = in.up(bgra, width, height, stride))) return rc;
+    DeviceBlock d_qt, d_c[3];
+    HIP_TRY(d_qt.alloc(384));
+    HIP_TRY(hipMemcpy(d_qt.p, qt, 384, hipMemcpyHostToDevice));
+    size_t cb[3];
+    for (int c = 0; c < 3; ++c) {
         cb[c] = static_cast<size_t>(stage->g.bw[c]) * stage->g.bh[c] * 128u;
-        e = hipMalloc(reinterpret_cast<void**>(&d_c[c]), cb[c]);
+        HIP_TRY(d_c[c].alloc(cb[c]));
     }
-    if (e == hipSuccess) {
-        rc = ifhip_jpeg_forward_batch_device(stage, d_in, in_bytes, stride, d_qt, 1, d_c[0], d_c[1], d_c[2], nullptr);
-        if (rc == IFHIP_OK) {
-            e = hipStreamSynchronize(nullptr);
-            for (int c = 0; c < 3 && e == hipSuccess; ++c) e = hipMemcpy(h_c[c], d_c[c], cb[c], hipMemcpyDeviceToHost);
-        }
-    }
-    if (d_in) (void)hipFree(d_in);
-    if (d_qt) (void)hipFree(d_qt);
-    for (auto* p : d_c) if (p) (void)hipFree(p);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(IFHIP_GPU_ERROR, "GpuError: jpeg forward staging failed: %s", hipGetErrorString(e));
+    if ((rc = ifhip_jpeg_forward_batch_device(stage, in.d, in.image_bytes, stride, d_qt.as<uint16_t>(), 1, d_c[0].as<int16_t>(),
+                                              d_c[1].as<int16_t>(), d_c[2].as<int16_t>(), nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    int16_t* h_c[3] = {coef0, coef1, coef2};
+    for (int c = 0; c < 3; ++c) HIP_TRY(hipMemcpy(h_c[c], d_c[c].p, cb[c], hipMemcpyDeviceToHost));
     return IFHIP_OK;
 }
 

@@ -22,7 +22,7 @@
 #include <memory>
 #include <mutex>
 
-#include "common.hpp"
+#include "hip_entry.hpp"
 
 namespace ifhip {
 
@@ -1030,13 +1030,6 @@ __global__ void __launch_bounds__(256) jpeg_color_kernel(const JpegArgs a) {
 using namespace ifhip;
 #include "block_scalers.hpp"
 
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess)                                                                          \
-            return fail(IFHIP_GPU_ERROR, "GpuError: %s failed: %s", #expr, hipGetErrorString(e__));     \
-    } while (0)
-
 namespace {
 struct ScalerDeviceTables { uint16_t* s2l = nullptr; uint8_t* l2s = nullptr; };
 std::mutex g_sc_mu;
@@ -1247,12 +1240,10 @@ int ifhip_jpeg_idct_color_batch_device(ifhip_jpeg_stage* stage, const int16_t* d
                                        uint8_t* d_bgra, size_t image_bytes, uint32_t stride, void* hip_stream) {
     if (!stage) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null stage");
     if (n_images == 0) return IFHIP_OK;
-    if (!d_bgra) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null coefficient / table / bitmap pointer");
-    if (static_cast<uint64_t>(stage->g.out_w) * 4u > stride || (stride & 3u) || (image_bytes & 3u) || (reinterpret_cast<uintptr_t>(d_bgra) & 3u))
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: BGRA rows must be 4-byte aligned and stride >= 4*w");
-    JpegArgs a;
-    int rc = stage_args(stage, d_coef0, d_coef1, d_coef2, d_qt, n_images, &a);
+    int rc = check_frames(d_bgra, image_bytes, stage->g.out_w, stage->g.out_h, stride, "BGRA");
     if (rc) return rc;
+    JpegArgs a;
+    if ((rc = stage_args(stage, d_coef0, d_coef1, d_coef2, d_qt, n_images, &a))) return rc;
     a.bgra = d_bgra; a.image_bytes = image_bytes; a.stride = stride;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     // full-size colour decode: the luma IDCT runs inside the colour kernel (no luma plane in HBM)
@@ -1332,39 +1323,22 @@ int ifhip_jpeg_idct_color(const int16_t* coef0, const int16_t* coef1, const int1
     if (static_cast<uint64_t>(g.out_w) * 4u > stride || (stride & 3u))
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: stride smaller than a BGRA row or not a multiple of 4");
     ifhip_jpeg_stage* stage = nullptr;
-    rc = ifhip_jpeg_stage_create(&stage, width, height, n_components, h_samp, v_samp, scale_num, luma_spatial, luma_srgb, 1);
-    width = g.out_w; height = g.out_h;          // the bitmap the caller handed in has the scaled size
-    if (rc) return rc;
+    if ((rc = ifhip_jpeg_stage_create(&stage, width, height, n_components, h_samp, v_samp, scale_num, luma_spatial, luma_srgb, 1))) return rc;
     std::unique_ptr<ifhip_jpeg_stage> guard(stage);
+    HostFrame out;                              // the bitmap the caller handed in has the scaled size
+    if ((rc = out.up(bgra, g.out_w, g.out_h, stride))) return rc;
     const int16_t* hc[3] = {coef0, coef1, coef2};
-    int16_t* dc[3] = {nullptr, nullptr, nullptr};
-    uint16_t* dq = nullptr;
-    uint8_t* dout = nullptr;
-    const size_t out_bytes = static_cast<size_t>(height) * stride;
-    hipError_t e = hipSuccess;
-    for (int c = 0; c < n_components && e == hipSuccess; ++c) {
+    DeviceBlock dc[3], dq;
+    for (int c = 0; c < n_components; ++c) {
         const size_t bytes = static_cast<size_t>(g.bw[c]) * g.bh[c] * 128u;
-        e = hipMalloc(reinterpret_cast<void**>(&dc[c]), bytes);
-        if (e == hipSuccess) e = hipMemcpy(dc[c], hc[c], bytes, hipMemcpyHostToDevice);
+        HIP_TRY(dc[c].alloc(bytes));
+        HIP_TRY(hipMemcpy(dc[c].p, hc[c], bytes, hipMemcpyHostToDevice));
     }
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dq), 128u * n_components);
-    if (e == hipSuccess) e = hipMemcpy(dq, qt, 128u * n_components, hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&dout), out_bytes);
-    if (e == hipSuccess) e = hipMemcpy(dout, bgra, static_cast<size_t>(height - 1) * stride + static_cast<size_t>(width) * 4u, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        rc = ifhip_jpeg_idct_color_batch_device(stage, dc[0], dc[1], dc[2], dq, 1, dout, out_bytes, stride, nullptr);
-        if (rc == IFHIP_OK) {
-            e = hipStreamSynchronize(nullptr);
-            if (e == hipSuccess)
-                e = hipMemcpy(bgra, dout, static_cast<size_t>(height - 1) * stride + static_cast<size_t>(width) * 4u, hipMemcpyDeviceToHost);
-        }
-    }
-    for (auto* p : dc) if (p) (void)hipFree(p);
-    if (dq) (void)hipFree(dq);
-    if (dout) (void)hipFree(dout);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(IFHIP_GPU_ERROR, "GpuError: jpeg stage staging failed: %s", hipGetErrorString(e));
-    return IFHIP_OK;
+    HIP_TRY(dq.alloc(128u * n_components));
+    HIP_TRY(hipMemcpy(dq.p, qt, 128u * n_components, hipMemcpyHostToDevice));
+    if ((rc = ifhip_jpeg_idct_color_batch_device(stage, dc[0].as<int16_t>(), dc[1].as<int16_t>(), dc[2].as<int16_t>(), dq.as<uint16_t>(),
+                                                 1, out.d, out.image_bytes, stride, nullptr))) return rc;
+    return out.down(bgra);
 }
 
 }  // extern "C"
@@ -1472,24 +1446,16 @@ int ifhip_scale_spatial_blocks(const uint8_t* blocks, uint32_t n_blocks, int n, 
     if (n < 1 || n > 7) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: block scaler size %d", n);
     if (n_blocks == 0) return IFHIP_OK;
     if (!blocks || !out) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null block pointer");
-    uint8_t *d_in = nullptr, *d_out = nullptr;
     const size_t in_bytes = static_cast<size_t>(n_blocks) * 64u, out_bytes = static_cast<size_t>(n_blocks) * n * n;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d_in), in_bytes));
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&d_out), out_bytes);
-    int rc = IFHIP_OK;
-    if (e == hipSuccess) e = hipMemcpy(d_in, blocks, in_bytes, hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        // the block array is a plane one block wide: pitch 8 in, pitch n out
-        rc = ifhip_scale_spatial_plane_device(d_in, 8, 1, n_blocks, n, srgb, d_out, static_cast<uint32_t>(n), nullptr);
-        if (rc == IFHIP_OK) {
-            e = hipStreamSynchronize(nullptr);
-            if (e == hipSuccess) e = hipMemcpy(out, d_out, out_bytes, hipMemcpyDeviceToHost);
-        }
-    }
-    (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(IFHIP_GPU_ERROR, "GpuError: block scaler staging failed: %s", hipGetErrorString(e));
+    DeviceBlock d_in, d_out;
+    HIP_TRY(d_in.alloc(in_bytes));
+    HIP_TRY(d_out.alloc(out_bytes));
+    HIP_TRY(hipMemcpy(d_in.p, blocks, in_bytes, hipMemcpyHostToDevice));
+    // the block array is a plane one block wide: pitch 8 in, pitch n out
+    if (int rc = ifhip_scale_spatial_plane_device(d_in.as<uint8_t>(), 8, 1, n_blocks, n, srgb, d_out.as<uint8_t>(), static_cast<uint32_t>(n), nullptr))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    HIP_TRY(hipMemcpy(out, d_out.p, out_bytes, hipMemcpyDeviceToHost));
     return IFHIP_OK;
 }
 

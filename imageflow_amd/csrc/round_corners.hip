@@ -21,14 +21,7 @@
 #include <cstring>
 #include <vector>
 
-#include "common.hpp"
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess)                                                                          \
-            return fail(IFHIP_GPU_ERROR, "GpuError: %s failed: %s", #expr, hipGetErrorString(e__));     \
-    } while (0)
+#include "hip_entry.hpp"
 
 namespace ifhip {
 namespace {
@@ -138,11 +131,6 @@ __global__ void __launch_bounds__(kThreads) round_corners_kernel(const Args a) {
         if (fill) { px = a.matte; have = true; dirty = true; }
     }
     if (dirty) *p = px;
-}
-
-int require_device() {
-    int dev = -1;
-    return require_gfx950(&dev);
 }
 
 // get_radius (:5-32) -> the four radii TL, TR, BL, BR, or circle
@@ -270,18 +258,15 @@ extern "C" {
 int ifhip_round_corners_batch_device(uint8_t* d_bgra, size_t image_bytes, uint32_t n_images, uint32_t w, uint32_t h,
                                      uint32_t stride, int mode, const float* radii, uint32_t matte_bgra, void* hip_stream) {
     if (n_images == 0) return IFHIP_OK;
-    if (!d_bgra || !radii) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null bitmap or radii pointer");
+    if (!radii) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null radii pointer");
     if (mode < IFHIP_ROUND_CORNERS_PERCENTAGE || mode > IFHIP_ROUND_CORNERS_PIXELS_CUSTOM)
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: unknown round corners mode %d", mode);
     if (w == 0 || h == 0) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Bitmap dimensions cannot be zero");
     if (w > static_cast<uint32_t>(INT32_MAX) || h > static_cast<uint32_t>(INT32_MAX))
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Bitmap dimension overflow");
-    if (static_cast<uint64_t>(w) * 4u > stride || (stride & 3u) || (image_bytes & 3u) || (reinterpret_cast<uintptr_t>(d_bgra) & 3u))
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: bitmap rows must be 4-byte aligned and stride >= 4*w");
-    if (static_cast<uint64_t>(h - 1u) * stride + 4ull * w > image_bytes)
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: image_bytes %zu is smaller than %u rows of stride %u", image_bytes, h, stride);
-    int rc = require_device();
+    int rc = check_frames(d_bgra, image_bytes, w, h, stride, "bitmap");
     if (rc) return rc;
+    if ((rc = require_gfx950(nullptr))) return rc;
     Args a{};
     a.bgra = d_bgra; a.image_bytes = image_bytes; a.w = w; a.h = h; a.stride = stride;
     plan(mode, radii, w, h, a.q);
@@ -311,21 +296,12 @@ int ifhip_round_corners_batch_device(uint8_t* d_bgra, size_t image_bytes, uint32
 }
 
 int ifhip_round_corners(uint8_t* bgra, uint32_t w, uint32_t h, uint32_t stride, int mode, const float* radii, uint32_t matte_bgra) {
-    if (!bgra || !radii) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null bitmap or radii pointer");
-    if (w == 0 || h == 0) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Bitmap dimensions cannot be zero");
-    if (static_cast<uint64_t>(w) * 4u > stride || (stride & 3u))
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: stride smaller than a BGRA row or not a multiple of 4");
-    int rc = require_device();
+    if (!radii) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null radii pointer");
+    HostFrame s;
+    int rc = s.up(bgra, w, h, stride);
     if (rc) return rc;
-    const size_t valid = static_cast<size_t>(h - 1u) * stride + static_cast<size_t>(w) * 4u;
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), static_cast<size_t>(h) * stride));
-    struct Guard { uint8_t* p; ~Guard() { (void)hipFree(p); } } guard{d};
-    HIP_TRY(hipMemcpy(d, bgra, valid, hipMemcpyHostToDevice));
-    if ((rc = ifhip_round_corners_batch_device(d, static_cast<size_t>(h) * stride, 1, w, h, stride, mode, radii, matte_bgra, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    HIP_TRY(hipMemcpy(bgra, d, valid, hipMemcpyDeviceToHost));
-    return IFHIP_OK;
+    if ((rc = ifhip_round_corners_batch_device(s.d, s.image_bytes, 1, w, h, stride, mode, radii, matte_bgra, nullptr))) return rc;
+    return s.down(bgra);
 }
 
 }  // extern "C"

@@ -19,14 +19,7 @@
 #include <climits>
 #include <cmath>
 
-#include "common.hpp"
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess)                                                                          \
-            return fail(IFHIP_GPU_ERROR, "GpuError: %s failed: %s", #expr, hipGetErrorString(e__));     \
-    } while (0)
+#include "hip_entry.hpp"
 
 namespace ifhip {
 namespace {
@@ -164,11 +157,6 @@ __global__ void __launch_bounds__(kThreads) apply_kernel(const Geometry g, doubl
     });
 }
 
-int require_device() {
-    int dev = -1;
-    return require_gfx950(&dev);
-}
-
 }  // namespace
 }  // namespace ifhip
 
@@ -179,18 +167,14 @@ extern "C" {
 int ifhip_white_balance_batch_device(uint8_t* d_bgra, size_t image_bytes, uint32_t n_images, uint32_t w, uint32_t h,
                                      uint32_t stride, float threshold, uint64_t* d_histograms, void* hip_stream) {
     if (n_images == 0) return IFHIP_OK;
-    if (!d_bgra) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null bitmap pointer");
     if (w == 0 || h == 0) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Bitmap dimensions cannot be zero");
     if (w > static_cast<uint32_t>(INT32_MAX) || h > static_cast<uint32_t>(INT32_MAX))
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Bitmap dimension overflow");
-    if (static_cast<uint64_t>(w) * 4u > stride || (stride & 3u) || (image_bytes & 3u) || (reinterpret_cast<uintptr_t>(d_bgra) & 3u) ||
-        (reinterpret_cast<uintptr_t>(d_histograms) & 7u))
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: bitmap rows must be 4-byte aligned and stride >= 4*w");
-    if (static_cast<uint64_t>(h - 1u) * stride + 4ull * w > image_bytes)
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: image_bytes %zu is smaller than %u rows of stride %u", image_bytes, h, stride);
-    if (n_images > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: more than 65535 images per launch");
-    int rc = require_device();
+    int rc = check_frames(d_bgra, image_bytes, w, h, stride, "bitmap");
     if (rc) return rc;
+    if (reinterpret_cast<uintptr_t>(d_histograms) & 7u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: histograms must be 8-byte aligned");
+    if (n_images > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: more than 65535 images per launch");
+    if ((rc = require_gfx950(nullptr))) return rc;
     const hipStream_t st = static_cast<hipStream_t>(hip_stream);
     // workgroups per frame: about kTargetBlocks in all, at least one row each, and few enough pixels per workgroup that a
     // u32 LDS count cannot overflow
@@ -223,24 +207,12 @@ int ifhip_white_balance_batch_device(uint8_t* d_bgra, size_t image_bytes, uint32
 }
 
 int ifhip_white_balance(uint8_t* bgra, uint32_t w, uint32_t h, uint32_t stride, float threshold, uint64_t* histograms) {
-    if (!bgra) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null bitmap pointer");
-    if (w == 0 || h == 0) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Bitmap dimensions cannot be zero");
-    if (static_cast<uint64_t>(w) * 4u > stride || (stride & 3u))
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: stride smaller than a BGRA row or not a multiple of 4");
-    int rc = require_device();
+    HostFrame s;
+    int rc = s.up(bgra, w, h, stride, 768u * sizeof(uint64_t));
     if (rc) return rc;
-    const size_t valid = static_cast<size_t>(h - 1u) * stride + static_cast<size_t>(w) * 4u;
-    const size_t bytes = (static_cast<size_t>(h) * stride + 15u) & ~static_cast<size_t>(15);
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), bytes + 768u * sizeof(uint64_t)));
-    struct Guard { uint8_t* p; ~Guard() { (void)hipFree(p); } } guard{d};
-    uint64_t* d_hist = reinterpret_cast<uint64_t*>(d + bytes);
-    HIP_TRY(hipMemcpy(d, bgra, valid, hipMemcpyHostToDevice));
-    if ((rc = ifhip_white_balance_batch_device(d, bytes, 1, w, h, stride, threshold, d_hist, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    HIP_TRY(hipMemcpy(bgra, d, valid, hipMemcpyDeviceToHost));
-    if (histograms) HIP_TRY(hipMemcpy(histograms, d_hist, 768u * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    return IFHIP_OK;
+    if ((rc = ifhip_white_balance_batch_device(s.d, s.image_bytes, 1, w, h, stride, threshold,
+                                               reinterpret_cast<uint64_t*>(s.side_output()), nullptr))) return rc;
+    return s.down(bgra, histograms);
 }
 
 }  // extern "C"

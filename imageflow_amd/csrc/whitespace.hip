@@ -21,14 +21,7 @@
 #include <climits>
 #include <cstring>
 
-#include "common.hpp"
-
-#define HIP_TRY(expr)                                                                                   \
-    do {                                                                                                \
-        hipError_t e__ = (expr);                                                                        \
-        if (e__ != hipSuccess)                                                                          \
-            return fail(IFHIP_GPU_ERROR, "GpuError: %s failed: %s", #expr, hipGetErrorString(e__));     \
-    } while (0)
+#include "hip_entry.hpp"
 
 namespace ifhip {
 namespace {
@@ -301,11 +294,6 @@ __global__ void __launch_bounds__(kThreads) replay_kernel(const Geometry g, cons
     }
 }
 
-int require_device() {
-    int dev = -1;
-    return require_gfx950(&dev);
-}
-
 }  // namespace
 }  // namespace ifhip
 
@@ -316,18 +304,15 @@ extern "C" {
 int ifhip_detect_content_batch_device(const uint8_t* d_bgra, size_t image_bytes, uint32_t n_images, uint32_t w, uint32_t h,
                                       uint32_t stride, int alpha_meaningful, uint32_t threshold, uint32_t* d_rects, void* hip_stream) {
     if (n_images == 0) return IFHIP_OK;
-    if (!d_bgra || !d_rects) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null bitmap or rectangle pointer");
+    if (!d_rects) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null rectangle pointer");
     if (w == 0 || h == 0) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Bitmap dimensions cannot be zero");
     if (w > static_cast<uint32_t>(INT32_MAX) || h > static_cast<uint32_t>(INT32_MAX))
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Bitmap dimension overflow");                  // :285-287
-    if (static_cast<uint64_t>(w) * 4u > stride || (stride & 3u) || (image_bytes & 3u) || (reinterpret_cast<uintptr_t>(d_bgra) & 3u) ||
-        (reinterpret_cast<uintptr_t>(d_rects) & 3u))
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: bitmap rows must be 4-byte aligned and stride >= 4*w");
-    if (static_cast<uint64_t>(h - 1u) * stride + 4ull * w > image_bytes)
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: image_bytes %zu is smaller than %u rows of stride %u", image_bytes, h, stride);
-    if (h > 65535u * kTileH || n_images > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: more than 65535 images per launch or too tall a bitmap");
-    int rc = require_device();
+    int rc = check_frames(d_bgra, image_bytes, w, h, stride, "bitmap");
     if (rc) return rc;
+    if (reinterpret_cast<uintptr_t>(d_rects) & 3u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: rectangles must be 4-byte aligned");
+    if (h > 65535u * kTileH || n_images > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: more than 65535 images per launch or too tall a bitmap");
+    if ((rc = require_gfx950(nullptr))) return rc;
     const hipStream_t st = static_cast<hipStream_t>(hip_stream);
     Geometry g{};
     g.w = w; g.h = h; g.stride = stride; g.image_bytes = image_bytes;
@@ -357,23 +342,13 @@ int ifhip_detect_content_batch_device(const uint8_t* d_bgra, size_t image_bytes,
 
 int ifhip_detect_content(const uint8_t* bgra, uint32_t w, uint32_t h, uint32_t stride, int alpha_meaningful, uint32_t threshold,
                          uint32_t* rect) {
-    if (!bgra || !rect) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null bitmap or rectangle pointer");
-    if (w == 0 || h == 0) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Bitmap dimensions cannot be zero");
-    if (static_cast<uint64_t>(w) * 4u > stride || (stride & 3u))
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: stride smaller than a BGRA row or not a multiple of 4");
-    int rc = require_device();
+    if (!rect) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null rectangle pointer");
+    HostFrame s;
+    int rc = s.up(bgra, w, h, stride, 16u);
     if (rc) return rc;
-    const size_t valid = static_cast<size_t>(h - 1u) * stride + static_cast<size_t>(w) * 4u;
-    const size_t bytes = (static_cast<size_t>(h) * stride + 15u) & ~static_cast<size_t>(15);
-    uint8_t* d = nullptr;
-    HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), bytes + 16u));
-    struct Guard { uint8_t* p; ~Guard() { (void)hipFree(p); } } guard{d};
-    uint32_t* d_rect = reinterpret_cast<uint32_t*>(d + bytes);
-    HIP_TRY(hipMemcpy(d, bgra, valid, hipMemcpyHostToDevice));
-    if ((rc = ifhip_detect_content_batch_device(d, bytes, 1, w, h, stride, alpha_meaningful, threshold, d_rect, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    HIP_TRY(hipMemcpy(rect, d_rect, 16u, hipMemcpyDeviceToHost));
-    return IFHIP_OK;
+    if ((rc = ifhip_detect_content_batch_device(s.d, s.image_bytes, 1, w, h, stride, alpha_meaningful, threshold,
+                                                reinterpret_cast<uint32_t*>(s.side_output()), nullptr))) return rc;
+    return s.down(nullptr, rect);
 }
 
 }  // extern "C"
