@@ -761,52 +761,12 @@ DecodeCoalescer& coalescer_for_device() {
     return *c;
 }
 
-// Resample plans (contribution tables of one shape on the device, immutable, thread-safe) are shared by all jobs of the
-// process: a service resizes to a handful of sizes, and a plan costs a dozen uploads.  Least recently used of 256 goes.
-struct PlanKey {
-    int device; uint32_t in_w, in_h, w, h; int filter; uint32_t sharpen_bits;
-    bool operator<(const PlanKey& o) const {
-        return std::tie(device, in_w, in_h, w, h, filter, sharpen_bits) < std::tie(o.device, o.in_w, o.in_h, o.w, o.h, o.filter, o.sharpen_bits);
-    }
-};
-std::mutex g_plan_mu;
-typedef std::map<PlanKey, std::pair<std::shared_ptr<ifhip_resample_plan>, uint64_t>> PlanMap;
-PlanMap& plan_map() { static PlanMap* m = new PlanMap; return *m; }        // never destroyed: no HIP calls from static destructors at exit
-uint64_t g_plan_clock = 0;
+// Resample plans are shared by all jobs of the process (ifhip::cached_plan).  A plan dropped from the cache while a job still
+// holds it is destroyed by that job's thread, behind the wait for the thread's stream -- which is the job's (StreamLease).
 std::shared_ptr<ifhip_resample_plan> shared_plan(uint32_t in_w, uint32_t in_h, uint32_t w, uint32_t h, int filter, float sharpen) {
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    uint32_t bits;
-    std::memcpy(&bits, &sharpen, 4);
-    const PlanKey key{dev, in_w, in_h, w, h, filter, bits};
-    {
-        std::lock_guard<std::mutex> lk(g_plan_mu);
-        auto it = plan_map().find(key);
-        if (it != plan_map().end()) { it->second.second = ++g_plan_clock; return it->second.first; }
-    }
-    ifhip_resample_plan* raw = nullptr;
-    check(ifhip_resample_plan_create(&raw, in_w, in_h, w, h, filter, sharpen));
-    // (a plan dropped from the cache while a job still holds it is destroyed by that job's thread, behind its stream's wait;
-    // one dropped with no holder was last used by a job that has ended: plain destroy)
-    // A plan's tables are only ever READ by kernels, and every job waits for its stream before it drops its reference
-    // (PendingJpeg / Job teardown), so the last reference -- whoever holds it -- goes with nothing in flight on the plan; the
-    // deleter still waits for the releasing thread's stream and, outside a job, the whole device (cached_free).
-    std::shared_ptr<ifhip_resample_plan> sp(raw, [](ifhip_resample_plan* q) { quiesce(); ifhip_resample_plan_destroy(q); });
-    std::shared_ptr<ifhip_resample_plan> evicted;                // released AFTER the lock: its deleter waits for a stream
-    std::shared_ptr<ifhip_resample_plan> result;
-    {
-        std::lock_guard<std::mutex> lk(g_plan_mu);
-        PlanMap& plans = plan_map();
-        if (plans.size() >= 256) {
-            auto victim = plans.begin();
-            for (auto it = plans.begin(); it != plans.end(); ++it) if (it->second.second < victim->second.second) victim = it;
-            evicted = std::move(victim->second.first);
-            plans.erase(victim);
-        }
-        auto ins = plans.emplace(key, std::make_pair(sp, ++g_plan_clock));
-        result = ins.first->second.first;
-    }
-    return result;
+    std::shared_ptr<ifhip_resample_plan> plan;
+    check(ifhip::cached_plan(in_w, in_h, w, h, filter, sharpen, &plan));
+    return plan;
 }
 
 struct Job {

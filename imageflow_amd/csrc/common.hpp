@@ -1,6 +1,7 @@
 // common.hpp -- shared declarations for libimageflow_hip.so (host side).
 #pragma once
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -124,5 +125,8 @@ int resample_from_ycc_planes_v(const ifhip_resample_plan* plan, const uint8_t* d
                                uint32_t matte, void* hip_stream, bool probe = false);   // probe: decide only, launch nothing
 void resample_plan_shape(const ifhip_resample_plan* plan, uint32_t* in_w, uint32_t* in_h, uint32_t* out_w, uint32_t* out_h);
 int max_live_rows(const AxisWeights& wv);
+// The process-wide cache of resample plans (api.cpp): the plan of (current device, shape, filter, sharpen), created on a
+// miss; the least recently used of 256 goes, and lives on for as long as a caller holds it.
+int cached_plan(uint32_t in_w, uint32_t in_h, uint32_t w, uint32_t h, int filter, float sharpen, std::shared_ptr<ifhip_resample_plan>* out);
 
 }  // namespace ifhip

@@ -54,6 +54,22 @@ class ResamplePlan:
             pass
 
 
+def describe_launch(in_w, in_h, w, h, filter=Filter.Robidoux, sharpen_percent_goal=0.0, alpha_meaningful=False, planar_ycc=False,
+                    n_images=1, in_stride=None, in_image_bytes=None, source_alignment=256,
+                    working_space=WorkingFloatspace.LinearRGB, force_kernel=-1):
+    """ifhip_describe_launch: the line `trace_launch` would print for this launch -- kernel and geometry -- decided on the host
+    alone (no GPU, no pixels).  Raises FlowError where the launch would fail."""
+    L = _native.lib()
+    L.ifhip_describe_launch.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_float, C.c_int, C.c_int,
+                                        C.c_uint32, C.c_uint32, C.c_size_t, C.c_uint32, C.c_int, C.c_int, C.c_char_p, C.c_size_t]
+    stride = in_stride if in_stride is not None else L.ifhip_stride_for_width(in_w)
+    buf = C.create_string_buffer(512)
+    _native.check(L.ifhip_describe_launch(in_w, in_h, w, h, int(filter), float(sharpen_percent_goal), int(alpha_meaningful),
+                                          int(planar_ycc), n_images, stride, in_image_bytes if in_image_bytes is not None else in_h * stride,
+                                          source_alignment, int(working_space), force_kernel, buf, len(buf)))
+    return buf.value.decode()
+
+
 _plans = {}
 
 

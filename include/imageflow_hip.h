@@ -174,6 +174,18 @@ IFHIP_API int ifhip_scale_and_render_batch_device(const ifhip_resample_plan* pla
                                                   int working_space, int compositing, uint32_t matte_bgra,
                                                   float* d_f32_dump, int force_kernel, void* hip_stream);
 
+/* Describes a launch and performs none (host only, for tests and tools: no device is asked for and no pixel is computed).
+ * What ifhip_scale_and_render_batch_device would launch for a plan of (in_w, in_h, w, h, filter, sharpen_percent_goal) and
+ * these frames -- planar_ycc_source: the component planes of the JPEG stage (in_stride = sample pitch, in_image_bytes =
+ * plane size); source_alignment: the largest power of two, in bytes, the source pointers are aligned to -- as one line of
+ * text in `line`: which kernel, and every number of its geometry.  It is the line the `trace_launch` debug switch prints
+ * for the real launch, and it honours ifhip_set_cu_budget and the debug switches alike.  A launch that would fail returns
+ * that status (message: ifhip_last_error_message). */
+IFHIP_API int ifhip_describe_launch(uint32_t in_w, uint32_t in_h, uint32_t w, uint32_t h, int filter,
+                                    float sharpen_percent_goal, int in_alpha_meaningful, int planar_ycc_source,
+                                    uint32_t n_images, uint32_t in_stride, size_t in_image_bytes, uint32_t source_alignment,
+                                    int working_space, int force_kernel, char* line, size_t line_capacity);
+
 /* ---- Inner B: flatten --------------------------------------------------------------------------------- */
 /* Replaces graphics::blend::apply_matte (graphics/blend.rs:6-59) / Bitmap::apply_matte (bitmaps.rs:528-541).
  * In place; no-op when !alpha_meaningful (blend.rs:11-13). */

@@ -320,6 +320,45 @@ def test_host_drop_in_from_several_threads():
     assert not errors, errors
 
 
+def test_host_drop_in_evicts_plans_other_threads_hold():
+    """The host-buffer entry point takes its plans from the process-wide cache of 256 (csrc/api.cpp, shared with the ABI
+    shim).  8 threads x 72 calls walk 288 distinct (shape, filter) keys, neighbouring threads over the same keys half of the
+    time, so plans are dropped from the cache while other threads still launch on them; every result equals the oracle's."""
+    import threading
+    from oracle import oracle as O
+    filters = [Filter.Robidoux, Filter.Lanczos, Filter.Box, Filter.Triangle]
+    keys = [(24 + 3 * a, 20 + 2 * b, f) for f in filters for b in range(6) for a in range(12)]
+    assert len(set(keys)) == 288
+    errors = []
+
+    def worker(k):
+        try:
+            rng = np.random.default_rng(700 + k)
+            for i in range(72):
+                iw, ih, filt = keys[(36 * k + i) % len(keys)]
+                ow, oh = iw // 2 + 1, ih // 2 + 1
+                alpha = (k + i) % 2 == 1
+                fr = U.random_frames(1, iw, ih, seed0=7000 + 100 * k + i, alpha=True)[0]
+                cst = U.stride_for(ow)
+                canvas0 = rng.integers(0, 256, size=(oh, cst), dtype=np.uint8)
+                exp = canvas0.copy()
+                rc, _ = O.scale_and_render(fr, iw, ih, exp, ow, oh, 0, 0, ow, oh, filter_id=int(filt), alpha_meaningful=alpha)
+                assert rc == 0
+                got = canvas0.copy()
+                scale_and_render_host(fr, iw, ih, fr.shape[1], alpha, got, ow, oh, cst, ScaleAndRenderParams(0, 0, ow, oh, 0.0, filt))
+                if not np.array_equal(got[:, :4 * ow], exp[:, :4 * ow]):
+                    errors.append((k, i, "pixels differ"))
+        except Exception as e:  # noqa: BLE001
+            errors.append((k, repr(e)))
+
+    threads = [threading.Thread(target=worker, args=(k,)) for k in range(8)]
+    for th in threads:
+        th.start()
+    for th in threads:
+        th.join()
+    assert not errors, errors
+
+
 # ---- banded two-pass kernel (force_kernel 2): the generic pair fused through LDS, for up-scales and small frames ------------
 BANDED_SHAPES = [
     (100, 100, 300, 300),    # the reference's test_trim_then_resize shape: 15 live output rows per source row

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Round 6, review item 4: can the moderate-ratio resample shapes run five waves per SIMD (20 per CU)?  Arithmetic on the
-launch geometry of csrc/api.cpp / device.hpp (no GPU): for every way to cut a source row into equal strips, the waves a
+launch geometry of csrc/resample_plan.cpp / device.hpp (no GPU): for every way to cut a source row into equal strips, the waves a
 strip's workgroup holds (a lane owns 4 source columns), the workgroup's minimal LDS (16 copies of the sRGB -> float table,
 the linear -> sRGB table, the two-row ring of the fast horizontal pass: (quads + G - 1) x 48 B per row and frame slot, the
 4-byte output records), how many such workgroups a CU's 160 KB holds, and the waves per CU that gives.  VGPRs: what
