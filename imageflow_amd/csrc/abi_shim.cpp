@@ -10,9 +10,10 @@
 //
 // Two labelled EXTENSIONS, because the reference's JSON API has no raw-pixel I/O:
 //   * decode accepts, besides baseline JPEG, the container "IFBGRA1\0" + u32le w, h, stride, alpha_meaningful + rows;
-//   * encode writes a real JPEG for the libjpeg_turbo preset -- baseline, optimised tables, progressive (device pixel stage + host Huffman coder, jpeg_write.cpp)
+//   * encode writes a real JPEG for the libjpeg_turbo preset -- baseline, optimised tables, progressive (device pixel stage + host Huffman coder, jpeg_write.cpp),
+//     a real PNG for the libpng preset (the device coder, png_encode.hip),
 //     and that container for every other preset (preferred_extension "ifbgra", mime "application/x-imageflow-bgra"):
-//     PNG deflate / GIF / WebP coders are out of scope, the caller's encoder takes the frame.
+//     the lodepng / pngquant / GIF / WebP coders are out of scope, the caller's encoder takes the frame.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1455,7 +1456,8 @@ struct Job {
     // (csrc/jpeg_write.cpp) -- baseline, with optimize_huffman_coding libjpeg's optimal tables, with progressive its
     // standard scan script (:121-129).  The content-adaptive sampling choice
     // (evalchroma, an external crate) is not reproduced: the file uses the maximum the reference allows (:133, 4:2:0).
-    // EXTENSION: every other preset writes the raw BGRA container (PNG / GIF / WebP coders are out of scope).
+    // EncoderPreset::Libpng is written as a real PNG by the device coder (csrc/png_encode.hip).
+    // EXTENSION: every other preset writes the raw BGRA container (lodepng / pngquant / GIF / WebP coders are out of scope).
     // `shared`: other consumers still read this frame -- the matte is then applied to a private copy.
     void encode(FramePtr f, int32_t io_id, const JVal* preset, bool shared) {
         Timed t(this, "primitive_encoder");
@@ -1542,6 +1544,52 @@ struct Job {
             o.owned.resize(len);
             o.written = true;
             encodes.push_back({io_id, f->w, f->h, "image/jpeg", "jpg"});
+            return;
+        }
+        if (const JVal* png = preset ? preset->get("libpng") : nullptr) {
+            // EncoderPreset::Libpng {depth, matte, zlib_compression} (imageflow_types/src/lib.rs:751-755, codecs/auto.rs:241-268)
+            // -> LibPngEncoder::write_frame (codecs/libpng_encoder.rs:43-72): the file is coded on the device
+            // (csrc/png_encode.hip), only its bytes leave it.
+            int color_type = -1;                                                         // by the frame's alpha, below
+            if (const JVal* d = png->get("depth"); d && !d->is_null()) {
+                if (d->t != JVal::Str || (d->s != "png_32" && d->s != "png_24")) raise(kInvalidJson, "InvalidJson: encode.preset.libpng.depth is \"png_32\" or \"png_24\"");
+                if (d->s == "png_24") color_type = IFHIP_PNG_RGB;
+            }
+            int level = -1;                                                              // absent: zlib's default (6)
+            if (const JVal* z = png->get("zlib_compression"); z && !z->is_null()) {
+                if (z->t != JVal::Num || z->n != std::floor(z->n) || z->n < -2147483648.0 || z->n > 2147483647.0)
+                    raise(kInvalidJson, "InvalidJson: encode.preset.libpng.zlib_compression is a 32-bit integer");
+                // i32 clamped to 0..255 (auto.rs:265); above 9 libpng is left at its default (codec_png_wrapper.c:380-387)
+                const int v = static_cast<int>(std::min(255.0, std::max(0.0, z->n)));
+                level = v > 9 ? -1 : v;
+            }
+            const JVal* m = png->get("matte");
+            if (m && !m->is_null() && f->alpha) {                                       // libpng_encoder.rs:55-57, bitmaps.rs:528-541
+                const uint32_t matte = parse_color(m, "encode.preset.libpng.matte");
+                if (shared) f = clone(f);
+                check(ifhip_apply_matte_batch_device(dev(f), f->bytes(), 1, f->w, f->h, f->stride, 1, matte, t_job_stream));
+                if ((matte >> 24) == 0xFFu) f->alpha = false;                            // matte.is_opaque(): set_alpha_meaningful(false)
+            } else if (m && !m->is_null()) {
+                (void)parse_color(m, "encode.preset.libpng.matte");                      // (still parsed: a malformed colour is an error)
+            }
+            if (color_type < 0) color_type = f->alpha ? IFHIP_PNG_RGBA : IFHIP_PNG_RGB;  // codec_png_wrapper.c:402-410
+            ifhip_png_enc_stage* ps = nullptr;
+            check(ifhip_png_enc_stage_create(&ps, f->w, f->h, color_type, 1));
+            std::unique_ptr<ifhip_png_enc_stage, void (*)(ifhip_png_enc_stage*)> ps_guard(ps, [](ifhip_png_enc_stage* q) { quiesce(); ifhip_png_enc_stage_destroy(q); });
+            const size_t pitch = (ifhip_png_enc_stage_max_file_bytes(ps) + 15u) & ~static_cast<size_t>(15u);
+            uint8_t* d_file = nullptr;
+            hip_check(job_malloc(reinterpret_cast<void**>(&d_file), pitch + 16u), "hipMalloc(png file)");
+            std::unique_ptr<uint8_t, void (*)(uint8_t*)> file_guard(d_file, [](uint8_t* p) { job_free(p); });
+            uint32_t* d_len = reinterpret_cast<uint32_t*>(d_file + pitch);               // length, status behind the file
+            check(ifhip_png_encode_batch_device(ps, dev(f), f->bytes(), f->stride, 1, level, d_file, pitch, d_len, d_len + 1, t_job_stream));
+            poll_cancel();
+            uint32_t len_status[2] = {0, 0};
+            hip_check(static_cast<hipError_t>(ifhip::copy_to_host(len_status, d_len, 8)), "download(file length)");
+            if (len_status[1] != 0 || len_status[0] == 0) raise(kInternalError, "InternalError: the PNG coder dropped a file sized for its worst case (status %u)", len_status[1]);
+            o.owned.assign(len_status[0], 0);
+            hip_check(static_cast<hipError_t>(ifhip::copy_to_host(o.owned.data(), d_file, len_status[0])), "download(file)");
+            o.written = true;
+            encodes.push_back({io_id, f->w, f->h, "image/png", "png"});
             return;
         }
         o.owned.assign(kRawHeader + f->bytes(), 0);

@@ -412,6 +412,41 @@ IFHIP_API int ifhip_jpeg_encode_batch_device(ifhip_jpeg_enc_stage* stage, const 
                                              const int16_t* d_coef2, int quality, uint32_t n_images, uint8_t* d_files,
                                              size_t file_pitch, uint32_t* d_lengths, uint32_t* d_status, void* hip_stream);
 
+/* Device PNG coder: EncoderPreset::Libpng {depth, matte, zlib_compression} (imageflow_types/src/lib.rs:751-755, chosen in
+ * codecs/auto.rs:241-268) without the host: what LibPngEncoder::write_frame (codecs/libpng_encoder.rs:43-72,134-160) has
+ * flow_codecs_png_encoder_write_frame / png_write_image do (c_components/lib/codec_png_wrapper.c:349-430) -- 8-bit RGB or
+ * RGBA, non-interlaced, png_set_sRGB_gAMA_and_cHRM's three chunks, libpng's default adaptive row filters, one zlib stream --
+ * on BGRA / BGRX frames that stay in HBM.  Every row carries the filter libpng's default choice takes; the deflate blocks
+ * are this coder's own (a parallel parse: 32 KiB blocks, each closed to a byte boundary), so a file is NOT libpng's byte
+ * for byte -- it decodes to the same pixels and is never larger than stored blocks.
+ * color_type: IFHIP_PNG_RGB drops the alpha byte (it is not flattened: apply a matte first), IFHIP_PNG_RGBA keeps it.
+ * A stage owns the scratch of a call in flight (filtered streams, tokens, symbol counts, code tables, scan arrays; it is
+ * allocated by the first batch), so it is bound to ONE stream at a time: a second call must be ordered behind the first --
+ * same stream, or an event between them; use one stage per stream for concurrent batches. */
+#define IFHIP_PNG_RGB 2
+#define IFHIP_PNG_RGBA 6
+#define IFHIP_PNG_FILE_OVERFLOW 1
+typedef struct ifhip_png_enc_stage ifhip_png_enc_stage;
+IFHIP_API int ifhip_png_enc_stage_create(ifhip_png_enc_stage** stage, uint32_t width, uint32_t height, int color_type,
+                                         uint32_t max_images);
+IFHIP_API void ifhip_png_enc_stage_destroy(ifhip_png_enc_stage* stage);
+/* a file_pitch with which no file overflows: every block stored (codec_png_wrapper.c's worst case too: zlib never grows a
+ * stream by more than its stored form) plus the framing.  With it IFHIP_PNG_FILE_OVERFLOW is never raised. */
+IFHIP_API size_t ifhip_png_enc_stage_max_file_bytes(const ifhip_png_enc_stage* stage);
+/* n_images frames of the stage's geometry at d_images + i * image_bytes (rows of `stride` bytes; the frame checks of every
+ * batch entry, made before the device is asked for).  Image i's file goes to d_files + i * file_pitch, its length to
+ * d_lengths[i] -- 0 when the file is longer than file_pitch, with IFHIP_PNG_FILE_OVERFLOW in d_status[i] (nullable).
+ * zlib_level is the preset's zlib_compression (codec_png_wrapper.c:380-387 png_set_compression_level): 0 writes stored
+ * blocks only; 1..9 and -1 all run the ONE device strategy -- levels do not change the search, only the FLEVEL bits of the
+ * zlib header.  Asynchronous on hip_stream.  The same pixels give the same bytes on every run and in every batch. */
+IFHIP_API int ifhip_png_encode_batch_device(ifhip_png_enc_stage* stage, const uint8_t* d_images, size_t image_bytes,
+                                            uint32_t stride, uint32_t n_images, int zlib_level, uint8_t* d_files,
+                                            size_t file_pitch, uint32_t* d_lengths, uint32_t* d_status, void* hip_stream);
+/* The synchronous host-buffer drop-in for flow_codecs_png_encoder_write_frame (codec_png_wrapper.c:349-430): one frame.
+ * out == NULL: only *len (the size needed) is written. */
+IFHIP_API int ifhip_png_encode(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int color_type,
+                               int zlib_level, uint8_t* out, size_t capacity, size_t* len);
+
 /* Host, for tests: what the device coder works from -- the Annex K Huffman tables in encode form (dc0, ac0, dc1, ac1; 256
  * entries `code | length << 16`) and the marker segments in front of the scan (SOI ... SOS). */
 IFHIP_API int ifhip_jpeg_debug_encode_tables(uint32_t* tabs4x256, int n_components, const uint8_t* h_samp, const uint8_t* v_samp,
