@@ -9,7 +9,7 @@
 // computes is computed by the ifhip_* entry points of this library on frames that stay in HBM.
 //
 // Two labelled EXTENSIONS, because the reference's JSON API has no raw-pixel I/O:
-//   * decode accepts, besides baseline JPEG, the container "IFBGRA1\0" + u32le w, h, stride, alpha_meaningful + rows;
+//   * decode accepts, besides JPEG and PNG (csrc/png_decode.hip), the container "IFBGRA1\0" + u32le w, h, stride, alpha_meaningful + rows;
 //   * encode writes a real JPEG for the libjpeg_turbo preset -- baseline, optimised tables, progressive (device pixel stage + host Huffman coder, jpeg_write.cpp),
 //     a real PNG for the libpng preset (the device coder, png_encode.hip),
 //     and that container for every other preset (preferred_extension "ifbgra", mime "application/x-imageflow-bgra"):
@@ -39,6 +39,7 @@
 #include "../../include/imageflow_abi_subset.h"
 #include "../../include/imageflow_hip.h"
 #include "common.hpp"           // the library's per-job memory cache and thread stream (devmem.cpp)
+#include "png_read.hpp"         // the PNG chunk walk and the device decode of a walked file (png_read.cpp, png_decode.hip)
 #include "layout.hpp"           // imageflow_riapi's constraint layout (constrain / watermark)
 
 namespace {
@@ -884,7 +885,12 @@ struct Job {
         return it->second;
     }
 
+    static bool is_png(const Io& in) {
+        static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 13, 10, 26, 10};
+        return in.in_len >= 8 && std::memcmp(in.in, sig, 8) == 0;
+    }
     // MzDec::get_exif_rotation_flag (mozjpeg_decoder.rs:290-292): the EXIF orientation tag of a JPEG input, -1 = none
+    // (a PNG has none: LibPngDecoder::get_exif_rotation_flag is None, libpng_decoder.rs:54-56)
     static int exif_flag(const Io& in) {
         int flag = -1;
         if (in.in_len >= 4 && in.in[0] == 0xFF && in.in[1] == 0xD8) (void)ifhip_jpeg_exif_orientation(in.in, in.in_len, &flag);
@@ -904,6 +910,12 @@ struct Job {
             uint32_t hdr[4];
             std::memcpy(hdr, in.in + 8, 16);
             *w = hdr[0]; *h = hdr[1];
+            return;
+        }
+        if (is_png(in)) {                                                // codecs/mod.rs:398-415 sniffing: the 8-byte signature
+            ifhip_png_file_info pi;
+            check(ifhip_png_info(in.in, in.in_len, &pi));
+            *w = pi.width; *h = pi.height;
             return;
         }
         int nc = 0;
@@ -945,6 +957,37 @@ struct Job {
         return b;
     }
 
+    // LibPngDecoder::read_frame (codecs/libpng_decoder.rs:82-104 -> c_components/lib/codec_png_wrapper.c:131-246) on the device:
+    // the host walks the chunks, the IDAT stream is inflated, un-filtered and expanded to BGRA by csrc/png_decode.hip.  The
+    // JPEG downscale hints do not apply (tell_decoder accepts and ignores them, libpng_decoder.rs:58-80).
+    FramePtr decode_png(int32_t io_id, Io& in) {
+        ifhip::PngParsed P;                                                           // ONE walk over the chunks: the facts and where the IDAT payloads lie
+        check(ifhip::parse_png(in.in, in.in_len, &P, true));                          // a bad CRC, a malformed critical chunk: ImageMalformed
+        check_size(sec.max_decode_size, "max_decode_size", P.w, P.h);                 // on the header, before anything is staged
+        // The colour policy of the JPEG path below (DESIGN 8 "Colour management: none"): the reference transforms a frame whose
+        // iCCP, or gAMA + cHRM, is not sRGB (libpng_decoder.rs:340-383); this build cannot, so it refuses -- never other colours.
+        if (!in.told_discard_profile && P.color_kind == 2)
+            raise(kActionNotSupported, "ActionNotSupported: io_id %d %s; this build has no colour "
+                  "management (the reference converts such frames to sRGB, codecs/libpng_decoder.rs:376).  Tell the decoder "
+                  "\"discard_color_profile\" to decode the samples as they are, or keep the file on the reference.", io_id,
+                  P.has_iccp ? "carries an embedded ICC profile that is not sRGB" : "carries gAMA and cHRM chunks that do not describe sRGB");
+        if (P.inflated > 0x7FFF0000ull) raise(kImageMalformed, "ImageMalformed: LibPNG error: the image data of io_id %d would inflate beyond 2^31 bytes", io_id);
+        FramePtr f = new_frame(P.w, P.h, P.alpha_used, 0, true);                      // (max_frame_size inside)
+        uint32_t* d_status = nullptr;
+        hip_check(job_malloc(reinterpret_cast<void**>(&d_status), 16), "hipMalloc(status)");
+        struct Guard { void* p; ~Guard() { job_free(p); } } guard{d_status};
+        const ifhip::PngParsed* parsed = &P;
+        const size_t bytes = f->bytes();
+        poll_cancel();
+        check(ifhip::png_decode_parsed_device(&parsed, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream));
+        uint32_t status = 0;
+        hip_check(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, t_job_stream), "download(status)");
+        hip_check(static_cast<hipError_t>(ifhip::wait_stream(t_job_stream)), "decode(png)");
+        if (status) raise(kImageMalformed, "ImageMalformed: LibPNG error: %s (io_id %d, status %u)", ifhip::png_status_text(status), io_id, status);
+        decodes.push_back({io_id, P.w, P.h, "image/png", "png"});
+        return f;
+    }
+
     // decode: MozJpegDecoder::read_frame (codecs/mozjpeg_decoder.rs:295-420) on the device, or the raw extension
     FramePtr decode(int32_t io_id, uint32_t hint_w, uint32_t hint_h, bool luma_spatial, bool luma_srgb) {
         Timed t(this, "primitive_decoder");
@@ -962,6 +1005,7 @@ struct Job {
             decodes.push_back({io_id, w, h, "application/x-imageflow-bgra", "ifbgra"});
             return f;
         }
+        if (is_png(in)) return decode_png(io_id, in);
         if (in.in_len < 3 || in.in[0] != 0xFF || in.in[1] != 0xD8)                        // codecs/mod.rs:398-415 sniffing
             raise(kImageTypeNotSupported, "ImageTypeNotSupported: io_id %d is neither a JPEG nor the raw BGRA extension", io_id);
         {   // limits before anything is staged (mozjpeg_decoder.rs:196-214 checks max_decode_size on the header)
@@ -2385,6 +2429,13 @@ const struct imageflow_json_response* imageflow_context_send_json(struct imagefl
         }
         if (!build && !execute) {                                    // get_image_info / get_scaled_image_info {io_id}: header facts only
             Io& in = job.input(static_cast<int32_t>(want_int(root, "io_id", "get_image_info")));
+            if (Job::is_png(in)) {                                   // LibPngDecoder: scaled = unscaled, no EXIF (libpng_decoder.rs:36-56)
+                ifhip_png_file_info pi;
+                check(ifhip_png_info(in.in, in.in_len, &pi));
+                return respond(c, 200, "{\n  \"code\": 200,\n  \"success\": true,\n  \"message\": \"OK\",\n  \"data\": {\n    \"image_info\": {\"preferred_mime_type\": \"image/png\", "
+                                       "\"preferred_extension\": \"png\", \"image_width\": " + std::to_string(pi.width) + ", \"image_height\": " + std::to_string(pi.height) +
+                                       ", \"frame_decodes_into\": \"" + (pi.alpha_used ? "bgra_32" : "bgr_32") + "\"}\n  }\n}");
+            }
             uint32_t w = 0, h = 0, bw[3], bh[3], ri = 0;
             int nc = 0;
             uint8_t hs[3], vs[3];

@@ -41,6 +41,9 @@ int require_gfx950(int* device_out);                  // IFHIP_OK and the curren
 #define DEV_MALLOC(pp, n) static_cast<hipError_t>(::ifhip::cached_malloc(reinterpret_cast<void**>(pp), (n)))
 #define DEV_FREE(p) static_cast<hipError_t>(::ifhip::cached_free(p))
 
+// An ICC profile that describes sRGB itself (csrc/jpeg_entropy.hip; the JPEG APP2 and the PNG iCCP readers share it)
+bool icc_describes_srgb(const uint8_t* profile, size_t profile_bytes);
+
 // Development switches (tests and tools/ only).  The library never reads the environment: a switch exists only after
 // ifhip_debug_set(key, value) (include/imageflow_hip.h); unset -> nullptr.  One relaxed atomic load when none is set.
 const char* debug_switch(const char* key);

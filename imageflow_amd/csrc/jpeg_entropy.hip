@@ -1097,6 +1097,68 @@ static int dev_alloc(ifhip_jpeg_entropy* e, T** out, size_t count, const T* init
     return IFHIP_OK;
 }
 
+namespace ifhip {
+// Does an ICC profile describe sRGB itself (see ifhip_jpeg_icc_profile_kind in include/imageflow_hip.h: an RGB matrix profile
+// with the sRGB primaries within 0.003 after D50 adaptation and the sRGB tone curve)?  Shared by the JPEG (APP2) and the PNG
+// (iCCP) readers.
+bool icc_describes_srgb(const uint8_t* profile, size_t profile_bytes) {
+    struct View {
+        const uint8_t* p; size_t n;
+        const uint8_t& operator[](size_t i) const { return p[i]; }
+        size_t size() const { return n; }
+    } icc{profile, profile_bytes};
+    // ICC.1 header: size (0..3), colour space (16..19), PCS (20..23); tag table at 128: count, then {sig, offset, size}
+    auto be32 = [&](size_t o) { return (static_cast<uint32_t>(icc[o]) << 24) | (static_cast<uint32_t>(icc[o + 1]) << 16) | (static_cast<uint32_t>(icc[o + 2]) << 8) | icc[o + 3]; };
+    if (icc.size() < 132 || std::memcmp(&icc[16], "RGB ", 4) != 0 || std::memcmp(&icc[20], "XYZ ", 4) != 0) return false;
+    const uint32_t tags = be32(128);
+    if (tags > 200 || 132 + static_cast<size_t>(tags) * 12 > icc.size()) return false;
+    auto find = [&](const char* sig, size_t* off, size_t* size) {
+        for (uint32_t t = 0; t < tags; ++t) {
+            const size_t e = 132 + static_cast<size_t>(t) * 12;
+            if (std::memcmp(&icc[e], sig, 4) != 0) continue;
+            *off = be32(e + 4); *size = be32(e + 8);
+            return *off + *size <= icc.size() && *size >= 8;
+        }
+        return false;
+    };
+    // primaries, D50-adapted (IEC 61966-2-1 through Bradford, as every sRGB profile carries them)
+    static const double want[3][3] = {{0.4360, 0.2225, 0.0139}, {0.3851, 0.7169, 0.0971}, {0.1431, 0.0606, 0.7141}};
+    const char* xyz_sig[3] = {"rXYZ", "gXYZ", "bXYZ"};
+    for (int c = 0; c < 3; ++c) {
+        size_t off = 0, size = 0;
+        if (!find(xyz_sig[c], &off, &size) || size < 20 || std::memcmp(&icc[off], "XYZ ", 4) != 0) return false;
+        for (int k = 0; k < 3; ++k) {
+            const double v = static_cast<int32_t>(be32(off + 8 + 4 * static_cast<size_t>(k))) / 65536.0;
+            if (std::fabs(v - want[c][k]) > 0.003) return false;
+        }
+    }
+    // tone curves: the sRGB parametric form (type 3: g 2.4, a 1/1.055, b 0.055/1.055, c 1/12.92, d 0.04045) or a sampled curve
+    // whose entries follow the sRGB function (checked at every entry; 2 of 65535 is the 16-bit tables' own rounding)
+    const char* trc_sig[3] = {"rTRC", "gTRC", "bTRC"};
+    for (int c = 0; c < 3; ++c) {
+        size_t off = 0, size = 0;
+        if (!find(trc_sig[c], &off, &size) || size < 12) return false;
+        if (std::memcmp(&icc[off], "para", 4) == 0) {
+            if (size < 12 + 20 || ((static_cast<uint32_t>(icc[off + 8]) << 8) | icc[off + 9]) != 3u) return false;
+            static const double p[5] = {2.4, 1.0 / 1.055, 0.055 / 1.055, 1.0 / 12.92, 0.04045};
+            for (int k = 0; k < 5; ++k)
+                if (std::fabs(static_cast<int32_t>(be32(off + 12 + 4 * static_cast<size_t>(k))) / 65536.0 - p[k]) > 0.002) return false;
+        } else if (std::memcmp(&icc[off], "curv", 4) == 0) {
+            const uint32_t n = be32(off + 8);
+            if (n < 256 || 12 + static_cast<size_t>(n) * 2 > size) return false;      // (a single gamma value is not the sRGB curve)
+            for (uint32_t k = 0; k < n; ++k) {
+                const double x = static_cast<double>(k) / (n - 1), y = x <= 0.04045 ? x / 12.92 : std::pow((x + 0.055) / 1.055, 2.4);
+                const double got = ((static_cast<uint32_t>(icc[off + 12 + 2 * static_cast<size_t>(k)]) << 8) | icc[off + 13 + 2 * static_cast<size_t>(k)]) / 65535.0;
+                if (std::fabs(got - y) > 2.0 / 65535.0 + 1e-4) return false;
+            }
+        } else {
+            return false;
+        }
+    }
+    return true;
+}
+}  // namespace ifhip
+
 extern "C" {
 
 int ifhip_jpeg_parse_headers(const uint8_t* jpeg, size_t len, uint32_t* width, uint32_t* height, int* n_components,
@@ -1223,56 +1285,7 @@ int ifhip_jpeg_icc_profile_kind(const uint8_t* d, size_t len, int* kind) {
     for (uint32_t k = 1; k <= count; ++k) icc.insert(icc.end(), chunk[k].first, chunk[k].first + chunk[k].second);
     if (icc.empty()) return IFHIP_OK;                                    // only empty markers: None
     if (icc.size() >= 20 && std::memcmp(&icc[16], "GRAY", 4) == 0 && frame_components != 1) return IFHIP_OK;   // -> SourceProfile::Srgb
-    *kind = 2;
-    // ICC.1 header: size (0..3), colour space (16..19), PCS (20..23); tag table at 128: count, then {sig, offset, size}
-    auto be32 = [&](size_t o) { return (static_cast<uint32_t>(icc[o]) << 24) | (static_cast<uint32_t>(icc[o + 1]) << 16) | (static_cast<uint32_t>(icc[o + 2]) << 8) | icc[o + 3]; };
-    if (icc.size() < 132 || std::memcmp(&icc[16], "RGB ", 4) != 0 || std::memcmp(&icc[20], "XYZ ", 4) != 0) return IFHIP_OK;
-    const uint32_t tags = be32(128);
-    if (tags > 200 || 132 + static_cast<size_t>(tags) * 12 > icc.size()) return IFHIP_OK;
-    auto find = [&](const char* sig, size_t* off, size_t* size) {
-        for (uint32_t t = 0; t < tags; ++t) {
-            const size_t e = 132 + static_cast<size_t>(t) * 12;
-            if (std::memcmp(&icc[e], sig, 4) != 0) continue;
-            *off = be32(e + 4); *size = be32(e + 8);
-            return *off + *size <= icc.size() && *size >= 8;
-        }
-        return false;
-    };
-    // primaries, D50-adapted (IEC 61966-2-1 through Bradford, as every sRGB profile carries them)
-    static const double want[3][3] = {{0.4360, 0.2225, 0.0139}, {0.3851, 0.7169, 0.0971}, {0.1431, 0.0606, 0.7141}};
-    const char* xyz_sig[3] = {"rXYZ", "gXYZ", "bXYZ"};
-    for (int c = 0; c < 3; ++c) {
-        size_t off = 0, size = 0;
-        if (!find(xyz_sig[c], &off, &size) || size < 20 || std::memcmp(&icc[off], "XYZ ", 4) != 0) return IFHIP_OK;
-        for (int k = 0; k < 3; ++k) {
-            const double v = static_cast<int32_t>(be32(off + 8 + 4 * static_cast<size_t>(k))) / 65536.0;
-            if (std::fabs(v - want[c][k]) > 0.003) return IFHIP_OK;
-        }
-    }
-    // tone curves: the sRGB parametric form (type 3: g 2.4, a 1/1.055, b 0.055/1.055, c 1/12.92, d 0.04045) or a sampled curve
-    // whose entries follow the sRGB function (checked at every entry; 2 of 65535 is the 16-bit tables' own rounding)
-    const char* trc_sig[3] = {"rTRC", "gTRC", "bTRC"};
-    for (int c = 0; c < 3; ++c) {
-        size_t off = 0, size = 0;
-        if (!find(trc_sig[c], &off, &size) || size < 12) return IFHIP_OK;
-        if (std::memcmp(&icc[off], "para", 4) == 0) {
-            if (size < 12 + 20 || ((static_cast<uint32_t>(icc[off + 8]) << 8) | icc[off + 9]) != 3u) return IFHIP_OK;
-            static const double p[5] = {2.4, 1.0 / 1.055, 0.055 / 1.055, 1.0 / 12.92, 0.04045};
-            for (int k = 0; k < 5; ++k)
-                if (std::fabs(static_cast<int32_t>(be32(off + 12 + 4 * static_cast<size_t>(k))) / 65536.0 - p[k]) > 0.002) return IFHIP_OK;
-        } else if (std::memcmp(&icc[off], "curv", 4) == 0) {
-            const uint32_t n = be32(off + 8);
-            if (n < 256 || 12 + static_cast<size_t>(n) * 2 > size) return IFHIP_OK;      // (a single gamma value is not the sRGB curve)
-            for (uint32_t k = 0; k < n; ++k) {
-                const double x = static_cast<double>(k) / (n - 1), y = x <= 0.04045 ? x / 12.92 : std::pow((x + 0.055) / 1.055, 2.4);
-                const double got = ((static_cast<uint32_t>(icc[off + 12 + 2 * static_cast<size_t>(k)]) << 8) | icc[off + 13 + 2 * static_cast<size_t>(k)]) / 65535.0;
-                if (std::fabs(got - y) > 2.0 / 65535.0 + 1e-4) return IFHIP_OK;
-            }
-        } else {
-            return IFHIP_OK;
-        }
-    }
-    *kind = 1;
+    *kind = icc_describes_srgb(icc.data(), icc.size()) ? 1 : 2;
     return IFHIP_OK;
 }
 

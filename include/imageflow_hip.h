@@ -447,6 +447,58 @@ IFHIP_API int ifhip_png_encode_batch_device(ifhip_png_enc_stage* stage, const ui
 IFHIP_API int ifhip_png_encode(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int color_type,
                                int zlib_level, uint8_t* out, size_t capacity, size_t* len);
 
+/* Device PNG decoder: what LibPngDecoder (imageflow_core/src/codecs/libpng_decoder.rs:36-104,297-299,340-383) gets from
+ * libpng (c_components/lib/codec_png_wrapper.c:131-212 wrap_png_decode_image_info, :215-246 wrap_png_decode_finish, :266-292
+ * wrap_png_decoder_get_info) -- all 15 legal (colour type, bit depth) pairs, interlaced or not, normalised to 8-bit BGRA in
+ * libpng's order: expand (palette -> RGB, gray 1/2/4 -> 8 bits, tRNS -> alpha with the key compared at the file's depth),
+ * filler 0xFF, strip 16 -> 8 by the high byte, gray -> RGB, BGR, Adam7 resolved.  The host parses the chunks and gathers the
+ * IDAT payloads (csrc/png_read.cpp); inflate, un-filter and expansion run on the device (csrc/png_decode.hip).
+ *
+ * alpha_used (-> alpha_meaningful, frame_decodes_into bgra_32 / bgr_32) is true for colour types with alpha and for palette
+ * files with or without tRNS (codec_png_wrapper.c:176-186): gray / RGB with a tRNS key decode with real alpha bytes in a
+ * frame marked bgr_32.  uses_palette: colour type bit 0 (:270).  color_kind, in the convention of
+ * ifhip_jpeg_icc_profile_kind: 0 no colour chunks, or gAMA alone (honor_gama_only = false, libpng_decoder.rs:234); 1 sRGB
+ * declared (an sRGB chunk, an iCCP profile that describes sRGB, gAMA + cHRM with the specification's sRGB values); 2 any
+ * other colour space (another iCCP profile, other gAMA + cHRM) -- the reference converts such frames (:340-383), this
+ * library has no colour management, so callers must refuse or be told discard_color_profile.
+ *
+ * Status word of a file (d_status[i]): 0, or why its stream is no image -- libpng's errors. */
+#define IFHIP_PNG_DEC_TRUNCATED 1        /* the zlib stream ends early                                        */
+#define IFHIP_PNG_DEC_BLOCK_TYPE 2       /* deflate block type 3                                              */
+#define IFHIP_PNG_DEC_STORED_LENGTH 3    /* LEN / NLEN of a stored block do not match                          */
+#define IFHIP_PNG_DEC_CODE_LENGTHS 4     /* over-subscribed or incomplete code, bad repeat, no end-of-block    */
+#define IFHIP_PNG_DEC_BAD_CODE 5         /* bits that are no code, or a reserved symbol                       */
+#define IFHIP_PNG_DEC_DISTANCE 6         /* a distance that reaches before the stream's start                 */
+#define IFHIP_PNG_DEC_ZLIB_HEADER 7
+#define IFHIP_PNG_DEC_ADLER 8            /* Adler-32 mismatch: refused                                        */
+#define IFHIP_PNG_DEC_TOO_LITTLE 9       /* "Not enough image data"                                           */
+#define IFHIP_PNG_DEC_FILTER 10          /* "bad adaptive filter value"                                       */
+#define IFHIP_PNG_DEC_CONTAINER 11       /* batch only: the file's chunks did not parse (signature, CRC, IHDR, PLTE ...),
+                                          * or its image would inflate beyond 2^31 bytes                              */
+typedef struct ifhip_png_file_info {
+    uint32_t width, height, bit_depth, color_type, interlace;
+    uint32_t alpha_used, uses_palette;
+    int32_t color_kind;
+} ifhip_png_file_info;
+/* Header facts (png_read_info; libpng_decoder.rs:40-52 get_unscaled_image_info = get_scaled_image_info :36-38).  Walks all
+ * chunks: a bad CRC on IHDR / PLTE / tRNS / IDAT / IEND / the colour chunks, a malformed critical chunk or a missing IEND is
+ * IFHIP_INVALID_ARGUMENT with an "ImageMalformed: LibPNG error: ..." message.  Host only, no device needed. */
+IFHIP_API int ifhip_png_info(const uint8_t* png, size_t len, ifhip_png_file_info* info);
+/* n files (host memory), each with its own geometry, type and depth, into n device frames: d_frames[i] holds height_i rows of
+ * strides[i] bytes inside frame_bytes[i]; only the 4 * width_i bytes of a row are written.  d_status[i] (device) receives the
+ * file's status word; a damaged file leaves its frame untouched and never disturbs its neighbours.  Three launches per
+ * batch, every file in each: inflate (one wave per stream), un-filter (a skewed wavefront over 64 rows), expansion.  The
+ * streams are uploaded before the call returns; the kernels are asynchronous on hip_stream.  Colour chunks are NOT acted
+ * on here (see color_kind).  Argument and frame checks come before the device check. */
+IFHIP_API int ifhip_png_decode_batch_device(const uint8_t* const* files, const size_t* lens, uint32_t n_files,
+                                            uint8_t* const* d_frames, const size_t* frame_bytes, const uint32_t* strides,
+                                            uint32_t* d_status, void* hip_stream);
+/* The synchronous host-buffer drop-in for wrap_png_decode_image_info + wrap_png_decode_finish (codec_png_wrapper.c:131-246):
+ * one file into `height` BGRA rows of `stride` bytes at bgra (capacity bytes; bytes between rows are kept).  A non-zero
+ * status word comes back in *status (nullable) with IFHIP_INVALID_ARGUMENT and an "ImageMalformed: LibPNG error" message. */
+IFHIP_API int ifhip_png_decode(const uint8_t* png, size_t len, uint8_t* bgra, uint32_t stride, size_t capacity,
+                               uint32_t* status);
+
 /* Host, for tests: what the device coder works from -- the Annex K Huffman tables in encode form (dc0, ac0, dc1, ac1; 256
  * entries `code | length << 16`) and the marker segments in front of the scan (SOI ... SOS). */
 IFHIP_API int ifhip_jpeg_debug_encode_tables(uint32_t* tabs4x256, int n_components, const uint8_t* h_samp, const uint8_t* v_samp,
