@@ -12,8 +12,9 @@
 //   * decode accepts, besides JPEG and PNG (csrc/png_decode.hip), the container "IFBGRA1\0" + u32le w, h, stride, alpha_meaningful + rows;
 //   * encode writes a real JPEG for the libjpeg_turbo preset -- baseline, optimised tables, progressive (device pixel stage + host Huffman coder, jpeg_write.cpp),
 //     a real PNG for the libpng preset (the device coder, png_encode.hip),
+//     a palette PNG for the pngquant preset (the device quantiser, png_quantize.hip),
 //     and that container for every other preset (preferred_extension "ifbgra", mime "application/x-imageflow-bgra"):
-//     the lodepng / pngquant / GIF / WebP coders are out of scope, the caller's encoder takes the frame.
+//     the lodepng / GIF / WebP coders are out of scope, the caller's encoder takes the frame.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -1495,13 +1496,35 @@ struct Job {
         return out;
     }
 
+    // a truecolour PNG of the frame by the device coder (csrc/png_encode.hip): only the file's bytes leave the device
+    void write_png(const FramePtr& f, int color_type, int level, Io& o, int32_t io_id) {
+        ifhip_png_enc_stage* ps = nullptr;
+        check(ifhip_png_enc_stage_create(&ps, f->w, f->h, color_type, 1));
+        std::unique_ptr<ifhip_png_enc_stage, void (*)(ifhip_png_enc_stage*)> ps_guard(ps, [](ifhip_png_enc_stage* q) { quiesce(); ifhip_png_enc_stage_destroy(q); });
+        const size_t pitch = (ifhip_png_enc_stage_max_file_bytes(ps) + 15u) & ~static_cast<size_t>(15u);
+        uint8_t* d_file = nullptr;
+        hip_check(job_malloc(reinterpret_cast<void**>(&d_file), pitch + 16u), "hipMalloc(png file)");
+        std::unique_ptr<uint8_t, void (*)(uint8_t*)> file_guard(d_file, [](uint8_t* p) { job_free(p); });
+        uint32_t* d_len = reinterpret_cast<uint32_t*>(d_file + pitch);               // length, status behind the file
+        check(ifhip_png_encode_batch_device(ps, dev(f), f->bytes(), f->stride, 1, level, d_file, pitch, d_len, d_len + 1, t_job_stream));
+        poll_cancel();
+        uint32_t len_status[2] = {0, 0};
+        hip_check(static_cast<hipError_t>(ifhip::copy_to_host(len_status, d_len, 8)), "download(file length)");
+        if (len_status[1] != 0 || len_status[0] == 0) raise(kInternalError, "InternalError: the PNG coder dropped a file sized for its worst case (status %u)", len_status[1]);
+        o.owned.assign(len_status[0], 0);
+        hip_check(static_cast<hipError_t>(ifhip::copy_to_host(o.owned.data(), d_file, len_status[0])), "download(file)");
+        o.written = true;
+        encodes.push_back({io_id, f->w, f->h, "image/png", "png"});
+    }
+
     // encode: EncoderPreset::LibjpegTurbo is written as a real JPEG (codecs/mozjpeg.rs:78-160, create_classic :62-77):
     // apply_matte + forward DCT / quantisation on the device, the Huffman coder and the markers on the host
     // (csrc/jpeg_write.cpp) -- baseline, with optimize_huffman_coding libjpeg's optimal tables, with progressive its
     // standard scan script (:121-129).  The content-adaptive sampling choice
     // (evalchroma, an external crate) is not reproduced: the file uses the maximum the reference allows (:133, 4:2:0).
-    // EncoderPreset::Libpng is written as a real PNG by the device coder (csrc/png_encode.hip).
-    // EXTENSION: every other preset writes the raw BGRA container (lodepng / pngquant / GIF / WebP coders are out of scope).
+    // EncoderPreset::Libpng is written as a real PNG by the device coder (csrc/png_encode.hip), EncoderPreset::Pngquant as
+    // a palette PNG by the device quantiser (csrc/png_quantize.hip), or losslessly where it misses minimum_quality.
+    // EXTENSION: every other preset writes the raw BGRA container (lodepng / GIF / WebP coders are out of scope).
     // `shared`: other consumers still read this frame -- the matte is then applied to a private copy.
     void encode(FramePtr f, int32_t io_id, const JVal* preset, bool shared) {
         Timed t(this, "primitive_encoder");
@@ -1617,19 +1640,45 @@ struct Job {
                 (void)parse_color(m, "encode.preset.libpng.matte");                      // (still parsed: a malformed colour is an error)
             }
             if (color_type < 0) color_type = f->alpha ? IFHIP_PNG_RGBA : IFHIP_PNG_RGB;  // codec_png_wrapper.c:402-410
-            ifhip_png_enc_stage* ps = nullptr;
-            check(ifhip_png_enc_stage_create(&ps, f->w, f->h, color_type, 1));
-            std::unique_ptr<ifhip_png_enc_stage, void (*)(ifhip_png_enc_stage*)> ps_guard(ps, [](ifhip_png_enc_stage* q) { quiesce(); ifhip_png_enc_stage_destroy(q); });
-            const size_t pitch = (ifhip_png_enc_stage_max_file_bytes(ps) + 15u) & ~static_cast<size_t>(15u);
+            write_png(f, color_type, level, o, io_id);
+            return;
+        }
+        if (const JVal* pq = preset ? preset->get("pngquant") : nullptr) {
+            // EncoderPreset::Pngquant {quality, minimum_quality, speed, maximum_deflate} (imageflow_types/src/lib.rs:756-761)
+            // -> PngquantEncoder (codecs/pngquant.rs:35-139): quantised, dithered and written as a palette PNG on the device
+            // (csrc/png_quantize.hip); no matte (codecs/auto.rs:98-110).  The three numbers are u8.
+            auto u8_option = [&](const char* key) -> int {
+                const JVal* v = pq->get(key);
+                if (!v || v->is_null()) return -1;
+                if (v->t != JVal::Num || v->n != std::floor(v->n) || v->n < 0.0 || v->n > 255.0) raise(kInvalidJson, "InvalidJson: encode.preset.pngquant.%s is an integer in 0..255", key);
+                return static_cast<int>(v->n);
+            };
+            const int quality = u8_option("quality"), min_quality = u8_option("minimum_quality"), speed = u8_option("speed");
+            bool maximum_deflate = false;
+            if (const JVal* z = pq->get("maximum_deflate"); z && !z->is_null()) {
+                if (z->t != JVal::Bool) raise(kInvalidJson, "InvalidJson: encode.preset.pngquant.maximum_deflate is a boolean");
+                maximum_deflate = z->b;
+            }
+            const int level = maximum_deflate ? 9 : 6;                                    // lode.rs:162-195
+            ifhip_png_quant_stage* qs = nullptr;
+            check(ifhip_png_quant_stage_create(&qs, f->w, f->h, 1));
+            std::unique_ptr<ifhip_png_quant_stage, void (*)(ifhip_png_quant_stage*)> qs_guard(qs, [](ifhip_png_quant_stage* q) { quiesce(); ifhip_png_quant_stage_destroy(q); });
+            const size_t pitch = (ifhip_png_quant_stage_max_file_bytes(qs) + 15u) & ~static_cast<size_t>(15u);
             uint8_t* d_file = nullptr;
             hip_check(job_malloc(reinterpret_cast<void**>(&d_file), pitch + 16u), "hipMalloc(png file)");
             std::unique_ptr<uint8_t, void (*)(uint8_t*)> file_guard(d_file, [](uint8_t* p) { job_free(p); });
             uint32_t* d_len = reinterpret_cast<uint32_t*>(d_file + pitch);               // length, status behind the file
-            check(ifhip_png_encode_batch_device(ps, dev(f), f->bytes(), f->stride, 1, level, d_file, pitch, d_len, d_len + 1, t_job_stream));
+            check(ifhip_png_quantize_batch_device(qs, dev(f), f->bytes(), f->stride, f->alpha ? 1 : 0, 1, quality, min_quality, speed, 256, 1, level,
+                                                  d_file, pitch, d_len, d_len + 1, nullptr, nullptr, nullptr, t_job_stream));
             poll_cancel();
             uint32_t len_status[2] = {0, 0};
             hip_check(static_cast<hipError_t>(ifhip::copy_to_host(len_status, d_len, 8)), "download(file length)");
-            if (len_status[1] != 0 || len_status[0] == 0) raise(kInternalError, "InternalError: the PNG coder dropped a file sized for its worst case (status %u)", len_status[1]);
+            if (len_status[1] == IFHIP_PNG_QUALITY_TOO_LOW) {
+                // pngquant.rs:105-139: below minimum_quality the frame is written losslessly, RGBA or RGB by its alpha
+                write_png(f, f->alpha ? IFHIP_PNG_RGBA : IFHIP_PNG_RGB, level, o, io_id);
+                return;
+            }
+            if (len_status[1] != 0 || len_status[0] == 0) raise(kInternalError, "InternalError: the palette PNG coder dropped a file sized for its worst case (status %u)", len_status[1]);
             o.owned.assign(len_status[0], 0);
             hip_check(static_cast<hipError_t>(ifhip::copy_to_host(o.owned.data(), d_file, len_status[0])), "download(file)");
             o.written = true;

@@ -20,34 +20,10 @@
 #include <memory>
 
 #include "hip_entry.hpp"
+#include "png_encode_args.hpp"
 #include "png_encode_core.hpp"
 
 namespace ifhip {
-
-struct PngArgs {
-    const uint8_t* images;
-    size_t image_bytes;
-    uint32_t stride, w, h, bpp, pitch, color_type;
-    uint32_t stream_bytes, n_chunks;    // per image
-    size_t stream_pitch;                // bytes between the filtered streams of two images (a multiple of 16, 16 to spare)
-    uint8_t* streams;
-    uint32_t* tokens;                   // [n_images][n_chunks][kPngChunk]
-    uint32_t* counts;                   // [n_images][n_chunks][320]
-    uint32_t* tabs;                     // [n_images][n_chunks][320]
-    uint32_t* prefix;                   // [n_images][n_chunks][kPngPrefixWords]
-    uint32_t* chunk;                    // [kChunkWords][n_images][n_chunks]: the per-chunk words below
-    uint32_t* image;                    // [3][n_images]: total chunk bytes, Adler-32, overflow
-    uint32_t n_images, stored_only, zlib_header;
-    uint8_t* files;
-    size_t file_pitch;
-    uint32_t* lengths;
-    uint32_t* status_out;
-};
-enum { kNtok = 0, kAdler, kType, kPrefixBits, kBytes, kOffset, kCrc, kChunkWords };
-__device__ __forceinline__ uint32_t* chunk_word(const PngArgs& a, uint32_t which, uint32_t img, uint32_t c) {
-    return a.chunk + (static_cast<size_t>(which) * a.n_images + img) * a.n_chunks + c;
-}
-__device__ __forceinline__ size_t chunk_index(const PngArgs& a, uint32_t img, uint32_t c) { return static_cast<size_t>(img) * a.n_chunks + c; }
 
 __device__ __forceinline__ uint32_t png_wave_inclusive_scan(uint32_t v, uint32_t lane) {
 #pragma unroll
@@ -395,6 +371,14 @@ __global__ __launch_bounds__(1024) void png_finish_kernel(const PngArgs a) {
     }
 }
 
+void png_launch_deflate(const PngArgs& a, hipStream_t st) {
+    const dim3 chunk_grid(a.n_chunks, a.n_images);
+    hipLaunchKernelGGL(png_match_kernel, chunk_grid, dim3(kPngRound), 0, st, a);
+    hipLaunchKernelGGL(png_codes_kernel, chunk_grid, dim3(64), 0, st, a);
+    hipLaunchKernelGGL(png_layout_kernel, dim3(a.n_images), dim3(1024), 0, st, a);
+    hipLaunchKernelGGL(png_emit_kernel, chunk_grid, dim3(kEmitThreads), 0, st, a);
+}
+
 }  // namespace ifhip
 
 using namespace ifhip;
@@ -480,12 +464,8 @@ int ifhip_png_encode_batch_device(ifhip_png_enc_stage* stage, const uint8_t* d_i
     a.tabs = stage->d_tabs; a.prefix = stage->d_prefix; a.chunk = stage->d_chunk; a.image = stage->d_image;
     a.n_images = n_images; a.stored_only = zlib_level == 0 ? 1u : 0u; a.zlib_header = png_zlib_header(zlib_level);
     a.files = d_files; a.file_pitch = file_pitch; a.lengths = d_lengths; a.status_out = d_status;
-    const dim3 chunk_grid(stage->n_chunks, n_images);
     hipLaunchKernelGGL(png_filter_kernel, dim3((stage->height + 3u) / 4u, n_images), dim3(256), 0, st, a);
-    hipLaunchKernelGGL(png_match_kernel, chunk_grid, dim3(kPngRound), 0, st, a);
-    hipLaunchKernelGGL(png_codes_kernel, chunk_grid, dim3(64), 0, st, a);
-    hipLaunchKernelGGL(png_layout_kernel, dim3(n_images), dim3(1024), 0, st, a);
-    hipLaunchKernelGGL(png_emit_kernel, chunk_grid, dim3(kEmitThreads), 0, st, a);
+    png_launch_deflate(a, st);
     hipLaunchKernelGGL(png_finish_kernel, dim3(n_images), dim3(1024), 0, st, a);
     HIP_TRY(hipGetLastError());
     return IFHIP_OK;

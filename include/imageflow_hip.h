@@ -447,6 +447,46 @@ IFHIP_API int ifhip_png_encode_batch_device(ifhip_png_enc_stage* stage, const ui
 IFHIP_API int ifhip_png_encode(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int color_type,
                                int zlib_level, uint8_t* out, size_t capacity, size_t* len);
 
+/* Device palette PNG coder: EncoderPreset::Pngquant {quality, minimum_quality, speed, maximum_deflate}
+ * (imageflow_types/src/lib.rs:756-761) without the host: what PngquantEncoder (codecs/pngquant.rs:35-139) has libimagequant
+ * and lode::LodepngEncoder::write_png8 (lode.rs:162-195) do -- at most 256 RGBA colours, Floyd-Steinberg dithering at full
+ * strength, an 8-bit palette PNG: colour type 3, filter 0 on every row, IHDR, PLTE, tRNS (only when an entry has alpha
+ * below 255; such entries come first), one IDAT, IEND, no gAMA / sRGB / cHRM -- on BGRA / BGRX frames that stay in HBM.
+ * The quantiser is this library's own: a frame of at most 256 distinct colours keeps exactly those (all pixels of alpha 0
+ * count as 00 00 00 00); otherwise the palette is NOT libimagequant's, and the quality scale is not pinned to it either.
+ * The zlib stream comes from the coder above (same blocks, same notes).  A stage owns the scratch of a call in flight and
+ * is bound to ONE stream at a time, like ifhip_png_enc_stage. */
+#define IFHIP_PNG_QUALITY_TOO_LOW 2
+typedef struct ifhip_png_quant_stage ifhip_png_quant_stage;
+/* refused: zero dimensions, more than 2^28 pixels, and frames of 1024 rows or more that are wider than 16384 pixels */
+IFHIP_API int ifhip_png_quant_stage_create(ifhip_png_quant_stage** stage, uint32_t width, uint32_t height, uint32_t max_images);
+IFHIP_API void ifhip_png_quant_stage_destroy(ifhip_png_quant_stage* stage);
+/* a file_pitch with which no file overflows: every block stored, plus the framing with a full PLTE and tRNS */
+IFHIP_API size_t ifhip_png_quant_stage_max_file_bytes(const ifhip_png_quant_stage* stage);
+/* n_images frames as in ifhip_png_encode_batch_device.  alpha_meaningful 0: every alpha byte counts as 255
+ * (normalize_unused_alpha).  quality / min_quality / speed as PngquantEncoder::create clamps them (codecs/pngquant.rs:50-57):
+ * speed 1..10, target = quality 0..100, minimum 0..target; a negative value stands for an absent one (100, 0, and
+ * libimagequant's default speed 4).  max_colors 2..256 (the preset passes 256), dither 0 or 1 (the preset passes 1),
+ * zlib_level as above (maximum_deflate: 9; it changes the FLEVEL bits only).
+ * Image i's file goes to d_files + i * file_pitch and its length to d_lengths[i].  d_status[i] (nullable):
+ * IFHIP_PNG_QUALITY_TOO_LOW when the palette's error, before dithering, is above what min_quality allows -- length 0, the
+ * caller writes a lossless file instead (codecs/pngquant.rs:105-139); IFHIP_PNG_FILE_OVERFLOW as above.  Neither touches
+ * the other images of the batch.  Nullable taps: d_palettes (per image 256 RGBA entries in file order, then the count
+ * as a little-endian u32: 1028 bytes), d_indices (per image width * height palette indices), d_mse (per image the mean
+ * error before dithering as a double, 1.0 = black against white).
+ * Asynchronous on hip_stream.  The same pixels give the same bytes on every run and in every batch position. */
+IFHIP_API int ifhip_png_quantize_batch_device(ifhip_png_quant_stage* stage, const uint8_t* d_images, size_t image_bytes,
+                                              uint32_t stride, int alpha_meaningful, uint32_t n_images, int quality,
+                                              int min_quality, int speed, uint32_t max_colors, int dither, int zlib_level,
+                                              uint8_t* d_files, size_t file_pitch, uint32_t* d_lengths, uint32_t* d_status,
+                                              uint8_t* d_palettes, uint8_t* d_indices, double* d_mse, void* hip_stream);
+/* The synchronous host-buffer form (codecs/pngquant.rs:35-139 up to the fallback): one frame, 256 colours, dithered,
+ * zlib level 6.  *status (nullable) gets the status word; with IFHIP_PNG_QUALITY_TOO_LOW the call succeeds and *len is 0.
+ * out == NULL: only *len (the size needed) is written. */
+IFHIP_API int ifhip_png_quantize(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int alpha_meaningful,
+                                 int quality, int min_quality, int speed, uint8_t* out, size_t capacity, size_t* len,
+                                 uint32_t* status);
+
 /* Device PNG decoder: what LibPngDecoder (imageflow_core/src/codecs/libpng_decoder.rs:36-104,297-299,340-383) gets from
  * libpng (c_components/lib/codec_png_wrapper.c:131-212 wrap_png_decode_image_info, :215-246 wrap_png_decode_finish, :266-292
  * wrap_png_decoder_get_info) -- all 15 legal (colour type, bit depth) pairs, interlaced or not, normalised to 8-bit BGRA in
