@@ -7,7 +7,7 @@ frame's padding, pre-filled with 0xA5, must come back untouched.  There is no to
 1 / 2 / 4 / 8; never interlaced); for the other pairs the seventh variant is zlib level 9 on Paeth rows.
 
 The damaged streams are the ones of tests/test_png_decode_core.py, green on the CPU emulation first, with the statuses
-that the emulation gives."""
+that the emulation gives.  Streams that zlib's encoder never writes are in tests/test_gpu_png_inflate_streams.py."""
 import io
 import struct
 import zlib

@@ -312,13 +312,33 @@ def test_a_filter_type_above_4_is_reported():
 
 
 # ---- the same cases under ASan + UBSan ---------------------------------------------------------------------------------------------
+def sanitizer_executable():
+    if "asan" not in _EMU:
+        d = tempfile.mkdtemp(prefix="png_decode_asan_")
+        exe = os.path.join(d, "png_decode_emulate_asan")
+        r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan",
+                            "-DPNG_DEC_EMU_MAIN", SRC, "-o", exe], capture_output=True, text=True)
+        if r.returncode != 0:                                           # (a toolchain without the static runtime)
+            subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DPNG_DEC_EMU_MAIN", SRC, "-o", exe], check=True)
+        _EMU["asan"] = exe
+    return _EMU["asan"]
+
+
+def run_under_sanitizers(cases):
+    """the packed cases of png_decode_emulate.cpp's main through the ASan + UBSan build -> its lines, "status produced crc32" each"""
+    exe = sanitizer_executable()
+    path = os.path.join(tempfile.mkdtemp(prefix="png_decode_cases_"), "cases.bin")
+    with open(path, "wb") as f:
+        f.write(b"".join(cases))
+    env = dict(os.environ, ASAN_OPTIONS="verify_asan_link_order=0:detect_leaks=0")
+    r = subprocess.run([exe, path], capture_output=True, text=True, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = r.stdout.split("\n")[:-1]
+    assert len(lines) == len(cases)
+    return lines
+
+
 def test_under_sanitizers_no_access_leaves_the_given_bounds():
-    d = tempfile.mkdtemp(prefix="png_decode_asan_")
-    exe = os.path.join(d, "png_decode_emulate_asan")
-    r = subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-static-libasan",
-                        "-DPNG_DEC_EMU_MAIN", SRC, "-o", exe], capture_output=True, text=True)
-    if r.returncode != 0:                                               # (a toolchain without the static runtime)
-        subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-DPNG_DEC_EMU_MAIN", SRC, "-o", exe], check=True)
     cases, want = [], []
     for name in sorted(GOOD):
         data, z = GOOD[name]
@@ -342,13 +362,7 @@ def test_under_sanitizers_no_access_leaves_the_given_bounds():
             stream = O.filtered_stream(s, ct, depth, [4, 3, 2, 1, 0], inter)
             cases.append(struct.pack("<IIIIIII", 1, 19, 70, ct, depth, int(inter), len(stream)) + stream)
             want.append((OK, len(stream), None))
-    path = os.path.join(d, "cases.bin")
-    with open(path, "wb") as f:
-        f.write(b"".join(cases))
-    env = dict(os.environ, ASAN_OPTIONS="verify_asan_link_order=0:detect_leaks=0")
-    r = subprocess.run([exe, path], capture_output=True, text=True, env=env)
-    assert r.returncode == 0, r.stderr[-3000:]
-    lines = r.stdout.split("\n")[:-1]
+    lines = run_under_sanitizers(cases)
     assert len(lines) == len(want)
     for line, w in zip(lines, want):
         st, n, crc = (int(v) for v in line.split())
