@@ -1496,23 +1496,40 @@ struct Job {
         return out;
     }
 
+    // The file a device coder writes for one frame: `pitch` bytes on the device, 16 to spare, and the coder's length and
+    // status words behind it at `tail` (the pitch, rounded up as the coder's caller chooses).
+    struct CodedFile {
+        uint8_t* d = nullptr;
+        uint32_t* d_len = nullptr;                                                   // length, status behind the file
+        uint32_t len = 0, status = 0;
+        ~CodedFile() { job_free(d); }
+        hipError_t alloc(size_t pitch, size_t tail) {
+            const hipError_t e = job_malloc(reinterpret_cast<void**>(&d), pitch + 16u);
+            if (e == hipSuccess) d_len = reinterpret_cast<uint32_t*>(d + tail);
+            return e;
+        }
+        void fetch(Io& o) {                                                          // after the coder's call; with status 0 the file goes into o.owned
+            uint32_t len_status[2] = {0, 0};
+            hip_check(static_cast<hipError_t>(ifhip::copy_to_host(len_status, d_len, 8)), "download(file length)");
+            len = len_status[0]; status = len_status[1];
+            if (status != 0 || len == 0) return;
+            o.owned.assign(len, 0);
+            hip_check(static_cast<hipError_t>(ifhip::copy_to_host(o.owned.data(), d, len)), "download(file)");
+        }
+    };
+
     // a truecolour PNG of the frame by the device coder (csrc/png_encode.hip): only the file's bytes leave the device
     void write_png(const FramePtr& f, int color_type, int level, Io& o, int32_t io_id) {
         ifhip_png_enc_stage* ps = nullptr;
         check(ifhip_png_enc_stage_create(&ps, f->w, f->h, color_type, 1));
         std::unique_ptr<ifhip_png_enc_stage, void (*)(ifhip_png_enc_stage*)> ps_guard(ps, [](ifhip_png_enc_stage* q) { quiesce(); ifhip_png_enc_stage_destroy(q); });
         const size_t pitch = (ifhip_png_enc_stage_max_file_bytes(ps) + 15u) & ~static_cast<size_t>(15u);
-        uint8_t* d_file = nullptr;
-        hip_check(job_malloc(reinterpret_cast<void**>(&d_file), pitch + 16u), "hipMalloc(png file)");
-        std::unique_ptr<uint8_t, void (*)(uint8_t*)> file_guard(d_file, [](uint8_t* p) { job_free(p); });
-        uint32_t* d_len = reinterpret_cast<uint32_t*>(d_file + pitch);               // length, status behind the file
-        check(ifhip_png_encode_batch_device(ps, dev(f), f->bytes(), f->stride, 1, level, d_file, pitch, d_len, d_len + 1, t_job_stream));
+        CodedFile file;
+        hip_check(file.alloc(pitch, pitch), "hipMalloc(png file)");
+        check(ifhip_png_encode_batch_device(ps, dev(f), f->bytes(), f->stride, 1, level, file.d, pitch, file.d_len, file.d_len + 1, t_job_stream));
         poll_cancel();
-        uint32_t len_status[2] = {0, 0};
-        hip_check(static_cast<hipError_t>(ifhip::copy_to_host(len_status, d_len, 8)), "download(file length)");
-        if (len_status[1] != 0 || len_status[0] == 0) raise(kInternalError, "InternalError: the PNG coder dropped a file sized for its worst case (status %u)", len_status[1]);
-        o.owned.assign(len_status[0], 0);
-        hip_check(static_cast<hipError_t>(ifhip::copy_to_host(o.owned.data(), d_file, len_status[0])), "download(file)");
+        file.fetch(o);
+        if (file.status != 0 || file.len == 0) raise(kInternalError, "InternalError: the PNG coder dropped a file sized for its worst case (status %u)", file.status);
         o.written = true;
         encodes.push_back({io_id, f->w, f->h, "image/png", "png"});
     }
@@ -1578,18 +1595,13 @@ struct Job {
                     if (ifhip_jpeg_enc_stage_create(&es, f->w, f->h, 3, hs, vs, bw, bh, 1, scan_cap) != IFHIP_OK) break;
                     std::unique_ptr<ifhip_jpeg_enc_stage, void (*)(ifhip_jpeg_enc_stage*)> es_guard(es, [](ifhip_jpeg_enc_stage* q) { quiesce(); ifhip_jpeg_enc_stage_destroy(q); });
                     const size_t pitch = ifhip_jpeg_enc_stage_max_file_bytes(es);
-                    uint8_t* d_file = nullptr;
-                    if (job_malloc(reinterpret_cast<void**>(&d_file), pitch + 16u) != hipSuccess) break;
-                    std::unique_ptr<uint8_t, void (*)(uint8_t*)> file_guard(d_file, [](uint8_t* p) { job_free(p); });
-                    uint32_t* d_len = reinterpret_cast<uint32_t*>(d_file + ((pitch + 3u) & ~static_cast<size_t>(3u)));   // length, status behind the file
-                    check(ifhip_jpeg_encode_batch_device(es, d_coef + off[0], d_coef + off[1], d_coef + off[2], quality, 1, d_file, pitch, d_len, d_len + 1, t_job_stream));
-                    uint32_t len_status[2] = {0, 0};
-                    hip_check(static_cast<hipError_t>(ifhip::copy_to_host(len_status, d_len, 8)), "download(file length)");
-                    if (len_status[1] & IFHIP_ENC_BAD_COEFFICIENT)
+                    CodedFile file;
+                    if (file.alloc(pitch, (pitch + 3u) & ~static_cast<size_t>(3u)) != hipSuccess) break;
+                    check(ifhip_jpeg_encode_batch_device(es, d_coef + off[0], d_coef + off[1], d_coef + off[2], quality, 1, file.d, pitch, file.d_len, file.d_len + 1, t_job_stream));
+                    file.fetch(o);
+                    if (file.status & IFHIP_ENC_BAD_COEFFICIENT)
                         raise(kArgumentInvalid, "InvalidArgument: coefficient out of range for 8-bit JPEG (more than 11 DC / 10 AC magnitude bits)");
-                    if (len_status[1] != 0) continue;
-                    o.owned.assign(len_status[0], 0);
-                    hip_check(static_cast<hipError_t>(ifhip::copy_to_host(o.owned.data(), d_file, len_status[0])), "download(file)");
+                    if (file.status != 0) continue;
                     o.written = true;
                     encodes.push_back({io_id, f->w, f->h, "image/jpeg", "jpg"});
                     c->device_coded_files.fetch_add(1, std::memory_order_relaxed);
@@ -1664,23 +1676,18 @@ struct Job {
             check(ifhip_png_quant_stage_create(&qs, f->w, f->h, 1));
             std::unique_ptr<ifhip_png_quant_stage, void (*)(ifhip_png_quant_stage*)> qs_guard(qs, [](ifhip_png_quant_stage* q) { quiesce(); ifhip_png_quant_stage_destroy(q); });
             const size_t pitch = (ifhip_png_quant_stage_max_file_bytes(qs) + 15u) & ~static_cast<size_t>(15u);
-            uint8_t* d_file = nullptr;
-            hip_check(job_malloc(reinterpret_cast<void**>(&d_file), pitch + 16u), "hipMalloc(png file)");
-            std::unique_ptr<uint8_t, void (*)(uint8_t*)> file_guard(d_file, [](uint8_t* p) { job_free(p); });
-            uint32_t* d_len = reinterpret_cast<uint32_t*>(d_file + pitch);               // length, status behind the file
+            CodedFile file;
+            hip_check(file.alloc(pitch, pitch), "hipMalloc(png file)");
             check(ifhip_png_quantize_batch_device(qs, dev(f), f->bytes(), f->stride, f->alpha ? 1 : 0, 1, quality, min_quality, speed, 256, 1, level,
-                                                  d_file, pitch, d_len, d_len + 1, nullptr, nullptr, nullptr, t_job_stream));
+                                                  file.d, pitch, file.d_len, file.d_len + 1, nullptr, nullptr, nullptr, t_job_stream));
             poll_cancel();
-            uint32_t len_status[2] = {0, 0};
-            hip_check(static_cast<hipError_t>(ifhip::copy_to_host(len_status, d_len, 8)), "download(file length)");
-            if (len_status[1] == IFHIP_PNG_QUALITY_TOO_LOW) {
+            file.fetch(o);
+            if (file.status == IFHIP_PNG_QUALITY_TOO_LOW) {
                 // pngquant.rs:105-139: below minimum_quality the frame is written losslessly, RGBA or RGB by its alpha
                 write_png(f, f->alpha ? IFHIP_PNG_RGBA : IFHIP_PNG_RGB, level, o, io_id);
                 return;
             }
-            if (len_status[1] != 0 || len_status[0] == 0) raise(kInternalError, "InternalError: the palette PNG coder dropped a file sized for its worst case (status %u)", len_status[1]);
-            o.owned.assign(len_status[0], 0);
-            hip_check(static_cast<hipError_t>(ifhip::copy_to_host(o.owned.data(), d_file, len_status[0])), "download(file)");
+            if (file.status != 0 || file.len == 0) raise(kInternalError, "InternalError: the palette PNG coder dropped a file sized for its worst case (status %u)", file.status);
             o.written = true;
             encodes.push_back({io_id, f->w, f->h, "image/png", "png"});
             return;

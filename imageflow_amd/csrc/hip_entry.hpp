@@ -69,6 +69,19 @@ struct HostFrame {
         if (side_out) HIP_TRY(hipMemcpy(side_out, side_output(), side, hipMemcpyDeviceToHost));
         return IFHIP_OK;
     }
+    // For a side output that is a coded file of `pitch` bytes, then its length, then its status word: waits, reads the two
+    // words and, where there is a file (status 0), copies it to `out` (null: the length alone) when `capacity` holds it.
+    int down_file(size_t pitch, uint8_t* out, size_t capacity, size_t* len, uint32_t* status) const {
+        HIP_TRY(hipStreamSynchronize(nullptr));
+        uint32_t len_status[2] = {0, 0};
+        HIP_TRY(hipMemcpy(len_status, side_output() + pitch, 8, hipMemcpyDeviceToHost));
+        *status = len_status[1];
+        *len = len_status[1] ? 0u : len_status[0];
+        if (!*len || !out) return IFHIP_OK;
+        if (capacity < *len) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: the file needs %zu bytes, the buffer has %zu", *len, capacity);
+        HIP_TRY(hipMemcpy(out, side_output(), *len, hipMemcpyDeviceToHost));
+        return IFHIP_OK;
+    }
 };
 
 }  // namespace ifhip

@@ -11,8 +11,9 @@
 //     is refined by Lloyd iterations with the palette and the 64-bit integer sums in LDS;
 //   * remap (a workgroup per image): nearest entry with Floyd-Steinberg error diffusion as a skewed wavefront -- lane L
 //     takes rows L, L + 1024, ..., two columns behind the lane above -- and writes the filtered stream itself;
-//   * match / codes / layout / emit of png_encode.hip, unchanged, on that stream with bpp = 1;
-//   * finish: IHDR (type 3), PLTE, tRNS, the IDAT framing with its CRC from the chunks' CRCs, and the body into place.
+//   * match / codes / layout / emit of the deflate back end (png_deflate.hip) on that stream with bpp = 1; the zlib body
+//     lands in the stage, since the size of the head in front of it is not known before the palette is;
+//   * finish: IHDR (type 3), PLTE, tRNS, the body into place and the IDAT framing around it (png_frame_device.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,7 +21,7 @@
 #include <memory>
 
 #include "hip_entry.hpp"
-#include "png_encode_args.hpp"
+#include "png_frame_device.hpp"      // (with png_deflate.hpp)
 #include "png_quantize_core.hpp"
 
 namespace ifhip {
@@ -35,7 +36,7 @@ struct QuantArgs {
     const uint8_t* images;
     size_t image_bytes;
     uint32_t stride, w, h, n_images;
-    uint32_t alpha, max_colors, dither, iterations, max_entries;
+    uint32_t alpha, max_colors, dither, iterations, max_entries, zlib_header;
     uint64_t bound_target, bound_min;
     uint32_t* tables;                   // [n_images][kPqLevels][2][kPqSlots]: slots, counts
     uint32_t* state;                    // [n_images][kPqStateWords]
@@ -201,7 +202,7 @@ struct RemapLds {
 };
 static_assert(sizeof(RemapLds) <= 160u * 1024u, "the remap's palette, rings and last row fit a workgroup's LDS");
 
-__global__ __launch_bounds__(kPqLanes) void pngq_remap_kernel(const QuantArgs a, const PngArgs png) {
+__global__ __launch_bounds__(kPqLanes) void pngq_remap_kernel(const QuantArgs a, const PngDeflateArgs png) {
     __shared__ RemapLds s;
     const uint32_t tid = threadIdx.x, img = blockIdx.x;
     const uint32_t* r = a.result + static_cast<size_t>(img) * kPqResultWords;
@@ -257,7 +258,7 @@ __global__ __launch_bounds__(kPqLanes) void pngq_remap_kernel(const QuantArgs a,
 }
 
 // ---- finish: the palette framing, the IDAT chunk's CRC and the body into place -----------------------------------------------------
-__global__ __launch_bounds__(256) void pngq_finish_kernel(const QuantArgs a, const PngArgs png) {
+__global__ __launch_bounds__(256) void pngq_finish_kernel(const QuantArgs a, const PngDeflateArgs png) {
     __shared__ uint32_t scratch[4];
     const uint32_t tid = threadIdx.x, img = blockIdx.y;
     const uint32_t* r = a.result + static_cast<size_t>(img) * kPqResultWords;
@@ -272,28 +273,12 @@ __global__ __launch_bounds__(256) void pngq_finish_kernel(const QuantArgs a, con
     }
     uint8_t* file = a.files + static_cast<size_t>(img) * a.file_pitch;
     uint8_t* idat = file + head;
-    const uint8_t* src = png.files + static_cast<size_t>(img) * png.file_pitch + kPngHeadBytes + 10u;
+    const uint8_t* src = png.body + static_cast<size_t>(img) * png.body_pitch;
     for (uint32_t i = blockIdx.x * 256u + tid; i < body; i += gridDim.x * 256u) idat[10u + i] = src[i];
     if (blockIdx.x != 0u) return;
-    uint32_t crc = 0;
-    for (uint32_t c = tid; c < png.n_chunks; c += 256u)
-        crc ^= png_crc_shift(*chunk_word(png, kCrc, img, c), static_cast<uint64_t>(body) - *chunk_word(png, kOffset, img, c) - *chunk_word(png, kBytes, img, c) + 4u);
-    if (tid == 255u) {                                           // the chunk type and the zlib header in front, the Adler-32 behind
-        png_be32(idat, zlen);
-        png_be32(idat + 4, kPngIDAT);
-        idat[8] = static_cast<uint8_t>(png.zlib_header >> 8); idat[9] = static_cast<uint8_t>(png.zlib_header);
-        png_be32(idat + 10u + body, adler);
-        crc ^= png_crc_shift(png_crc32(idat + 4, 6), static_cast<uint64_t>(body) + 4u) ^ png_crc32(idat + 10u + body, 4);
-    }
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) crc ^= __shfl_xor(crc, d, 64);
-    if ((tid & 63u) == 0u) scratch[tid >> 6] = crc;
-    __syncthreads();
+    png_frame_idat<256>(idat, body, adler, a.zlib_header, png, img, scratch);
     if (tid == 0u) {
-        crc = scratch[0] ^ scratch[1] ^ scratch[2] ^ scratch[3];
         pq_write_head(file, a.w, a.h, r + 8, count, n_trans);
-        png_be32(idat + 8u + zlen, crc);
-        png_close_chunk(idat + 12u + zlen, kPngIEND, 0);
         a.lengths[img] = static_cast<uint32_t>(total);
         if (a.status_out) a.status_out[img] = 0u;
     }
@@ -305,17 +290,13 @@ using namespace ifhip;
 
 struct ifhip_png_quant_stage {
     uint32_t width = 0, height = 0, max_images = 0;
-    uint32_t pitch = 0, stream_bytes = 0, n_chunks = 0;
-    size_t stream_pitch = 0, body_pitch = 0;
-    int device = -1;                    // -1: the scratch is not allocated yet (the first batch does it, behind the argument checks)
-    uint8_t *d_streams = nullptr, *d_body = nullptr;
-    uint32_t *d_tokens = nullptr, *d_counts = nullptr, *d_tabs = nullptr, *d_prefix = nullptr, *d_chunk = nullptr, *d_image = nullptr;
+    PngDeflateScratch deflate;
+    size_t body_pitch = 0;
+    uint8_t* d_body = nullptr;          // the zlib bodies, until finish knows where in the file they go
     uint32_t *d_tables = nullptr, *d_ekey = nullptr, *d_ew = nullptr, *d_result = nullptr;   // (the state words lie behind the tables)
     uint64_t* d_edmin = nullptr;
     ~ifhip_png_quant_stage() {
-        (void)DEV_FREE(d_streams); (void)DEV_FREE(d_body); (void)DEV_FREE(d_tokens); (void)DEV_FREE(d_counts); (void)DEV_FREE(d_tabs); (void)DEV_FREE(d_prefix);
-        (void)DEV_FREE(d_chunk); (void)DEV_FREE(d_image); (void)DEV_FREE(d_tables); (void)DEV_FREE(d_ekey); (void)DEV_FREE(d_ew); (void)DEV_FREE(d_result);
-        (void)DEV_FREE(d_edmin);
+        (void)DEV_FREE(d_body); (void)DEV_FREE(d_tables); (void)DEV_FREE(d_ekey); (void)DEV_FREE(d_ew); (void)DEV_FREE(d_result); (void)DEV_FREE(d_edmin);
     }
 };
 
@@ -323,27 +304,15 @@ namespace {
 size_t quant_table_words(size_t n) { return n * kPqLevels * 2u * kPqSlots; }
 
 int quant_stage_allocate(ifhip_png_quant_stage* s) {
-    int dev = -1;
-    if (int rc = require_gfx950(&dev)) return rc;
-    if (s->device >= 0) {
-        if (dev != s->device) return fail(IFHIP_INVALID_STATE, "InvalidState: stage belongs to device %d, current device is %d", s->device, dev);
-        return IFHIP_OK;
-    }
-    const size_t n = s->max_images, chunks = n * s->n_chunks;
-    HIP_TRY(DEV_MALLOC(&s->d_streams, n * s->stream_pitch));
+    if (int rc = s->deflate.allocate(s->max_images)) return rc;
+    if (s->d_result) return IFHIP_OK;                            // the stage's own buffers follow on the same device, this one last
+    const size_t n = s->max_images;
     HIP_TRY(DEV_MALLOC(&s->d_body, n * s->body_pitch));
-    HIP_TRY(DEV_MALLOC(&s->d_tokens, chunks * kPngChunk * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_counts, chunks * (kPngSyms + 4u) * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_tabs, chunks * (kPngSyms + 4u) * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_prefix, chunks * kPngPrefixWords * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_chunk, chunks * kChunkWords * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_image, n * 3u * sizeof(uint32_t)));
     HIP_TRY(DEV_MALLOC(&s->d_tables, (quant_table_words(n) + n * kPqStateWords) * sizeof(uint32_t)));
     HIP_TRY(DEV_MALLOC(&s->d_ekey, n * kPqMaxEntries * sizeof(uint32_t)));
     HIP_TRY(DEV_MALLOC(&s->d_ew, n * kPqMaxEntries * sizeof(uint32_t)));
     HIP_TRY(DEV_MALLOC(&s->d_edmin, n * kPqMaxEntries * sizeof(uint64_t)));
     HIP_TRY(DEV_MALLOC(&s->d_result, n * kPqResultWords * sizeof(uint32_t)));
-    s->device = dev;
     return IFHIP_OK;
 }
 int clamp_int(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
@@ -362,11 +331,8 @@ int ifhip_png_quant_stage_create(ifhip_png_quant_stage** stage, uint32_t width, 
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: a frame of %u rows or more is at most %u pixels wide (the remap's error row lies in LDS)", kPqLanes, kPqLastRowCols);
     std::unique_ptr<ifhip_png_quant_stage> s(new ifhip_png_quant_stage);
     s->width = width; s->height = height; s->max_images = max_images;
-    s->pitch = png_stream_pitch(width, 1u);
-    s->stream_bytes = static_cast<uint32_t>(static_cast<uint64_t>(s->pitch) * height);
-    s->n_chunks = (s->stream_bytes + kPngChunk - 1u) / kPngChunk;
-    s->stream_pitch = ((static_cast<size_t>(s->stream_bytes) + 15u) & ~static_cast<size_t>(15u)) + 16u;
-    s->body_pitch = ((static_cast<size_t>(s->stream_bytes) + 5u * s->n_chunks + 6u + kPngFraming + 15u) & ~static_cast<size_t>(15u)) + 16u;
+    s->deflate.shape(width, 1u, height);
+    s->body_pitch = (s->deflate.max_body_bytes() + 15u) & ~static_cast<size_t>(15u);
     *stage = s.release();
     return IFHIP_OK;
 }
@@ -374,8 +340,7 @@ int ifhip_png_quant_stage_create(ifhip_png_quant_stage** stage, uint32_t width, 
 void ifhip_png_quant_stage_destroy(ifhip_png_quant_stage* stage) { delete stage; }
 
 size_t ifhip_png_quant_stage_max_file_bytes(const ifhip_png_quant_stage* stage) {
-    // every chunk stored (its bytes + 5), the zlib header and Adler-32, the framing with a full PLTE and tRNS
-    return stage ? static_cast<size_t>(stage->stream_bytes) + 5u * stage->n_chunks + 6u + kPqFramingMax : 0u;
+    return stage ? stage->deflate.max_body_bytes() + kPqFramingMax : 0u;     // (the framing with a full PLTE and tRNS)
 }
 
 int ifhip_png_quantize_batch_device(ifhip_png_quant_stage* stage, const uint8_t* d_images, size_t image_bytes, uint32_t stride, int alpha_meaningful,
@@ -402,19 +367,14 @@ int ifhip_png_quantize_batch_device(ifhip_png_quant_stage* stage, const uint8_t*
     std::memset(&q, 0, sizeof q);
     q.images = d_images; q.image_bytes = image_bytes; q.stride = stride; q.w = stage->width; q.h = stage->height; q.n_images = n_images;
     q.alpha = alpha_meaningful ? 1u : 0u; q.max_colors = max_colors; q.dither = static_cast<uint32_t>(dither);
-    q.iterations = pq_speed_iterations(sp); q.max_entries = pq_speed_max_entries(sp);
+    q.iterations = pq_speed_iterations(sp); q.max_entries = pq_speed_max_entries(sp); q.zlib_header = png_zlib_header(zlib_level);
     q.bound_target = pq_quality_bound(static_cast<uint32_t>(target)); q.bound_min = pq_quality_bound(static_cast<uint32_t>(minimum));
     q.tables = stage->d_tables; q.state = stage->d_tables + quant_table_words(stage->max_images);
     q.ekey = stage->d_ekey; q.ew = stage->d_ew; q.edmin = stage->d_edmin; q.result = stage->d_result;
     q.palettes = d_palettes; q.indices = d_indices; q.mse = d_mse;
     q.files = d_files; q.file_pitch = file_pitch; q.lengths = d_lengths; q.status_out = d_status;
-    PngArgs a;
-    std::memset(&a, 0, sizeof a);
-    a.w = stage->width; a.h = stage->height; a.bpp = 1u; a.pitch = stage->pitch; a.color_type = 3u;
-    a.stream_bytes = stage->stream_bytes; a.n_chunks = stage->n_chunks; a.stream_pitch = stage->stream_pitch; a.streams = stage->d_streams;
-    a.tokens = stage->d_tokens; a.counts = stage->d_counts; a.tabs = stage->d_tabs; a.prefix = stage->d_prefix; a.chunk = stage->d_chunk;
-    a.image = stage->d_image; a.n_images = n_images; a.stored_only = zlib_level == 0 ? 1u : 0u; a.zlib_header = png_zlib_header(zlib_level);
-    a.files = stage->d_body; a.file_pitch = stage->body_pitch;      // the zlib body first lands in the stage; finish frames it
+    // the zlib body first lands in the stage, which has room for its worst case; finish copies it into its frame
+    const PngDeflateArgs a = stage->deflate.args(n_images, zlib_level, stage->d_body, stage->body_pitch, static_cast<uint32_t>(stage->deflate.max_body_bytes() - 6u));
     // the tables of the images in use and all state words: one clear (an empty slot is 0)
     HIP_TRY(hipMemsetAsync(q.tables, 0, quant_table_words(n_images) * sizeof(uint32_t), st));
     HIP_TRY(hipMemsetAsync(q.state, 0, static_cast<size_t>(n_images) * kPqStateWords * sizeof(uint32_t), st));
@@ -440,20 +400,14 @@ int ifhip_png_quantize(const uint8_t* bgra, uint32_t width, uint32_t height, uin
     const size_t pitch = (ifhip_png_quant_stage_max_file_bytes(stage) + 15u) & ~static_cast<size_t>(15u);
     HostFrame f;
     if (int rc = f.up(bgra, width, height, stride, pitch + 16u)) return rc;
-    uint8_t* d_file = f.side_output();
-    uint32_t* d_len = reinterpret_cast<uint32_t*>(d_file + pitch);
+    uint32_t* d_len = reinterpret_cast<uint32_t*>(f.side_output() + pitch);
     if (int rc = ifhip_png_quantize_batch_device(stage, f.d, f.image_bytes, stride, alpha_meaningful, 1, quality, min_quality, speed, kPqMaxColors, 1, 6,
-                                                 d_file, pitch, d_len, d_len + 1, nullptr, nullptr, nullptr, nullptr)) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    uint32_t len_status[2] = {0, 0};
-    HIP_TRY(hipMemcpy(len_status, d_len, 8, hipMemcpyDeviceToHost));
-    if (status) *status = len_status[1];
-    if (len_status[1] == kPqQualityTooLow) return IFHIP_OK;                // no file: the caller writes a lossless one (pngquant.rs:105-139)
-    if (len_status[1] || !len_status[0]) return fail(IFHIP_INVALID_STATE, "InvalidState: the file did not fit its worst-case size (status %u)", len_status[1]);
-    *len = len_status[0];
-    if (!out) return IFHIP_OK;
-    if (capacity < *len) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: the file needs %zu bytes, the buffer has %zu", *len, capacity);
-    HIP_TRY(hipMemcpy(out, d_file, *len, hipMemcpyDeviceToHost));
+                                                 f.side_output(), pitch, d_len, d_len + 1, nullptr, nullptr, nullptr, nullptr)) return rc;
+    uint32_t word = 0;
+    if (int rc = f.down_file(pitch, out, capacity, len, &word)) return rc;
+    if (status) *status = word;
+    if (word == kPqQualityTooLow) return IFHIP_OK;                         // no file: the caller writes a lossless one (pngquant.rs:105-139)
+    if (word || !*len) return fail(IFHIP_INVALID_STATE, "InvalidState: the file did not fit its worst-case size (status %u)", word);
     return IFHIP_OK;
 }
 

@@ -1,4 +1,5 @@
-// png_emulate.cpp -- the passes of csrc/png_encode.hip on the CPU, lane by lane, from the same core header
+// png_emulate.cpp -- the passes of csrc/png_encode.hip (filter, finish) and csrc/png_deflate.hip (match, codes, layout,
+// emit) on the CPU, lane by lane, from the same core header
 // (csrc/png_encode_core.hpp): the filter choice of a wave per row, the round-based parse of a workgroup per chunk (hash
 // table read before the round, pointer jumping for the greedy parse, highest position wins in the table), the code
 // construction, the bit placement and the checksum combination over slices.  tests/test_png_device_coder.py builds this

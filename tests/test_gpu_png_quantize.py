@@ -3,6 +3,7 @@ preset of `encode`): palettes, counts, index planes and whole files equal the CP
 the same core header) byte for byte, at the shapes where the remap's skewed wavefront can go wrong; a batch gives every
 frame the bytes it gets alone; an image that misses minimum_quality is dropped alone; and the preset writes palette files
 that Pillow and this library's own decoder read, with the lossless fall-back of the reference."""
+import ctypes as C
 import io
 import json
 import struct
@@ -107,6 +108,45 @@ def test_the_host_buffer_form_equals_the_device_form():
     assert status == 0 and host == device([rgba], True, stride=stride)[0][0]
     none, status = Q.quantize_png_host(E.bgra_rows(rgba, stride), w, h, stride, True, minimum_quality=100)
     assert none is None and status == Q.PNG_QUALITY_TOO_LOW
+
+
+def test_guard_regions_and_file_overflow():
+    """Where the zlib body lands and what a pitch below the file does, on a stream of two deflate chunks (201 x 170 bytes):
+    nothing outside a file's own bytes is written, and a file that does not fit its pitch is dropped with the status word."""
+    w, h, n = 200, 170, 3
+    frames = [E.photo_rgba(w, h, seed=21 + i) for i in range(n)]
+    alone = [device([f], False)[0][0] for f in frames]
+    frames_dev = bitmap(np.stack([E.bgra_rows(f) for f in frames]), w, h, False)
+    stage = Q.PngQuantStage(w, h, n, DEV)
+    L, guard = Q._bind(), 4096
+
+    def run(pitch):
+        files = torch.full((n * pitch + guard,), 0x5C, dtype=torch.uint8, device=DEV)
+        lengths = torch.full((n + 64,), -7, dtype=torch.int32, device=DEV)
+        status = torch.full((n + 64,), -9, dtype=torch.int32, device=DEV)
+        with torch.cuda.device(DEV):
+            assert L.ifhip_png_quantize_batch_device(stage._h, frames_dev.data.data_ptr(), frames_dev.image_bytes, frames_dev.stride, 0, n, -1, -1, -1,
+                                                     Q.MAX_COLORS, 1, Q.DEFAULT_ZLIB_LEVEL, files.data_ptr(), pitch, lengths.data_ptr(), status.data_ptr(),
+                                                     None, None, None, C.c_void_p(torch.cuda.current_stream().cuda_stream)) == 0
+            torch.cuda.synchronize()
+        assert bool((lengths[n:] == -7).all()) and bool((status[n:] == -9).all()), "the unused length / status words"
+        return files.cpu().numpy(), lengths[:n].cpu().tolist(), status[:n].cpu().tolist()
+
+    pitch = (stage.max_file_bytes + 15) // 16 * 16
+    host, ln, st = run(pitch)
+    assert st == [0] * n
+    assert (host[n * pitch:] == 0x5C).all(), "nothing behind the last pitch is touched"
+    for i in range(n):
+        assert 0 < ln[i] <= stage.max_file_bytes
+        assert host[i * pitch:i * pitch + ln[i]].tobytes() == alone[i], "the file the frame gets alone"
+        assert (host[i * pitch + ln[i]:(i + 1) * pitch] == 0x5C).all(), "nothing behind a file's end is touched"
+    # a pitch below the files (and above the entry's minimum, which is an argument error): every image is dropped with the
+    # status word, nothing is written
+    small = 2048
+    assert all(len(f) > small for f in alone)
+    host, ln, st = run(small)
+    assert ln == [0] * n and st == [Q.PNG_FILE_OVERFLOW] * n
+    assert (host == 0x5C).all()
 
 
 # ---- the `pngquant` preset of `encode` (csrc/abi_shim.cpp) ----------------------------------------------------------------------

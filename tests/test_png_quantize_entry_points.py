@@ -110,6 +110,6 @@ def test_quantize_kernels_use_no_scratch_and_fit_a_workgroups_lds():
         assert _int(r, "LDS Size [bytes/block]") <= 160 * 1024, (name, r)
         assert _int(r, "VGPRs") <= 512 // max(1, n // 256), (name, r)
     # the kernels of the shared deflate keep their names: the palette coder launches them, it does not fork them
-    shared = resource_usage(os.path.join(B.CSRC, "png_encode.hip"))
+    shared = resource_usage(os.path.join(B.CSRC, "png_deflate.hip"))
     for name in ("png_match_kernel", "png_codes_kernel", "png_layout_kernel", "png_emit_kernel"):
         assert name in shared and not any(name in k for k in rows), name
