@@ -1,0 +1,100 @@
+"""Host mirror of the lossless half of WebPEncoder (imageflow_core/src/codecs/webp.rs:281-345 over libwebp's
+WebPEncodeLosslessBGRA / WebPEncodeLosslessBGR; chosen in codecs/auto.rs:282-319) on the device WebP coder of
+libimageflow_hip.so (csrc/webp_encode.hip): BGRA / BGRX frames that stay in HBM -> complete lossless WebP (VP8L) files in
+HBM.  For tests and tools; the job path is the `webplossless` preset of `encode` (csrc/abi_shim.cpp)."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _native
+from ..graphics.bitmaps import Bitmap
+
+WEBP_FILE_OVERFLOW = 1                  # include/imageflow_hip.h IFHIP_WEBP_FILE_OVERFLOW
+MAX_DIMENSION = 16384                   # 14 bits of width - 1 and height - 1
+
+
+def _bind():
+    L = _native.lib()
+    if getattr(L, "_webp_enc_bound", False):
+        return L
+    L.ifhip_webp_enc_stage_create.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_int, C.c_uint32]
+    L.ifhip_webp_enc_stage_destroy.argtypes = [C.c_void_p]
+    L.ifhip_webp_enc_stage_destroy.restype = None
+    L.ifhip_webp_enc_stage_max_file_bytes.argtypes = [C.c_void_p]
+    L.ifhip_webp_enc_stage_max_file_bytes.restype = C.c_size_t
+    L.ifhip_webp_encode_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.c_size_t,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ifhip_webp_encode.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+    L._webp_enc_bound = True
+    return L
+
+
+class WebpEncodeStage:
+    """ifhip_webp_enc_stage: one geometry and alpha mode, the scratch of a batch in flight (one stream at a time)."""
+
+    def __init__(self, width, height, alpha_meaningful=True, max_images=1, device="cuda:0"):
+        L = _bind()
+        self.width, self.height, self.alpha_meaningful, self.max_images = width, height, bool(alpha_meaningful), max_images
+        self.device = torch.device(device)
+        self._h = C.c_void_p()
+        _native.check(L.ifhip_webp_enc_stage_create(C.byref(self._h), width, height, 1 if alpha_meaningful else 0, max_images))
+        self.max_file_bytes = int(L.ifhip_webp_enc_stage_max_file_bytes(self._h))
+
+    def encode_device(self, frames: Bitmap, file_pitch=None, files=None, lengths=None, status=None):
+        """frames: n BGRA frames of the stage's geometry.  Returns (files [n, file_pitch] uint8, lengths [n] int32, status [n]
+        int32), all cuda tensors; nothing is synchronised."""
+        L = _bind()
+        n = frames.n
+        if file_pitch is None:
+            file_pitch = files.shape[1] if files is not None else (self.max_file_bytes + 15) // 16 * 16
+        if files is None:
+            files = torch.empty((n, file_pitch), dtype=torch.uint8, device=self.device)
+        if lengths is None:
+            lengths = torch.zeros(n, dtype=torch.int32, device=self.device)
+        if status is None:
+            status = torch.zeros(n, dtype=torch.int32, device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            _native.check(L.ifhip_webp_encode_batch_device(self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride, n,
+                                                           files.data_ptr(), file_pitch, lengths.data_ptr(), status.data_ptr(), C.c_void_p(stream)))
+        return files, lengths, status
+
+    def encode(self, frames: Bitmap, file_pitch=None):
+        """The n files as bytes (None for a file that did not fit file_pitch) and the status words."""
+        files, lengths, status = self.encode_device(frames, file_pitch)
+        lengths, status = lengths.cpu().numpy(), status.cpu().numpy()
+        host = files[:, :max(int(lengths.max()), 1)].cpu().numpy()
+        return [host[i, :int(k)].tobytes() if k else None for i, k in enumerate(lengths)], [int(s) for s in status]
+
+    def __del__(self):
+        try:
+            if self._h:
+                torch.cuda.synchronize(self.device)
+                _bind().ifhip_webp_enc_stage_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+
+def encode_webp_lossless(bitmap: Bitmap):
+    """WebPEncoder::write_frame for EncoderPreset::WebPLossless on every frame of the bitmap: BGRA when the frame's alpha is
+    meaningful, else BGR (the file then says alpha_is_used = 0 and decodes to alpha 255); no matte.  Returns the files."""
+    stage = WebpEncodeStage(bitmap.w, bitmap.h, bitmap.alpha_meaningful, bitmap.n, bitmap.data.device)
+    files, status = stage.encode(bitmap)
+    if any(status):                                                       # (cannot happen with the stage's own pitch)
+        raise RuntimeError(f"device WebP coder dropped images: status {status}")
+    return files
+
+
+def encode_webp_host(bgra, width, height, stride, alpha_meaningful=True):
+    """Host-buffer drop-in (numpy): BGRA rows -> the file's bytes."""
+    L = _bind()
+    src = np.ascontiguousarray(bgra, np.uint8)
+    n = C.c_size_t(0)
+    h = C.c_void_p()
+    _native.check(L.ifhip_webp_enc_stage_create(C.byref(h), width, height, 1 if alpha_meaningful else 0, 1))   # (geometry only: for the bound)
+    out = np.empty(L.ifhip_webp_enc_stage_max_file_bytes(h), np.uint8)
+    L.ifhip_webp_enc_stage_destroy(h)
+    _native.check(L.ifhip_webp_encode(src.ctypes.data, width, height, stride, 1 if alpha_meaningful else 0, out.ctypes.data, out.size, C.byref(n)))
+    return out[:n.value].tobytes()

@@ -13,8 +13,9 @@
 //   * encode writes a real JPEG for the libjpeg_turbo preset -- baseline, optimised tables, progressive (device pixel stage + host Huffman coder, jpeg_write.cpp),
 //     a real PNG for the libpng preset (the device coder, png_encode.hip),
 //     a palette PNG for the pngquant preset (the device quantiser, png_quantize.hip),
+//     a lossless WebP for the webplossless preset (the device coder, webp_encode.hip),
 //     and that container for every other preset (preferred_extension "ifbgra", mime "application/x-imageflow-bgra"):
-//     the lodepng / GIF / WebP coders are out of scope, the caller's encoder takes the frame.
+//     the lodepng / GIF / lossy WebP coders are out of scope, the caller's encoder takes the frame.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -218,6 +219,17 @@ JVal parse_json(const uint8_t* buf, size_t n) {
     P.ws();
     if (P.p != P.end) P.bad("trailing characters");
     return v;
+}
+// Which coder `encode` hands a preset to (IFHIP_ENCODE_CODER_*): the object forms by their key, in the order `encode` asks;
+// EncoderPreset::WebPLossless is a unit variant, so its JSON is the string "webplossless".  Everything else -- "gif",
+// "webplossy" in any form, lodepng, no preset -- is the raw BGRA container.
+int encode_coder(const JVal* preset) {
+    if (!preset) return IFHIP_ENCODE_CODER_RAW;
+    if (preset->get("libjpeg_turbo")) return IFHIP_ENCODE_CODER_JPEG;
+    if (preset->get("libpng")) return IFHIP_ENCODE_CODER_PNG;
+    if (preset->get("pngquant")) return IFHIP_ENCODE_CODER_PNGQUANT;
+    if (preset->t == JVal::Str && preset->s == "webplossless") return IFHIP_ENCODE_CODER_WEBP_LOSSLESS;
+    return IFHIP_ENCODE_CODER_RAW;
 }
 int64_t want_int(const JVal& o, const char* key, const char* node) {
     const JVal* v = o.get(key);
@@ -1541,14 +1553,16 @@ struct Job {
     // (evalchroma, an external crate) is not reproduced: the file uses the maximum the reference allows (:133, 4:2:0).
     // EncoderPreset::Libpng is written as a real PNG by the device coder (csrc/png_encode.hip), EncoderPreset::Pngquant as
     // a palette PNG by the device quantiser (csrc/png_quantize.hip), or losslessly where it misses minimum_quality.
-    // EXTENSION: every other preset writes the raw BGRA container (lodepng / GIF / WebP coders are out of scope).
+    // EncoderPreset::WebPLossless is written as a real lossless WebP by the device coder (csrc/webp_encode.hip).
+    // EXTENSION: every other preset writes the raw BGRA container (lodepng / GIF / lossy WebP coders are out of scope).
     // `shared`: other consumers still read this frame -- the matte is then applied to a private copy.
     void encode(FramePtr f, int32_t io_id, const JVal* preset, bool shared) {
         Timed t(this, "primitive_encoder");
         Io& o = output(io_id);
         if (o.out_state == OutState::Taken) raise(kArgumentInvalid, "InvalidArgument: Output buffer for io_id %d has already been taken", io_id);
         poll_cancel();
-        const JVal* classic = preset ? preset->get("libjpeg_turbo") : nullptr;
+        const int coder = encode_coder(preset);
+        const JVal* classic = coder == IFHIP_ENCODE_CODER_JPEG ? preset->get("libjpeg_turbo") : nullptr;
         if (classic) {
             auto flag = [&](const char* k) { const JVal* v = classic->get(k); return v && v->t == JVal::Bool && v->b; };
             const int write_flags = (flag("progressive") ? IFHIP_JPEG_PROGRESSIVE : 0) | (flag("optimize_huffman_coding") ? IFHIP_JPEG_OPTIMIZE_HUFFMAN : 0);
@@ -1625,7 +1639,7 @@ struct Job {
             encodes.push_back({io_id, f->w, f->h, "image/jpeg", "jpg"});
             return;
         }
-        if (const JVal* png = preset ? preset->get("libpng") : nullptr) {
+        if (const JVal* png = coder == IFHIP_ENCODE_CODER_PNG ? preset->get("libpng") : nullptr) {
             // EncoderPreset::Libpng {depth, matte, zlib_compression} (imageflow_types/src/lib.rs:751-755, codecs/auto.rs:241-268)
             // -> LibPngEncoder::write_frame (codecs/libpng_encoder.rs:43-72): the file is coded on the device
             // (csrc/png_encode.hip), only its bytes leave it.
@@ -1655,7 +1669,7 @@ struct Job {
             write_png(f, color_type, level, o, io_id);
             return;
         }
-        if (const JVal* pq = preset ? preset->get("pngquant") : nullptr) {
+        if (const JVal* pq = coder == IFHIP_ENCODE_CODER_PNGQUANT ? preset->get("pngquant") : nullptr) {
             // EncoderPreset::Pngquant {quality, minimum_quality, speed, maximum_deflate} (imageflow_types/src/lib.rs:756-761)
             // -> PngquantEncoder (codecs/pngquant.rs:35-139): quantised, dithered and written as a palette PNG on the device
             // (csrc/png_quantize.hip); no matte (codecs/auto.rs:98-110).  The three numbers are u8.
@@ -1690,6 +1704,24 @@ struct Job {
             if (file.status != 0 || file.len == 0) raise(kInternalError, "InternalError: the palette PNG coder dropped a file sized for its worst case (status %u)", file.status);
             o.written = true;
             encodes.push_back({io_id, f->w, f->h, "image/png", "png"});
+            return;
+        }
+        if (coder == IFHIP_ENCODE_CODER_WEBP_LOSSLESS) {
+            // EncoderPreset::WebPLossless (imageflow_types/src/lib.rs:773, codecs/auto.rs:282-319) -> WebPEncoder::write_frame
+            // (codecs/webp.rs:281-345: WebPEncodeLosslessBGRA, or ...BGR when the frame's alpha is not meaningful); no matte
+            // (the reference passes None).  The file is coded on the device (csrc/webp_encode.hip), only its bytes leave it.
+            ifhip_webp_enc_stage* ws = nullptr;
+            check(ifhip_webp_enc_stage_create(&ws, f->w, f->h, f->alpha ? 1 : 0, 1));
+            std::unique_ptr<ifhip_webp_enc_stage, void (*)(ifhip_webp_enc_stage*)> ws_guard(ws, [](ifhip_webp_enc_stage* q) { quiesce(); ifhip_webp_enc_stage_destroy(q); });
+            const size_t pitch = (ifhip_webp_enc_stage_max_file_bytes(ws) + 15u) & ~static_cast<size_t>(15u);
+            CodedFile file;
+            hip_check(file.alloc(pitch, pitch), "hipMalloc(webp file)");
+            check(ifhip_webp_encode_batch_device(ws, dev(f), f->bytes(), f->stride, 1, file.d, pitch, file.d_len, file.d_len + 1, t_job_stream));
+            poll_cancel();
+            file.fetch(o);
+            if (file.status != 0 || file.len == 0) raise(kInternalError, "InternalError: the WebP coder dropped a file sized for its worst case (status %u)", file.status);
+            o.written = true;
+            encodes.push_back({io_id, f->w, f->h, "image/webp", "webp"});
             return;
         }
         o.owned.assign(kRawHeader + f->bytes(), 0);
@@ -2564,6 +2596,15 @@ bool imageflow_context_memory_free(struct imageflow_context* c, void* p, const c
     for (auto it = c->allocations.begin(); it != c->allocations.end(); ++it)
         if (it->get() == p) { c->allocations.erase(it); return true; }
     return false;
+}
+
+// the coder `encode` picks for a preset given as JSON text; -1 when the text is no JSON (include/imageflow_hip.h)
+int ifhip_encode_preset_coder(const char* preset_json, size_t len) {
+    if (!preset_json) return -1;
+    try {
+        const JVal v = parse_json(reinterpret_cast<const uint8_t*>(preset_json), len);
+        return encode_coder(&v);
+    } catch (...) { return -1; }
 }
 
 }  // extern "C"

@@ -487,6 +487,52 @@ IFHIP_API int ifhip_png_quantize(const uint8_t* bgra, uint32_t width, uint32_t h
                                  int quality, int min_quality, int speed, uint8_t* out, size_t capacity, size_t* len,
                                  uint32_t* status);
 
+/* Device lossless WebP coder: EncoderPreset::WebPLossless (imageflow_types/src/lib.rs EncoderPreset, chosen in
+ * codecs/auto.rs:282-319) without the host: what WebPEncoder::write_frame (codecs/webp.rs:281-345) has libwebp's
+ * WebPEncodeLosslessBGRA / WebPEncodeLosslessBGR do -- a VP8L stream in a RIFF container -- on BGRA / BGRX frames that stay
+ * in HBM.  A lossless coder is free in its choices: the file is NOT libwebp's byte for byte, it decodes through libwebp to
+ * exactly the frame's pixels.  The choices are this coder's own: subtract green, one of the 14 predictors per 16 x 16 tile,
+ * matches over the residual pixels one pixel back and one row up, a group of five prefix codes per band of 64 rows, no
+ * colour cache, no colour indexing.
+ * alpha_meaningful 0 (normalize_unused_alpha): every pixel is coded with alpha 255 and the header says alpha_is_used = 0.
+ * There is no matte (the reference passes None).  A stage owns the scratch of a call in flight (residuals, tokens, symbol
+ * counts, code tables, bit offsets; allocated by the first batch) and is bound to ONE stream at a time, like
+ * ifhip_png_enc_stage. */
+#define IFHIP_WEBP_FILE_OVERFLOW 1
+typedef struct ifhip_webp_enc_stage ifhip_webp_enc_stage;
+/* refused: zero dimensions, a width or a height above 16384 (the format's 14 bits), max_images outside 1..65535 */
+IFHIP_API int ifhip_webp_enc_stage_create(ifhip_webp_enc_stage** stage, uint32_t width, uint32_t height, int alpha_meaningful,
+                                          uint32_t max_images);
+IFHIP_API void ifhip_webp_enc_stage_destroy(ifhip_webp_enc_stage* stage);
+/* a file_pitch with which no file overflows, by arithmetic over the coder's choices (csrc/webp_encode_core.hpp
+ * webp_max_file_bytes): a band that would take more is written as literals under four flat codes, which gives 32 bits a
+ * pixel, plus the worst-case head, the bands' flat-code headers and the RIFF framing.  With it IFHIP_WEBP_FILE_OVERFLOW is never raised. */
+IFHIP_API size_t ifhip_webp_enc_stage_max_file_bytes(const ifhip_webp_enc_stage* stage);
+/* n_images frames of the stage's geometry at d_images + i * image_bytes (rows of `stride` bytes; the frame checks of every
+ * batch entry, made before the device is asked for).  Image i's file goes to d_files + i * file_pitch, its length to
+ * d_lengths[i] -- 0 when the file is longer than file_pitch, with IFHIP_WEBP_FILE_OVERFLOW in d_status[i] (nullable); its
+ * neighbours are untouched.  All of d_files' n_images * file_pitch bytes are written (zeros behind a file) and none
+ * beyond them; d_files must be 4-byte aligned, file_pitch may be any size from 28 bytes on.
+ * Asynchronous on hip_stream.  The same pixels give the same bytes on every run and in every batch position. */
+IFHIP_API int ifhip_webp_encode_batch_device(ifhip_webp_enc_stage* stage, const uint8_t* d_images, size_t image_bytes,
+                                             uint32_t stride, uint32_t n_images, uint8_t* d_files, size_t file_pitch,
+                                             uint32_t* d_lengths, uint32_t* d_status, void* hip_stream);
+/* The synchronous host-buffer drop-in for WebPEncodeLosslessBGRA / WebPEncodeLosslessBGR (codecs/webp.rs:281-345): one
+ * frame.  out == NULL: only *len (the size needed) is written. */
+IFHIP_API int ifhip_webp_encode(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int alpha_meaningful,
+                                uint8_t* out, size_t capacity, size_t* len);
+
+/* Which coder the shim's `encode` node hands an EncoderPreset to (imageflow_types/src/lib.rs:745-774, chosen in
+ * codecs/auto.rs), given the preset's JSON text: an object with the key libjpeg_turbo / libpng / pngquant, or the string
+ * "webplossless" (a unit variant); every other preset ("gif", webplossy in any form, lodepng, ...) gets the raw BGRA
+ * container.  -1: the text is no JSON.  Host only: it lets a test see the dispatch without a device. */
+#define IFHIP_ENCODE_CODER_RAW 0
+#define IFHIP_ENCODE_CODER_JPEG 1
+#define IFHIP_ENCODE_CODER_PNG 2
+#define IFHIP_ENCODE_CODER_PNGQUANT 3
+#define IFHIP_ENCODE_CODER_WEBP_LOSSLESS 4
+IFHIP_API int ifhip_encode_preset_coder(const char* preset_json, size_t len);
+
 /* Device PNG decoder: what LibPngDecoder (imageflow_core/src/codecs/libpng_decoder.rs:36-104,297-299,340-383) gets from
  * libpng (c_components/lib/codec_png_wrapper.c:131-212 wrap_png_decode_image_info, :215-246 wrap_png_decode_finish, :266-292
  * wrap_png_decoder_get_info) -- all 15 legal (colour type, bit depth) pairs, interlaced or not, normalised to 8-bit BGRA in
