@@ -24,8 +24,10 @@
 #include <memory>
 #include <vector>
 
+#include "block_scan.hpp"
 #include "hip_entry.hpp"
 #include "jpeg_encode_core.hpp"
+#include "stage_scratch.hpp"
 
 namespace ifhip {
 
@@ -70,34 +72,6 @@ struct LdsCoef {                    // a lane's block in LDS, slot order (jpeg_e
     __device__ __forceinline__ int32_t operator()(int k) const { return reinterpret_cast<const int16_t*>(w)[enc_slot(static_cast<uint32_t>(k))]; }
     __device__ __forceinline__ uint32_t pair(int j) const { return w[j]; }
 };
-
-__device__ __forceinline__ uint32_t wave_inclusive_scan(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u = __shfl_up(v, d, 64);
-        if (lane >= static_cast<uint32_t>(d)) v += u;
-    }
-    return v;
-}
-
-// exclusive scan over the T lanes of a workgroup (T a multiple of 64, <= 1024); *total = the sum.  `scratch`: T / 64 + 1 dwords.
-template <uint32_t T>
-__device__ __forceinline__ uint32_t block_exclusive_scan(uint32_t v, uint32_t* scratch, uint32_t* total) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t incl = wave_inclusive_scan(v, lane);
-    __syncthreads();                                       // (scratch may still be read from a previous call)
-    if (lane == 63u) scratch[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, sum = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < T / 64u; ++w) {
-        const uint32_t t = scratch[w];
-        if (w < wave) before += t;
-        sum += t;
-    }
-    *total = sum;
-    return before + incl - v;
-}
 
 // Stage the workgroup's 256 scan-order blocks into LDS -- coalesced 16-byte loads (eight lanes per block), stored in the
 // walk's slot order (zigzag positions, paired for the nonzero mask: enc_slot) -- and the tables.
@@ -363,7 +337,6 @@ struct ifhip_jpeg_enc_stage {
     size_t plane_blocks[3] = {0, 0, 0};
     uint32_t max_images = 0, n_wg = 0, max_chunks = 0;
     size_t cap_words = 0;
-    int device = -1;
     int header_quality = -1;
     uint32_t header_len = 0;
     // device buffers
@@ -371,12 +344,9 @@ struct ifhip_jpeg_enc_stage {
     uint16_t* d_nbits = nullptr;
     uint32_t *d_wg_bits = nullptr, *d_tot_bits = nullptr, *d_words = nullptr, *d_ff = nullptr, *d_tot_ff = nullptr, *d_status = nullptr;
     uint8_t* d_header = nullptr;
+    StageScratch blocks{&d_tabs, &d_nbits, &d_wg_bits, &d_tot_bits, &d_words, &d_ff, &d_tot_ff, &d_status, &d_header};
     uint8_t* h_header = nullptr;    // pinned
-    ~ifhip_jpeg_enc_stage() {
-        (void)DEV_FREE(d_tabs); (void)DEV_FREE(d_nbits); (void)DEV_FREE(d_wg_bits); (void)DEV_FREE(d_tot_bits); (void)DEV_FREE(d_words);
-        (void)DEV_FREE(d_ff); (void)DEV_FREE(d_tot_ff); (void)DEV_FREE(d_status); (void)DEV_FREE(d_header);
-        if (h_header) (void)cached_host_free(h_header);
-    }
+    ~ifhip_jpeg_enc_stage() { if (h_header) (void)cached_host_free(h_header); }
 };
 
 namespace {
@@ -460,18 +430,20 @@ int ifhip_jpeg_enc_stage_create(ifhip_jpeg_enc_stage** stage, uint32_t width, ui
     cap = (cap + kEncChunkBytes - 1u) / kEncChunkBytes * kEncChunkBytes + kEncChunkBytes;      // whole chunks, one to spare
     s->cap_words = static_cast<size_t>(cap / 4u);
     s->max_chunks = static_cast<uint32_t>(cap / kEncChunkBytes);
-    if (int arc = require_gfx950(&s->device)) return arc;
     s->max_images = max_images;
     const size_t n = max_images;
-    HIP_TRY(DEV_MALLOC(&s->d_tabs, 4096));
-    HIP_TRY(DEV_MALLOC(&s->d_nbits, n * s->g.nblocks * sizeof(uint16_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_wg_bits, n * s->n_wg * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_tot_bits, n * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_words, n * s->cap_words * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_ff, n * s->max_chunks * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_tot_ff, n * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_status, n * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_header, kHeaderCap));
+    if (int arc = s->blocks.ensure([&]() -> int {
+        HIP_TRY(DEV_MALLOC(&s->d_tabs, 4096));
+        HIP_TRY(DEV_MALLOC(&s->d_nbits, n * s->g.nblocks * sizeof(uint16_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_wg_bits, n * s->n_wg * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_tot_bits, n * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_words, n * s->cap_words * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_ff, n * s->max_chunks * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_tot_ff, n * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_status, n * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_header, kHeaderCap));
+        return IFHIP_OK;
+    })) return arc;
     HIP_TRY(static_cast<hipError_t>(cached_host_malloc(reinterpret_cast<void**>(&s->h_header), kHeaderCap)));
     uint32_t tabs[4][256];
     jpeg_std_encode_tables(tabs);
@@ -499,9 +471,7 @@ int ifhip_jpeg_encode_batch_device(ifhip_jpeg_enc_stage* stage, const int16_t* d
     if ((reinterpret_cast<uintptr_t>(d_coef0) | reinterpret_cast<uintptr_t>(d_coef1) | reinterpret_cast<uintptr_t>(d_coef2)) & 15u)
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: coefficient planes must be 16-byte aligned");
     if (file_pitch < kHeaderCap) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: file_pitch below %u bytes", kHeaderCap);
-    int dev = -1;
-    HIP_TRY(hipGetDevice(&dev));
-    if (dev != stage->device) return fail(IFHIP_INVALID_STATE, "InvalidState: stage belongs to device %d, current device is %d", stage->device, dev);
+    if (int rc = stage->blocks.check_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     if (quality != stage->header_quality) {
         uint16_t qt[2][64];

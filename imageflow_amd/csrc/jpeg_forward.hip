@@ -15,6 +15,7 @@
 #include <memory>
 
 #include "hip_entry.hpp"
+#include "stage_scratch.hpp"
 
 namespace ifhip {
 
@@ -340,7 +341,7 @@ int ifhip_jpeg_forward_batch_device(ifhip_jpeg_fwd_stage* stage, const uint8_t* 
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: coefficient planes must be 16-byte aligned");
     int dev = -1;
     HIP_TRY(hipGetDevice(&dev));
-    if (dev != stage->device) return fail(IFHIP_INVALID_STATE, "InvalidState: stage belongs to device %d, current device is %d", stage->device, dev);
+    if (int rc = stage_on_device(stage->device, dev)) return rc;
     FwdArgs a;
     std::memset(&a, 0, sizeof a);
     a.g = stage->g; a.bgra = d_bgra; a.image_bytes = image_bytes; a.stride = stride; a.n_images = n_images; a.qt = d_qt;

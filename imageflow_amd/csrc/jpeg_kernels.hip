@@ -23,6 +23,7 @@
 #include <mutex>
 
 #include "hip_entry.hpp"
+#include "stage_scratch.hpp"
 
 namespace ifhip {
 
@@ -1172,7 +1173,7 @@ static int stage_args(ifhip_jpeg_stage* stage, const int16_t* d_coef0, const int
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: coefficient planes and quantisation tables must be 16-byte aligned");
     int dev = -1;
     HIP_TRY(hipGetDevice(&dev));
-    if (dev != stage->device) return fail(IFHIP_INVALID_STATE, "InvalidState: stage belongs to device %d, current device is %d", stage->device, dev);
+    if (int rc = stage_on_device(stage->device, dev)) return rc;
     JpegArgs& a = *out;
     std::memset(&a, 0, sizeof a);
     a.g = stage->g;

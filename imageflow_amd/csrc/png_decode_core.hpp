@@ -114,7 +114,7 @@ IFHIP_HD bool png_build_huff(X& x, PngHuff& H, const uint8_t* lens, uint32_t n, 
         for (uint32_t i = lane; i < used; i += kInfLanes) {
             const uint32_t s = H.symbol[i], l = lens[s];
             if (l > kInfFastBits) continue;
-            const uint32_t rev = png_reverse_bits(H.first[l] + (i - H.offs[l]), l);
+            const uint32_t rev = reverse_bits(H.first[l] + (i - H.offs[l]), l);
             for (uint32_t k = rev; k < (1u << kInfFastBits); k += 1u << l) H.fast[k] = static_cast<uint16_t>(s << 4 | l);
         }
     });

@@ -7,41 +7,16 @@
 //   * the bit position: a chunk is one deflate block closed to a byte boundary (an empty stored block, as a zlib sync
 //     flush writes), so chunks meet at byte offsets: exact sizes from the histograms -> scan -> write.
 // Launches per batch (all images in each): match (a workgroup per chunk), codes (a wave per chunk: 316 symbols), layout
-// (scan of the chunk sizes per image), emit (a workgroup per chunk).  Every rule with a bit in it lives in
-// png_encode_core.hpp, shared with the CPU emulation of the tests (tests/png_emulate.cpp).
+// (scan of the chunk sizes per image), emit (a workgroup per chunk).  Every rule with a bit in it lives in png_encode_core.hpp
+// and, where every prefix code shares it, prefix_code_core.hpp; the CPU emulation of the tests compiles both (tests/png_emulate.cpp).
 #include <hip/hip_runtime.h>
 
+#include "block_scan.hpp"
 #include "hip_entry.hpp"
 #include "png_frame_device.hpp"      // (with png_deflate.hpp and png_encode_core.hpp)
 
 namespace ifhip {
 
-__device__ __forceinline__ uint32_t png_wave_inclusive_scan(uint32_t v, uint32_t lane) {
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t u = __shfl_up(v, d, 64);
-        if (lane >= static_cast<uint32_t>(d)) v += u;
-    }
-    return v;
-}
-// exclusive scan over the T lanes of a workgroup; *total = the sum.  `scratch`: T / 64 dwords.
-template <uint32_t T>
-__device__ __forceinline__ uint32_t png_block_scan(uint32_t v, uint32_t* scratch, uint32_t* total) {
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    const uint32_t incl = png_wave_inclusive_scan(v, lane);
-    __syncthreads();
-    if (lane == 63u) scratch[wave] = incl;
-    __syncthreads();
-    uint32_t before = 0, sum = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < T / 64u; ++w) {
-        const uint32_t t = scratch[w];
-        if (w < wave) before += t;
-        sum += t;
-    }
-    *total = sum;
-    return before + incl - v;
-}
 // Adler-32 of T pieces in order (ad / ln: checksum and length of every lane's piece, in LDS): a tree of combinations;
 // the result is ad[0], ln[0]
 template <uint32_t T>
@@ -136,7 +111,7 @@ __global__ __launch_bounds__(kPngRound) void png_match_kernel(const PngDeflateAr
             }
             const bool emitted = valid && s.mark[tid];
             uint32_t total;
-            const uint32_t ex = png_block_scan<kPngRound>(emitted ? 1u : 0u, s.scratch, &total);
+            const uint32_t ex = block_exclusive_scan<kPngRound>(emitted ? 1u : 0u, s.scratch, &total);
             if (emitted) {
                 if (len >= kPngMinMatch) {
                     uint32_t sym, eb, ev;
@@ -169,12 +144,12 @@ __global__ __launch_bounds__(64) void png_codes_kernel(const PngDeflateArgs a) {
     const uint32_t* counts = a.counts + chunk_index(a, img, c) * (kPngSyms + 4u);
     for (uint32_t i = lane; i < kPngSyms + 4u; i += 64u) W.cnt[i] = counts[i];
     __syncthreads();
-    png_rank_sort_lane(W.cnt, kPngLL, lane, 64u, W.sorted);
+    code_rank_sort_lane(W.cnt, kPngLL, lane, 64u, W.sorted);
     __syncthreads();
     if (lane == 0u) {
-        png_build_lengths(W, W.cnt, kPngLL, 15, W.len, 256, true);
-        png_rank_sort_lane(W.cnt + kPngLL, kPngD, 0, 1, W.sorted);
-        png_build_lengths(W, W.cnt + kPngLL, kPngD, 15, W.len + kPngLL, 0, false);
+        code_build_lengths(W, W.cnt, kPngLL, 15, W.len, 256, true);
+        code_rank_sort_lane(W.cnt + kPngLL, kPngD, 0, 1, W.sorted);
+        code_build_lengths(W, W.cnt + kPngLL, kPngD, 15, W.len + kPngLL, 0, false);
         const uint32_t n = min(kPngChunk, a.stream_bytes - c * kPngChunk);
         uint32_t type;
         plan[1] = png_plan_block(W, n, c + 1u == a.n_chunks, a.stored_only != 0u, &type);
@@ -205,7 +180,7 @@ __global__ __launch_bounds__(1024) void png_layout_kernel(const PngDeflateArgs a
         const bool in = c < a.n_chunks;
         const uint32_t nb = in ? *chunk_word(a, kBytes, img, c) : 0u;
         uint32_t total;
-        const uint32_t ex = png_block_scan<1024>(nb, scratch, &total);
+        const uint32_t ex = block_exclusive_scan<1024>(nb, scratch, &total);
         if (in) *chunk_word(a, kOffset, img, c) = carry + ex;
         carry += total;
         ad[tid] = in ? *chunk_word(a, kAdler, img, c) : 1u;
@@ -264,8 +239,8 @@ __global__ __launch_bounds__(kEmitThreads) void png_emit_kernel(const PngDeflate
             if (i < ntok) bits = png_token_bits(tab, tokens[i], &val);
             else if (i == ntok) { val = tab[256] & 0xFFFFu; bits = tab[256] >> 16; }
             uint32_t total;
-            const uint32_t at = pos + png_block_scan<kEmitThreads>(bits, scratch, &total);
-            if (bits && (at >> 5) + 3u <= kEmitWords) png_or_bits(out, at, val, or_word);
+            const uint32_t at = pos + block_exclusive_scan<kEmitThreads>(bits, scratch, &total);
+            if (bits && (at >> 5) + 3u <= kEmitWords) or_bits(out, at, val, or_word);
             pos += total;
         }
         __syncthreads();
@@ -295,10 +270,6 @@ void png_launch_deflate(const PngDeflateArgs& a, hipStream_t st) {
 }
 
 // ---- the scratch ----------------------------------------------------------------------------------------------------------------
-PngDeflateScratch::~PngDeflateScratch() {
-    (void)DEV_FREE(d_streams); (void)DEV_FREE(d_tokens); (void)DEV_FREE(d_counts); (void)DEV_FREE(d_tabs); (void)DEV_FREE(d_prefix);
-    (void)DEV_FREE(d_chunk); (void)DEV_FREE(d_image);
-}
 void PngDeflateScratch::shape(uint32_t width, uint32_t bytes_per_pixel, uint32_t height) {
     bpp = bytes_per_pixel;
     pitch = png_stream_pitch(width, bpp);
@@ -307,19 +278,17 @@ void PngDeflateScratch::shape(uint32_t width, uint32_t bytes_per_pixel, uint32_t
     stream_pitch = ((static_cast<size_t>(stream_bytes) + 15u) & ~static_cast<size_t>(15u)) + 16u;
 }
 int PngDeflateScratch::allocate(uint32_t max_images) {
-    int dev = -1;
-    if (int rc = require_gfx950(&dev)) return rc;
-    if (device >= 0) return dev == device ? IFHIP_OK : fail(IFHIP_INVALID_STATE, "InvalidState: stage belongs to device %d, current device is %d", device, dev);
     const size_t n = max_images, chunks = n * n_chunks;
-    HIP_TRY(DEV_MALLOC(&d_streams, n * stream_pitch));
-    HIP_TRY(DEV_MALLOC(&d_tokens, chunks * kPngChunk * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&d_counts, chunks * (kPngSyms + 4u) * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&d_tabs, chunks * (kPngSyms + 4u) * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&d_prefix, chunks * kPngPrefixWords * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&d_chunk, chunks * kChunkWords * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&d_image, n * 3u * sizeof(uint32_t)));
-    device = dev;
-    return IFHIP_OK;
+    return blocks.ensure([&]() -> int {
+        HIP_TRY(DEV_MALLOC(&d_streams, n * stream_pitch));
+        HIP_TRY(DEV_MALLOC(&d_tokens, chunks * kPngChunk * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&d_counts, chunks * (kPngSyms + 4u) * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&d_tabs, chunks * (kPngSyms + 4u) * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&d_prefix, chunks * kPngPrefixWords * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&d_chunk, chunks * kChunkWords * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&d_image, n * 3u * sizeof(uint32_t)));
+        return IFHIP_OK;
+    });
 }
 PngDeflateArgs PngDeflateScratch::args(uint32_t n_images, int zlib_level, uint8_t* body, size_t body_pitch, uint32_t body_cap) const {
     return PngDeflateArgs{d_streams, stream_pitch, stream_bytes, pitch, bpp, n_chunks, n_images, zlib_level == 0 ? 1u : 0u,

@@ -7,6 +7,8 @@
 #include <cstddef>
 #include <cstdint>
 
+#include "stage_scratch.hpp"
+
 namespace ifhip {
 
 struct PngDeflateArgs {
@@ -38,10 +40,9 @@ void png_launch_deflate(const PngDeflateArgs& a, hipStream_t stream);
 struct PngDeflateScratch {
     uint32_t bpp = 0, pitch = 0, stream_bytes = 0, n_chunks = 0;
     size_t stream_pitch = 0;
-    int device = -1;                    // -1: not allocated yet (the first batch does it, behind the argument checks)
     uint8_t* d_streams = nullptr;
     uint32_t *d_tokens = nullptr, *d_counts = nullptr, *d_tabs = nullptr, *d_prefix = nullptr, *d_chunk = nullptr, *d_image = nullptr;
-    ~PngDeflateScratch();
+    StageScratch blocks{&d_streams, &d_tokens, &d_counts, &d_tabs, &d_prefix, &d_chunk, &d_image};   // allocated by the first batch, behind the argument checks
     void shape(uint32_t width, uint32_t bytes_per_pixel, uint32_t height);   // (the caller has checked that the stream is below 2^31 bytes)
     size_t max_body_bytes() const { return static_cast<size_t>(stream_bytes) + 5u * n_chunks + 6u; }   // every chunk stored (+ 5), zlib header, Adler-32
     int allocate(uint32_t max_images);  // the first call allocates on the current device, later ones check that it still is the current one

@@ -5,8 +5,8 @@
 // and the chunk framing with its CRCs.  8-bit RGB or RGBA, non-interlaced, gAMA / sRGB / cHRM in front of one IDAT.
 // Launches per batch (all images in each): filter (a wave per row) into the streams of the deflate back end, its match /
 // codes / layout / emit (png_deflate.hip), which write the zlib body straight into the caller's file, and finish (the
-// head, and the IDAT framing of png_frame_device.hpp).  Every rule with a bit in it lives in png_encode_core.hpp, shared
-// with the CPU emulation of the tests (tests/png_emulate.cpp).
+// head, and the IDAT framing of png_frame_device.hpp).  Every rule with a bit in it lives in png_encode_core.hpp (the
+// construction of the prefix codes: prefix_code_core.hpp), shared with the CPU emulation of the tests (tests/png_emulate.cpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

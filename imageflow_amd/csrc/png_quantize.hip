@@ -295,9 +295,7 @@ struct ifhip_png_quant_stage {
     uint8_t* d_body = nullptr;          // the zlib bodies, until finish knows where in the file they go
     uint32_t *d_tables = nullptr, *d_ekey = nullptr, *d_ew = nullptr, *d_result = nullptr;   // (the state words lie behind the tables)
     uint64_t* d_edmin = nullptr;
-    ~ifhip_png_quant_stage() {
-        (void)DEV_FREE(d_body); (void)DEV_FREE(d_tables); (void)DEV_FREE(d_ekey); (void)DEV_FREE(d_ew); (void)DEV_FREE(d_result); (void)DEV_FREE(d_edmin);
-    }
+    StageScratch blocks{&d_body, &d_tables, &d_ekey, &d_ew, &d_edmin, &d_result};
 };
 
 namespace {
@@ -305,15 +303,16 @@ size_t quant_table_words(size_t n) { return n * kPqLevels * 2u * kPqSlots; }
 
 int quant_stage_allocate(ifhip_png_quant_stage* s) {
     if (int rc = s->deflate.allocate(s->max_images)) return rc;
-    if (s->d_result) return IFHIP_OK;                            // the stage's own buffers follow on the same device, this one last
     const size_t n = s->max_images;
-    HIP_TRY(DEV_MALLOC(&s->d_body, n * s->body_pitch));
-    HIP_TRY(DEV_MALLOC(&s->d_tables, (quant_table_words(n) + n * kPqStateWords) * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_ekey, n * kPqMaxEntries * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_ew, n * kPqMaxEntries * sizeof(uint32_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_edmin, n * kPqMaxEntries * sizeof(uint64_t)));
-    HIP_TRY(DEV_MALLOC(&s->d_result, n * kPqResultWords * sizeof(uint32_t)));
-    return IFHIP_OK;
+    return s->blocks.ensure([&]() -> int {                       // the stage's own buffers, on the same device
+        HIP_TRY(DEV_MALLOC(&s->d_body, n * s->body_pitch));
+        HIP_TRY(DEV_MALLOC(&s->d_tables, (quant_table_words(n) + n * kPqStateWords) * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_ekey, n * kPqMaxEntries * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_ew, n * kPqMaxEntries * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_edmin, n * kPqMaxEntries * sizeof(uint64_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_result, n * kPqResultWords * sizeof(uint32_t)));
+        return IFHIP_OK;
+    });
 }
 int clamp_int(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 }  // namespace

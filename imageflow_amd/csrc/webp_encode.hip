@@ -18,15 +18,17 @@
 //   emit      a workgroup per segment (bits into an LDS window, shifted by the segment's bit offset; the one word two
 //             neighbours share is ORed atomically into the zeroed file) and per group header
 //   finish    RIFF framing, lengths, status
-// Every rule with a bit in it lives in webp_encode_core.hpp, shared with the CPU emulation of the tests
-// (tests/webp_emulate.cpp).  Everything reduced across lanes is an integer sum or an OR: the same pixels give the same
+// Every rule with a bit in it lives in webp_encode_core.hpp (VP8L's own) and prefix_code_core.hpp (what every prefix
+// code shares), both compiled into the CPU emulation of the tests as well (tests/webp_emulate.cpp).  Everything reduced across lanes is an integer sum or an OR: the same pixels give the same
 // bytes on every run and in every batch position.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <memory>
 
+#include "block_scan.hpp"
 #include "hip_entry.hpp"
+#include "stage_scratch.hpp"
 #include "webp_encode_core.hpp"
 
 namespace ifhip {
@@ -68,22 +70,6 @@ struct GlobalOr {
 __device__ __forceinline__ GlobalOr webp_global_or(const WebpArgs& a, uint32_t img) {
     const uintptr_t end = reinterpret_cast<uintptr_t>(a.files) + static_cast<size_t>(img + 1u) * a.file_pitch;
     return GlobalOr{(end & 3u) ? reinterpret_cast<uint32_t*>(end & ~static_cast<uintptr_t>(3)) : nullptr, a.image + 4u * img + 2u};
-}
-
-// exclusive sum of v over a workgroup of 1024 lanes (wave sums meet in wsum[16]); *total: the workgroup's sum
-__device__ __forceinline__ uint32_t block_exscan(uint32_t v, uint32_t* wsum, uint32_t* total) {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const uint32_t o = __shfl_up(inc, d, 64); if (lane >= static_cast<uint32_t>(d)) inc += o; }
-    __syncthreads();                                           // (wsum may still be read from the call before)
-    if (lane == 63u) wsum[wave] = inc;
-    __syncthreads();
-    uint32_t before = 0, all = 0;
-    const uint32_t waves = blockDim.x >> 6;
-    for (uint32_t k = 0; k < waves; ++k) { const uint32_t s = wsum[k]; if (k < wave) before += s; all += s; }
-    *total = all;
-    return before + inc - v;
 }
 
 // ---- residual: a workgroup per tile, a lane per pixel ----------------------------------------------------------------------------
@@ -221,7 +207,7 @@ __global__ __launch_bounds__(1024) void webp_parse_kernel(const WebpArgs a) {
 __device__ __forceinline__ void webp_build_codes(WebpCodeWork& W, const uint32_t* cnt, uint32_t* tab, uint32_t* hdr, uint32_t* pos, bool force_flat) {
     for (uint32_t al = 0; al < 5u; ++al) {
         const uint32_t off = webp_alphabet_offset(al);
-        png_rank_sort_lane(cnt + off, webp_alphabet_size(al), threadIdx.x, blockDim.x, W.P.sorted);
+        code_rank_sort_lane(cnt + off, webp_alphabet_size(al), threadIdx.x, blockDim.x, W.P.sorted);
         __syncthreads();
         if (threadIdx.x == 0u) { uint32_t fixed; webp_build_code(W, cnt + off, al, tab + off, hdr, pos, &fixed, force_flat); }
         __syncthreads();
@@ -304,8 +290,8 @@ __device__ __forceinline__ void webp_emit_sub_image(uint32_t* words, uint64_t wh
         uint64_t v = 0;
         const uint32_t nb = i < count ? webp_token_bits(tab, 1u, pixel(i), &v) : 0u;
         uint32_t total;
-        const uint32_t ex = block_exscan(nb, wsum, &total);
-        if (nb) webp_or_bits(words, where + ex, v, go);
+        const uint32_t ex = block_exclusive_scan<1024>(nb, wsum, &total);
+        if (nb) or_bits(words, where + ex, v, go);
         where += total;
     }
 }
@@ -361,7 +347,7 @@ __global__ __launch_bounds__(1024) void webp_layout_kernel(const WebpArgs a) {
         const uint32_t seg = base + tid;
         const uint32_t bits = seg < a.S.n_segs ? a.seg_bits[static_cast<size_t>(img) * a.S.n_segs + seg] : 0u;
         uint32_t total;
-        const uint32_t ex = block_exscan(bits, wsum, &total);  // (1024 segments hold fewer than 2^32 bits)
+        const uint32_t ex = block_exclusive_scan<1024>(bits, wsum, &total);  // (1024 segments hold fewer than 2^32 bits)
         if (seg < a.S.n_segs) a.seg_off[static_cast<size_t>(img) * a.S.n_segs + seg] = at + ex;
         at += total;
     }
@@ -376,8 +362,8 @@ __global__ __launch_bounds__(1024) void webp_layout_kernel(const WebpArgs a) {
     uint32_t origin;
     uint32_t* words = webp_payload_words(a, img, &origin);
     const GlobalOr go = webp_global_or(a, img);
-    for (uint32_t i = tid; i < (front_bits + 31u) / 32u; i += 1024u) webp_or_bits(words, origin + 32ull * i, front[i], go);
-    for (uint32_t i = tid; i < (middle_bits + 31u) / 32u; i += 1024u) webp_or_bits(words, origin + at_middle + 32ull * i, middle[i], go);
+    for (uint32_t i = tid; i < (front_bits + 31u) / 32u; i += 1024u) or_bits(words, origin + 32ull * i, front[i], go);
+    for (uint32_t i = tid; i < (middle_bits + 31u) / 32u; i += 1024u) or_bits(words, origin + at_middle + 32ull * i, middle[i], go);
     webp_emit_sub_image(words, origin + at_mode_px, mode_tab, n_tiles, wsum, go, [&](uint32_t i) { return 0xFF000000u | (static_cast<uint32_t>(modes[i]) << 8); });
     webp_emit_sub_image(words, origin + at_ent_px, ent_tab, n_ent, wsum, go, [&](uint32_t i) { return 0xFF000000u | ((i / ent_x) << 8); });
 }
@@ -395,7 +381,7 @@ __global__ __launch_bounds__(1024) void webp_emit_kernel(const WebpArgs a) {
         const size_t g = static_cast<size_t>(img) * a.S.n_bands + (blockIdx.x - a.S.n_segs);
         const uint32_t bits = a.grp_hbits[g];
         const uint64_t where = origin + a.grp_off[g];
-        for (uint32_t i = tid; i < (bits + 31u) / 32u; i += 1024u) webp_or_bits(words, where + 32ull * i, a.grp_hdr[g * kWebpGroupWords + i], go);
+        for (uint32_t i = tid; i < (bits + 31u) / 32u; i += 1024u) or_bits(words, where + 32ull * i, a.grp_hdr[g * kWebpGroupWords + i], go);
         return;
     }
     const uint32_t seg = blockIdx.x;
@@ -426,10 +412,10 @@ __global__ __launch_bounds__(1024) void webp_emit_kernel(const WebpArgs a) {
         mine += nb[k];
     }
     uint32_t total;
-    uint32_t at = shift + block_exscan(mine, wsum, &total);
+    uint32_t at = shift + block_exclusive_scan<1024>(mine, wsum, &total);
 #pragma unroll
     for (uint32_t k = 0; k < 4u; ++k) {
-        if (nb[k]) webp_or_bits(win, at, v[k], [](uint32_t* p, uint32_t x) { atomicOr(p, x); });
+        if (nb[k]) or_bits(win, at, v[k], [](uint32_t* p, uint32_t x) { atomicOr(p, x); });
         at += nb[k];
     }
     __syncthreads();
@@ -466,40 +452,30 @@ struct ifhip_webp_enc_stage {
     uint32_t width = 0, height = 0, alpha = 0, max_images = 0;
     WebpShape S{};
     size_t px_pitch = 0;
-    int device = -1;                    // -1: not allocated yet (the first batch does it, behind the argument checks)
-    void *d_resid = nullptr, *d_tok = nullptr, *d_modes = nullptr, *d_seg_hist = nullptr, *d_seg_bits = nullptr, *d_seg_flat = nullptr, *d_seg_off = nullptr, *d_grp_off = nullptr,
-         *d_grp_tab = nullptr, *d_grp_hdr = nullptr, *d_grp_hbits = nullptr, *d_grp_literal = nullptr, *d_image = nullptr;
+    uint32_t *d_resid = nullptr, *d_tok = nullptr, *d_seg_hist = nullptr, *d_seg_bits = nullptr, *d_seg_flat = nullptr, *d_grp_tab = nullptr, *d_grp_hdr = nullptr,
+             *d_grp_hbits = nullptr, *d_grp_literal = nullptr, *d_image = nullptr;
+    uint8_t* d_modes = nullptr;
+    uint64_t *d_seg_off = nullptr, *d_grp_off = nullptr;
     uint32_t flat_group_bits = 0;
-    void release() {
-        for (void** p : {&d_resid, &d_tok, &d_modes, &d_seg_hist, &d_seg_bits, &d_seg_flat, &d_seg_off, &d_grp_off, &d_grp_tab, &d_grp_hdr, &d_grp_hbits,
-                         &d_grp_literal, &d_image}) { (void)DEV_FREE(*p); *p = nullptr; }
-    }
-    ~ifhip_webp_enc_stage() { release(); }
-    int allocate() {                    // all of the scratch or none of it: a failed call leaves nothing behind for the next one to leak
-        const int rc = allocate_all();
-        if (rc != IFHIP_OK && device < 0) release();
-        return rc;
-    }
-    int allocate_all() {
-        int dev = -1;
-        if (int rc = require_gfx950(&dev)) return rc;
-        if (device >= 0) return dev == device ? IFHIP_OK : fail(IFHIP_INVALID_STATE, "InvalidState: stage belongs to device %d, current device is %d", device, dev);
+    StageScratch blocks{&d_resid, &d_tok, &d_modes, &d_seg_hist, &d_seg_bits, &d_seg_flat, &d_seg_off, &d_grp_off, &d_grp_tab, &d_grp_hdr, &d_grp_hbits, &d_grp_literal, &d_image};
+    int allocate() {                    // (the first batch does it, behind the argument checks)
         const size_t n = max_images, segs = n * S.n_segs, bands = n * S.n_bands;
-        HIP_TRY(DEV_MALLOC(&d_resid, n * px_pitch * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&d_tok, n * px_pitch * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&d_modes, n * S.tiles_x * S.tiles_y));
-        HIP_TRY(DEV_MALLOC(&d_seg_hist, segs * kWebpSyms * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&d_seg_bits, segs * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&d_seg_flat, segs * 2u * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&d_seg_off, segs * sizeof(uint64_t)));
-        HIP_TRY(DEV_MALLOC(&d_grp_off, bands * sizeof(uint64_t)));
-        HIP_TRY(DEV_MALLOC(&d_grp_tab, bands * kWebpSyms * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&d_grp_hdr, bands * kWebpGroupWords * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&d_grp_hbits, bands * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&d_grp_literal, bands * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&d_image, n * 4u * sizeof(uint32_t)));
-        device = dev;
-        return IFHIP_OK;
+        return blocks.ensure([&]() -> int {
+            HIP_TRY(DEV_MALLOC(&d_resid, n * px_pitch * sizeof(uint32_t)));
+            HIP_TRY(DEV_MALLOC(&d_tok, n * px_pitch * sizeof(uint32_t)));
+            HIP_TRY(DEV_MALLOC(&d_modes, n * S.tiles_x * S.tiles_y));
+            HIP_TRY(DEV_MALLOC(&d_seg_hist, segs * kWebpSyms * sizeof(uint32_t)));
+            HIP_TRY(DEV_MALLOC(&d_seg_bits, segs * sizeof(uint32_t)));
+            HIP_TRY(DEV_MALLOC(&d_seg_flat, segs * 2u * sizeof(uint32_t)));
+            HIP_TRY(DEV_MALLOC(&d_seg_off, segs * sizeof(uint64_t)));
+            HIP_TRY(DEV_MALLOC(&d_grp_off, bands * sizeof(uint64_t)));
+            HIP_TRY(DEV_MALLOC(&d_grp_tab, bands * kWebpSyms * sizeof(uint32_t)));
+            HIP_TRY(DEV_MALLOC(&d_grp_hdr, bands * kWebpGroupWords * sizeof(uint32_t)));
+            HIP_TRY(DEV_MALLOC(&d_grp_hbits, bands * sizeof(uint32_t)));
+            HIP_TRY(DEV_MALLOC(&d_grp_literal, bands * sizeof(uint32_t)));
+            HIP_TRY(DEV_MALLOC(&d_image, n * 4u * sizeof(uint32_t)));
+            return IFHIP_OK;
+        });
     }
 };
 
@@ -536,13 +512,9 @@ int ifhip_webp_encode_batch_device(ifhip_webp_enc_stage* stage, const uint8_t* d
     if (int rc = stage->allocate()) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const WebpShape& S = stage->S;
-    const WebpArgs a{d_images, image_bytes, stride, stage->alpha ? 0u : 0xFF000000u, n_images, S, stage->px_pitch,
-                     static_cast<uint32_t*>(stage->d_resid), static_cast<uint32_t*>(stage->d_tok), static_cast<uint8_t*>(stage->d_modes),
-                     static_cast<uint32_t*>(stage->d_seg_hist), static_cast<uint32_t*>(stage->d_seg_bits), static_cast<uint32_t*>(stage->d_seg_flat),
-                     static_cast<uint64_t*>(stage->d_seg_off),
-                     static_cast<uint64_t*>(stage->d_grp_off), static_cast<uint32_t*>(stage->d_grp_tab), static_cast<uint32_t*>(stage->d_grp_hdr),
-                     static_cast<uint32_t*>(stage->d_grp_hbits), static_cast<uint32_t*>(stage->d_grp_literal), stage->flat_group_bits,
-                     static_cast<uint32_t*>(stage->d_image), d_files, file_pitch, d_lengths, d_status};
+    const WebpArgs a{d_images, image_bytes, stride, stage->alpha ? 0u : 0xFF000000u, n_images, S, stage->px_pitch, stage->d_resid, stage->d_tok, stage->d_modes,
+                     stage->d_seg_hist, stage->d_seg_bits, stage->d_seg_flat, stage->d_seg_off, stage->d_grp_off, stage->d_grp_tab, stage->d_grp_hdr,
+                     stage->d_grp_hbits, stage->d_grp_literal, stage->flat_group_bits, stage->d_image, d_files, file_pitch, d_lengths, d_status};
     // everything of the payload is ORed into place: the files start out as zeros (which also is the pad byte)
     HIP_TRY(hipMemsetAsync(d_files, 0, static_cast<size_t>(n_images) * file_pitch, st));
     HIP_TRY(hipMemsetAsync(stage->d_image, 0, static_cast<size_t>(n_images) * 4u * sizeof(uint32_t), st));

@@ -8,11 +8,11 @@
 // coder's own: subtract green, a predictor per 16 x 16 tile, LZ77 over the residual pixels at the two distances image
 // data favours (one pixel back, one row up), a group of five prefix codes per band of 64 rows, no colour cache.  Every
 // rule of the format with a bit in it lives here.  The code construction (lengths of at most 15 bits, canonical codes,
-// the run-length coded header) is the deflate back end's (png_encode_core.hpp): VP8L took both from deflate.
+// the run-length coded header) is prefix_code_core.hpp's, shared with the deflate back end: VP8L took both from deflate.
 #pragma once
 #include <cstdint>
 
-#include "png_encode_core.hpp"
+#include "prefix_code_core.hpp"
 
 namespace ifhip {
 
@@ -105,8 +105,9 @@ IFHIP_HD uint32_t webp_sub_pixels(uint32_t a, uint32_t b) {             // per c
     const uint32_t ag = 0x00FF00FFu + (a & 0xFF00FF00u) - (b & 0xFF00FF00u), rb = 0xFF00FF00u + (a & 0x00FF00FFu) - (b & 0x00FF00FFu);
     return (ag & 0xFF00FF00u) | (rb & 0x00FF00FFu);
 }
+IFHIP_HD uint32_t webp_byte_cost(uint32_t v) { return v < 128u ? v : 256u - v; }             // |the residual byte as a signed one|
 IFHIP_HD uint32_t webp_residual_cost(uint32_t r) {
-    return png_filter_cost(r & 255u) + png_filter_cost((r >> 8) & 255u) + png_filter_cost((r >> 16) & 255u) + png_filter_cost(r >> 24);
+    return webp_byte_cost(r & 255u) + webp_byte_cost((r >> 8) & 255u) + webp_byte_cost((r >> 16) & 255u) + webp_byte_cost(r >> 24);
 }
 // The pixel at (x, y) of a frame, as the predictor sees it: alpha 255 where it is not meaningful, green subtracted.
 IFHIP_HD uint32_t webp_source(const uint8_t* frame, uint32_t stride, uint32_t x, uint32_t y, uint32_t alpha_or) {
@@ -142,7 +143,7 @@ IFHIP_HD uint32_t webp_choose_mode(const uint32_t sums[14]) {           // the s
 IFHIP_HD void webp_prefix(uint32_t v, uint32_t* sym, uint32_t* ebits, uint32_t* eval) {
     const uint32_t p = v - 1u;
     if (p < 4u) { *sym = p; *ebits = 0; *eval = 0; return; }
-    const uint32_t hb = png_log2(p), e = hb - 1u;
+    const uint32_t hb = floor_log2(p), e = hb - 1u;
     *sym = 2u * hb + ((p >> e) & 1u); *ebits = e; *eval = p & ((1u << e) - 1u);
 }
 IFHIP_HD uint32_t webp_prefix_extra_bits(uint32_t sym) { return sym < 4u ? 0u : (sym - 2u) >> 1; }
@@ -187,22 +188,12 @@ IFHIP_HD uint32_t webp_token_bits(const uint32_t* tab, uint32_t tok, uint32_t ar
     *value = v;
     return n;
 }
-// up to 64 bits of v ORed into a zeroed dword stream at bit position pos; or_word: how a word shared between writers is ORed
-template <typename Or>
-IFHIP_HD void webp_or_bits(uint32_t* words, uint64_t pos, uint64_t v, Or or_word) {
-    uint32_t* w = words + (pos >> 5);
-    const uint32_t s = static_cast<uint32_t>(pos) & 31u;
-    const uint32_t w0 = static_cast<uint32_t>(v << s);
-    const uint64_t rest = s ? v >> (32u - s) : v >> 32;
-    if (w0) or_word(w, w0);
-    if (static_cast<uint32_t>(rest)) or_word(w + 1, static_cast<uint32_t>(rest));
-    if (rest >> 32) or_word(w + 2, static_cast<uint32_t>(rest >> 32));
-}
 
 // ---- prefix codes -----------------------------------------------------------------------------------------------------------
 struct WebpCodeWork {
-    PngCodeWork P;                  // the deflate back end's workspace: sorted, wt, parent, nc, rle, clcnt, cltab, len
-    uint8_t keep[288];              // the Huffman lengths while the fixed code is sized
+    CodeWork P;                     // the prefix-code workspace
+    uint8_t len[kCodeMaxSyms];      // the lengths of the code under construction
+    uint8_t keep[kCodeMaxSyms];     // the Huffman lengths while the fixed code is sized
 };
 IFHIP_HD uint32_t webp_cl_order(uint32_t i) {           // 17 18 0 1 2 3 4 5 16 6 7 ... 15
     return i == 0u ? 17u : i == 1u ? 18u : i < 8u ? i - 2u : i == 8u ? 16u : i - 3u;
@@ -210,56 +201,22 @@ IFHIP_HD uint32_t webp_cl_order(uint32_t i) {           // 17 18 0 1 2 3 4 5 16 
 // The flat code a channel falls back to when its Huffman code with its header is larger: 256 symbols of 8 bits (green:
 // only in a group without matches; a group with matches falls back as a whole, see webp_flat_group_bits).
 IFHIP_HD uint32_t webp_fixed_length(uint32_t s) { return s < 256u ? 8u : 0u; }
-// The header of the code whose lengths are in W.P.len[0, n): run-length tokens (16: the previous non-zero length 3-6
-// times, used only behind that length itself; 17: 3-10 zeros; 18: 11-138 zeros) over ALL n lengths, and the code of the
-// code lengths, complete, at most 7 bits.  Returns the header's bits.
+// The header of the normal code whose lengths are in W.len[0, n), over ALL n lengths (code_plan_header).  Returns its bits:
+// the normal-code bit, the 4-bit count and the "all symbols follow" bit are VP8L's own.
 IFHIP_HD uint32_t webp_plan_header(WebpCodeWork& W, uint32_t n) {
-    PngCodeWork& P = W.P;
-    P.nrle = 0;
-    for (uint32_t i = 0; i < 20u; ++i) P.clcnt[i] = 0;
-    for (uint32_t i = 0; i < n;) {
-        const uint32_t v = P.len[i];
-        uint32_t run = 1;
-        while (i + run < n && P.len[i + run] == v) ++run;
-        i += run;
-        if (v == 0u) {
-            while (run >= 11u) { const uint32_t t = run < 138u ? run : 138u; png_rle_emit(P, 18u, t - 11u); run -= t; }
-            if (run >= 3u) { png_rle_emit(P, 17u, run - 3u); run = 0; }
-        } else {
-            png_rle_emit(P, v, 0); --run;
-            while (run >= 3u) { const uint32_t t = run < 6u ? run : 6u; png_rle_emit(P, 16u, t - 3u); run -= t; }
-        }
-        while (run > 0u) { png_rle_emit(P, v, 0); --run; }
-    }
-    png_rank_sort_lane(P.clcnt, kPngCL, 0, 1, P.sorted);
-    png_build_lengths(P, P.clcnt, kPngCL, 7, P.len + kPngLenCL, 0, true);
-    uint32_t ncl = kPngCL;
-    while (ncl > 4u && P.len[kPngLenCL + webp_cl_order(ncl - 1u)] == 0) --ncl;
-    P.hclen = ncl;
-    uint32_t bits = 1u + 4u + 3u * ncl + 1u;
-    for (uint32_t i = 0; i < P.nrle; ++i) {
-        const uint32_t s = P.rle[i] & 255u;
-        bits += P.len[kPngLenCL + s] + (s == 16u ? 2u : s == 17u ? 3u : s == 18u ? 7u : 0u);
-    }
-    return bits;
+    return 1u + 4u + 1u + code_plan_header(W.P, n, [&](uint32_t i) -> uint32_t { return W.len[i]; }, webp_cl_order);
 }
 IFHIP_HD void webp_write_header(WebpCodeWork& W, uint32_t* hdr, uint32_t* pos) {
-    PngCodeWork& P = W.P;
-    png_assign_codes(P, P.len + kPngLenCL, kPngCL, P.cltab);
-    png_put(hdr, pos, 0u, 1);                                   // a normal code
-    png_put(hdr, pos, P.hclen - 4u, 4);
-    for (uint32_t i = 0; i < P.hclen; ++i) png_put(hdr, pos, P.len[kPngLenCL + webp_cl_order(i)], 3);
-    png_put(hdr, pos, 0u, 1);                                   // all symbols follow
-    for (uint32_t i = 0; i < P.nrle; ++i) {
-        const uint32_t s = P.rle[i] & 255u, e = P.rle[i] >> 8, t = P.cltab[s];
-        png_put(hdr, pos, t & 0xFFFFu, t >> 16);
-        if (s >= 16u) png_put(hdr, pos, e, s == 16u ? 2u : s == 17u ? 3u : 7u);
-    }
+    put_bits(hdr, pos, 0u, 1);                                  // a normal code
+    put_bits(hdr, pos, W.P.hclen - 4u, 4);
+    code_write_cl_lengths(W.P, hdr, pos, webp_cl_order);
+    put_bits(hdr, pos, 0u, 1);                                  // all symbols follow
+    code_write_rle(W.P, hdr, pos);
 }
 IFHIP_HD void webp_put_simple_symbol(uint32_t* hdr, uint32_t* pos, uint32_t s) {
-    if (s < 2u) { png_put(hdr, pos, 0u, 1); png_put(hdr, pos, s, 1); } else { png_put(hdr, pos, 1u, 1); png_put(hdr, pos, s, 8); }
+    if (s < 2u) { put_bits(hdr, pos, 0u, 1); put_bits(hdr, pos, s, 1); } else { put_bits(hdr, pos, 1u, 1); put_bits(hdr, pos, s, 8); }
 }
-// One alphabet's code from its counts, by one lane (W.P.sorted filled by png_rank_sort_lane over cnt): the table (bit-
+// One alphabet's code from its counts, by one lane (W.P.sorted filled by code_rank_sort_lane over cnt): the table (bit-
 // reversed code | length << 16 per symbol) and the header's bits appended to the zeroed dword stream hdr at *pos.  VP8L
 // rejects incomplete codes: no or one used symbol below 256 is the simple one-symbol code (no bits per use), two such the
 // simple two-symbol code; everything else is a normal code, Huffman lengths or, where that is smaller with its header (or
@@ -267,7 +224,6 @@ IFHIP_HD void webp_put_simple_symbol(uint32_t* hdr, uint32_t* pos, uint32_t s) {
 // are in use).  *fixed: the flat code was taken.  Returns the bits of the counted symbols under the code, without extra bits.
 IFHIP_HD uint64_t webp_build_code(WebpCodeWork& W, const uint32_t* cnt, uint32_t alphabet, uint32_t* tab, uint32_t* hdr, uint32_t* pos, uint32_t* fixed,
                                   bool force_flat = false) {
-    PngCodeWork& P = W.P;
     const uint32_t n = webp_alphabet_size(alphabet);
     uint32_t m = 0, s0 = 0, s1 = 0;
     bool with_lengths = false;
@@ -280,44 +236,44 @@ IFHIP_HD uint64_t webp_build_code(WebpCodeWork& W, const uint32_t* cnt, uint32_t
     }
     *fixed = 0;
     if (force_flat && alphabet < 4u) {
-        for (uint32_t s = 0; s < n; ++s) P.len[s] = static_cast<uint8_t>(webp_fixed_length(s));
+        for (uint32_t s = 0; s < n; ++s) W.len[s] = static_cast<uint8_t>(webp_fixed_length(s));
         (void)webp_plan_header(W, n);
         webp_write_header(W, hdr, pos);
-        png_assign_codes(P, P.len, n, tab);
+        code_assign_codes(W.P, W.len, n, tab);
         *fixed = 1;
         uint64_t bits = 0;
-        for (uint32_t s = 0; s < n; ++s) bits += static_cast<uint64_t>(cnt[s]) * P.len[s];
+        for (uint32_t s = 0; s < n; ++s) bits += static_cast<uint64_t>(cnt[s]) * W.len[s];
         return bits;
     }
     if (m < 2u && s0 < 256u) {
-        png_put(hdr, pos, 1u, 1); png_put(hdr, pos, 0u, 1);
+        put_bits(hdr, pos, 1u, 1); put_bits(hdr, pos, 0u, 1);
         webp_put_simple_symbol(hdr, pos, s0);
         return 0;
     }
     if (m == 2u && s1 < 256u) {
-        png_put(hdr, pos, 1u, 1); png_put(hdr, pos, 1u, 1);
+        put_bits(hdr, pos, 1u, 1); put_bits(hdr, pos, 1u, 1);
         webp_put_simple_symbol(hdr, pos, s0);
-        png_put(hdr, pos, s1, 8);
+        put_bits(hdr, pos, s1, 8);
         tab[s0] = 0u | (1u << 16); tab[s1] = 1u | (1u << 16);
         return static_cast<uint64_t>(cnt[s0]) + cnt[s1];
     }
-    png_build_lengths(P, cnt, n, 15, P.len, s0, true);
+    code_build_lengths(W.P, cnt, n, 15, W.len, s0, true);
     uint64_t huff = webp_plan_header(W, n);
-    for (uint32_t s = 0; s < n; ++s) huff += static_cast<uint64_t>(cnt[s]) * P.len[s];
+    for (uint32_t s = 0; s < n; ++s) huff += static_cast<uint64_t>(cnt[s]) * W.len[s];
     if (alphabet < 4u && !with_lengths) {
-        for (uint32_t s = 0; s < n; ++s) { W.keep[s] = P.len[s]; P.len[s] = static_cast<uint8_t>(webp_fixed_length(s)); }
+        for (uint32_t s = 0; s < n; ++s) { W.keep[s] = W.len[s]; W.len[s] = static_cast<uint8_t>(webp_fixed_length(s)); }
         uint64_t fix = webp_plan_header(W, n);
-        for (uint32_t s = 0; s < n; ++s) fix += static_cast<uint64_t>(cnt[s]) * P.len[s];
+        for (uint32_t s = 0; s < n; ++s) fix += static_cast<uint64_t>(cnt[s]) * W.len[s];
         if (fix < huff) *fixed = 1;
         else {
-            for (uint32_t s = 0; s < n; ++s) P.len[s] = W.keep[s];
+            for (uint32_t s = 0; s < n; ++s) W.len[s] = W.keep[s];
             (void)webp_plan_header(W, n);
         }
     }
     webp_write_header(W, hdr, pos);
-    png_assign_codes(P, P.len, n, tab);
+    code_assign_codes(W.P, W.len, n, tab);
     uint64_t bits = 0;
-    for (uint32_t s = 0; s < n; ++s) bits += static_cast<uint64_t>(cnt[s]) * P.len[s];
+    for (uint32_t s = 0; s < n; ++s) bits += static_cast<uint64_t>(cnt[s]) * W.len[s];
     return bits;
 }
 // The headers of a group that is coded as literals under four flat codes (and the one-symbol distance code, 4 bits):
@@ -326,7 +282,7 @@ IFHIP_HD uint32_t webp_flat_group_bits(WebpCodeWork& W) {
     uint32_t bits = 4u;
     for (uint32_t a = 0; a < 4u; ++a) {
         const uint32_t n = webp_alphabet_size(a);
-        for (uint32_t s = 0; s < n; ++s) W.P.len[s] = static_cast<uint8_t>(webp_fixed_length(s));
+        for (uint32_t s = 0; s < n; ++s) W.len[s] = static_cast<uint8_t>(webp_fixed_length(s));
         bits += webp_plan_header(W, n);
     }
     return bits;
@@ -338,15 +294,15 @@ IFHIP_HD uint32_t webp_symbol_cost(const uint32_t* tab, uint32_t s) { return (ta
 // signature, size, alpha_is_used, version 0; subtract green; the predictor transform and its tile bits: 49 bits in front
 // of the mode sub-image
 IFHIP_HD void webp_put_front(uint32_t* hdr, uint32_t* pos, uint32_t w, uint32_t h, uint32_t alpha) {
-    png_put(hdr, pos, 0x2Fu, 8); png_put(hdr, pos, w - 1u, 14); png_put(hdr, pos, h - 1u, 14); png_put(hdr, pos, alpha, 1); png_put(hdr, pos, 0u, 3);
-    png_put(hdr, pos, 1u, 1); png_put(hdr, pos, 2u, 2);
-    png_put(hdr, pos, 1u, 1); png_put(hdr, pos, 0u, 2); png_put(hdr, pos, kWebpTileBits - 2u, 3);
-    png_put(hdr, pos, 0u, 1);                                   // the mode sub-image: no colour cache
+    put_bits(hdr, pos, 0x2Fu, 8); put_bits(hdr, pos, w - 1u, 14); put_bits(hdr, pos, h - 1u, 14); put_bits(hdr, pos, alpha, 1); put_bits(hdr, pos, 0u, 3);
+    put_bits(hdr, pos, 1u, 1); put_bits(hdr, pos, 2u, 2);
+    put_bits(hdr, pos, 1u, 1); put_bits(hdr, pos, 0u, 2); put_bits(hdr, pos, kWebpTileBits - 2u, 3);
+    put_bits(hdr, pos, 0u, 1);                                   // the mode sub-image: no colour cache
 }
 // no further transform; the main image: no colour cache, meta prefix codes with their tile bits; the entropy sub-image: no cache
 IFHIP_HD void webp_put_middle(uint32_t* hdr, uint32_t* pos) {
-    png_put(hdr, pos, 0u, 1); png_put(hdr, pos, 0u, 1); png_put(hdr, pos, 1u, 1); png_put(hdr, pos, kWebpBandBits - 2u, 3);
-    png_put(hdr, pos, 0u, 1);
+    put_bits(hdr, pos, 0u, 1); put_bits(hdr, pos, 0u, 1); put_bits(hdr, pos, 1u, 1); put_bits(hdr, pos, kWebpBandBits - 2u, 3);
+    put_bits(hdr, pos, 0u, 1);
 }
 IFHIP_HD void webp_le32(uint8_t* p, uint32_t v) { p[0] = static_cast<uint8_t>(v); p[1] = static_cast<uint8_t>(v >> 8); p[2] = static_cast<uint8_t>(v >> 16); p[3] = static_cast<uint8_t>(v >> 24); }
 // the 20 bytes in front of a payload of payload_bytes; returns the file's size (the payload is padded to an even size)

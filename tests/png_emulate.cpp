@@ -110,10 +110,10 @@ void code_chunk(const uint8_t* stream, uint32_t total, uint32_t c, uint32_t n_ch
         if (covered != end) stats[0]++;                              // the parse must tile the chunk exactly
     }
     W.cnt[256] = 1;
-    for (uint32_t lane = 0; lane < kLanes; ++lane) png_rank_sort_lane(W.cnt, kPngLL, lane, kLanes, W.sorted);
-    png_build_lengths(W, W.cnt, kPngLL, 15, W.len, 256, true);
-    png_rank_sort_lane(W.cnt + kPngLL, kPngD, 0, 1, W.sorted);
-    png_build_lengths(W, W.cnt + kPngLL, kPngD, 15, W.len + kPngLL, 0, false);
+    for (uint32_t lane = 0; lane < kLanes; ++lane) code_rank_sort_lane(W.cnt, kPngLL, lane, kLanes, W.sorted);
+    code_build_lengths(W, W.cnt, kPngLL, 15, W.len, 256, true);
+    code_rank_sort_lane(W.cnt + kPngLL, kPngD, 0, 1, W.sorted);
+    code_build_lengths(W, W.cnt + kPngLL, kPngD, 15, W.len + kPngLL, 0, false);
     const bool last = c + 1u == n_chunks;
     const uint32_t nbytes = png_plan_block(W, n, last, stored_only, &out->type);
     out->bytes.assign(nbytes, 0);
@@ -140,7 +140,7 @@ void code_chunk(const uint8_t* stream, uint32_t total, uint32_t c, uint32_t n_ch
             uint32_t ex = 0;
             std::vector<uint32_t> at(kEmitThreads);
             for (uint32_t t = 0; t < kEmitThreads; ++t) { at[t] = pos + ex; ex += bits[t]; }
-            for (uint32_t t = kEmitThreads; t-- > 0u;) if (bits[t]) png_or_bits(words.data(), at[t], val[t], or_word);
+            for (uint32_t t = kEmitThreads; t-- > 0u;) if (bits[t]) or_bits(words.data(), at[t], val[t], or_word);
             pos += ex;
         }
         const uint32_t coded = last ? (pos + 7u) >> 3 : ((pos + 3u + 7u) >> 3) + 4u;

@@ -21,7 +21,7 @@ void build_codes(const uint32_t* cnt, uint32_t* tab, uint32_t* hdr, uint32_t* po
     static WebpCodeWork W;
     for (uint32_t a = 0; a < 5u; ++a) {
         const uint32_t off = webp_alphabet_offset(a), n = webp_alphabet_size(a);
-        for (uint32_t lane = 0; lane < kLanes; ++lane) png_rank_sort_lane(cnt + off, n, lane, kLanes, W.P.sorted);
+        for (uint32_t lane = 0; lane < kLanes; ++lane) code_rank_sort_lane(cnt + off, n, lane, kLanes, W.P.sorted);
         uint32_t fixed = 0;
         webp_build_code(W, cnt + off, a, tab + off, hdr, pos, &fixed, force_flat);
         stats[5] += fixed;
@@ -190,13 +190,13 @@ int webp_emu_encode(const uint8_t* bgra, uint32_t w, uint32_t h, uint32_t stride
     std::vector<uint32_t> words(static_cast<size_t>(payload / 4u) + 4u, 0u);
     auto or_word = [](uint32_t* p, uint32_t v) { *p |= v; };
     auto or_stream = [&](const uint32_t* src, uint32_t bits, uint64_t where) {
-        for (uint32_t i = 0; i < (bits + 31u) / 32u; ++i) webp_or_bits(words.data(), where + 32ull * i, src[i], or_word);
+        for (uint32_t i = 0; i < (bits + 31u) / 32u; ++i) or_bits(words.data(), where + 32ull * i, src[i], or_word);
     };
     auto emit_literals = [&](const uint32_t* tab, uint32_t count, uint64_t where, auto pixel) -> uint64_t {
         for (uint32_t i = 0; i < count; ++i) {
             uint64_t v;
             const uint32_t nb = webp_token_bits(tab, 1u, pixel(i), &v);
-            if (nb) webp_or_bits(words.data(), where, v, or_word);
+            if (nb) or_bits(words.data(), where, v, or_word);
             where += nb;
         }
         return where;
@@ -217,7 +217,7 @@ int webp_emu_encode(const uint8_t* bgra, uint32_t w, uint32_t h, uint32_t stride
             if (!literals && !tok[start + i]) continue;
             uint64_t v;
             const uint32_t nb = webp_token_bits(tab, literals ? 1u : tok[start + i], resid[start + i], &v);
-            if (nb) webp_or_bits(words.data(), where, v, or_word);
+            if (nb) or_bits(words.data(), where, v, or_word);
             where += nb;
         }
         if (where != seg_off[seg] + seg_bits[seg]) stats[0]++;       // the layout's exact size is what the writer reaches
