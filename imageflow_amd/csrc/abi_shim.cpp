@@ -42,6 +42,7 @@
 #include "../../include/imageflow_hip.h"
 #include "common.hpp"           // the library's per-job memory cache and thread stream (devmem.cpp)
 #include "png_read.hpp"         // the PNG chunk walk and the device decode of a walked file (png_read.cpp, png_decode.hip)
+#include "webp_read.hpp"        // the RIFF walk, the prepare and the device decode of a lossless WebP (webp_read.cpp, webp_decode.hip)
 #include "layout.hpp"           // imageflow_riapi's constraint layout (constrain / watermark)
 
 namespace {
@@ -502,7 +503,19 @@ struct Io {
     uint32_t told_w = 0, told_h = 0;
     bool told_spatial = false, told_gamma = false;
     bool told_discard_profile = false;           // DecoderCommand::DiscardColorProfile (mozjpeg_decoder.rs:88-91)
+    // DecoderCommand::WebPDecoderHints (codecs/webp.rs:181-188): the size libwebp's rescaler would decode to; acted on by a WebP input only
+    bool told_webp = false;
+    uint32_t told_webp_w = 0, told_webp_h = 0;
 };
+// webp_decoder_hints is accepted whatever it holds, as it was before a WebP input could act on it: only a hint that
+// carries both sizes is kept with the input
+void tell_webp_hint(Io& in, const JVal& j) {
+    const JVal* w = j.get("width");
+    const JVal* h = j.get("height");
+    if (!w || !h || w->t != JVal::Num || h->t != JVal::Num || !(w->n >= 0 && w->n <= 4294967295.0) || !(h->n >= 0 && h->n <= 4294967295.0)) return;
+    in.told_webp = true;
+    in.told_webp_w = static_cast<uint32_t>(w->n); in.told_webp_h = static_cast<uint32_t>(h->n);
+}
 struct Response {
     int64_t status;
     std::string json;
@@ -902,6 +915,15 @@ struct Job {
         static const uint8_t sig[8] = {0x89, 'P', 'N', 'G', 13, 10, 26, 10};
         return in.in_len >= 8 && std::memcmp(in.in, sig, 8) == 0;
     }
+    static bool is_webp(const Io& in) {                                  // codecs/mod.rs:130-131: RIFF....WEBP, 12 bytes
+        return in.in_len >= 12 && std::memcmp(in.in, "RIFF", 4) == 0 && std::memcmp(in.in + 8, "WEBP", 4) == 0;
+    }
+    // the walk of a WebP input for a decode: a lossy file is ImageTypeNotSupported (known difference: the reference decodes it)
+    static void walk_webp(const Io& in, ifhip::WebpParsed* P) {
+        const int rc = ifhip::parse_webp_for_decode(in.in, in.in_len, P);
+        if (rc == IFHIP_METHOD_NOT_IMPLEMENTED) raise(kImageTypeNotSupported, "%s", ifhip_last_error_message());
+        check(rc);
+    }
     // MzDec::get_exif_rotation_flag (mozjpeg_decoder.rs:290-292): the EXIF orientation tag of a JPEG input, -1 = none
     // (a PNG has none: LibPngDecoder::get_exif_rotation_flag is None, libpng_decoder.rs:54-56)
     static int exif_flag(const Io& in) {
@@ -929,6 +951,12 @@ struct Job {
             ifhip_png_file_info pi;
             check(ifhip_png_info(in.in, in.in_len, &pi));
             *w = pi.width; *h = pi.height;
+            return;
+        }
+        if (is_webp(in)) {                                               // WebPDecoder: no EXIF orientation (webp.rs:176-179)
+            ifhip::WebpParsed P;
+            walk_webp(in, &P);
+            *w = P.w; *h = P.h;
             return;
         }
         int nc = 0;
@@ -1001,6 +1029,39 @@ struct Job {
         return f;
     }
 
+    // WebPDecoder::read_frame (codecs/webp.rs:162-248 -> WebPDecode, MODE_BGRA) on the device for a lossless file: the host walks
+    // the container and prepares the stream, the token loop and the inverse transforms run in csrc/webp_decode.hip.  The JPEG
+    // downscale hints are accepted and ignored; a told WebP hint that differs from the file's size would need libwebp's
+    // decode-time rescaler (webp.rs:181-188), which is not built.
+    FramePtr decode_webp(int32_t io_id, Io& in) {
+        ifhip::WebpParsed P;
+        walk_webp(in, &P);
+        check_size(sec.max_decode_size, "max_decode_size", P.w, P.h);                 // on the header, before anything is staged
+        if (!in.told_discard_profile && P.color_kind == 2)
+            raise(kActionNotSupported, "ActionNotSupported: io_id %d carries an embedded ICC profile that is not sRGB; this build has no colour "
+                  "management.  Tell the decoder \"discard_color_profile\" to decode the samples as they are, or keep the file on the reference.", io_id);
+        if (in.told_webp && (in.told_webp_w != P.w || in.told_webp_h != P.h))
+            raise(kActionNotSupported, "ActionNotSupported: webp_decoder_hints %ux%u for io_id %d (%ux%u): libwebp's decode-time rescaler is not built "
+                  "(the reference shrinks during the decode, codecs/webp.rs:181-188); decode at full size and resample", in.told_webp_w, in.told_webp_h, io_id, P.w, P.h);
+        FramePtr f = new_frame(P.w, P.h, P.has_alpha, 0, true);                       // (max_frame_size inside)
+        ifhip::WebpJob J;
+        ifhip::webp_prepare_job(P, &J);                                               // on this job's thread, like ifhip_jpeg_entropy_prepare
+        if (J.status) raise(kImageMalformed, "ImageMalformed: libwebp decoding error %s (io_id %d, status %u)", ifhip::webp_status_text(J.status), io_id, J.status);
+        uint32_t* d_status = nullptr;
+        hip_check(job_malloc(reinterpret_cast<void**>(&d_status), 16), "hipMalloc(status)");
+        struct Guard { void* p; ~Guard() { job_free(p); } } guard{d_status};
+        const ifhip::WebpJob* job = &J;
+        const size_t bytes = f->bytes();
+        poll_cancel();
+        check(ifhip::webp_decode_prepared_device(&job, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream));
+        uint32_t status = 0;
+        hip_check(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, t_job_stream), "download(status)");
+        hip_check(static_cast<hipError_t>(ifhip::wait_stream(t_job_stream)), "decode(webp)");
+        if (status) raise(kImageMalformed, "ImageMalformed: libwebp decoding error %s (io_id %d, status %u)", ifhip::webp_status_text(status), io_id, status);
+        decodes.push_back({io_id, P.w, P.h, "image/webp", "webp"});
+        return f;
+    }
+
     // decode: MozJpegDecoder::read_frame (codecs/mozjpeg_decoder.rs:295-420) on the device, or the raw extension
     FramePtr decode(int32_t io_id, uint32_t hint_w, uint32_t hint_h, bool luma_spatial, bool luma_srgb) {
         Timed t(this, "primitive_decoder");
@@ -1019,6 +1080,7 @@ struct Job {
             return f;
         }
         if (is_png(in)) return decode_png(io_id, in);
+        if (is_webp(in)) return decode_webp(io_id, in);
         if (in.in_len < 3 || in.in[0] != 0xFF || in.in[1] != 0xD8)                        // codecs/mod.rs:398-415 sniffing
             raise(kImageTypeNotSupported, "ImageTypeNotSupported: io_id %d is neither a JPEG nor the raw BGRA extension", io_id);
         {   // limits before anything is staged (mozjpeg_decoder.rs:196-214 checks max_decode_size on the header)
@@ -1461,6 +1523,10 @@ struct Job {
                 const double downscale = std::min(static_cast<double>(src_w) / ow, static_cast<double>(src_h) / ow);   // sic: `to.w` twice (:161-162)
                 const double preshrink = 2.1 / downscale;
                 if (preshrink < 1.0) { hint_w = static_cast<uint32_t>(std::floor(src_w * preshrink)); hint_h = static_cast<uint32_t>(std::floor(src_h * preshrink)); }
+            }
+            if (srgb && hint_w) {                                        // the WebP hint goes out only with down.colorspace=srgb (ir4/mod.rs:187-199)
+                Io& src = input(static_cast<int32_t>(dec->n));
+                if (is_webp(src)) { src.told_webp = true; src.told_webp_w = hint_w; src.told_webp_h = hint_h; }
             }
             in = decode_oriented(static_cast<int32_t>(dec->n), hint_w, hint_h, !srgb, !srgb);
             if (!src_w) { src_w = in->w; src_h = in->h; }
@@ -1914,6 +1980,8 @@ struct Job {
                     for (const JVal& cmd : cmds->a) {
                         if (cmd.t == JVal::Str && cmd.s == "discard_color_profile") {
                             input(static_cast<int32_t>(want_int(p, "io_id", "decode"))).told_discard_profile = true;
+                        } else if (const JVal* j = cmd.get("webp_decoder_hints")) {          // s::WebPDecoderHints {width, height}
+                            tell_webp_hint(input(static_cast<int32_t>(want_int(p, "io_id", "decode"))), *j);
                         } else if (const JVal* j = cmd.get("jpeg_downscale_hints")) {        // s::JpegIDCTDownscaleHints
                             hw = want_u32(*j, "width", "jpeg_downscale_hints"); hh = want_u32(*j, "height", "jpeg_downscale_hints");
                             if (const JVal* b = j->get("scale_luma_spatially")) spatial = b->t == JVal::Bool && b->b;
@@ -2509,8 +2577,9 @@ const struct imageflow_json_response* imageflow_context_send_json(struct imagefl
                 in.told_gamma = b && b->t == JVal::Bool && b->b;
             } else if (cmd->t == JVal::Str && cmd->s == "discard_color_profile") {
                 in.told_discard_profile = true;                                      // the samples as they are: what this library does anyway
-            } else if (!(cmd->t == JVal::Str && cmd->s == "ignore_color_profile_errors") &&
-                       !(cmd->t == JVal::Obj && cmd->get("webp_decoder_hints"))) {   // profile errors (there is no CMS to fail) / WebP: nothing to act on
+            } else if (cmd->t == JVal::Obj && cmd->get("webp_decoder_hints")) {      // s::DecoderCommand::WebPDecoderHints: kept with the input
+                tell_webp_hint(in, *cmd->get("webp_decoder_hints"));
+            } else if (!(cmd->t == JVal::Str && cmd->s == "ignore_color_profile_errors")) {   // profile errors: there is no CMS to fail
                 raise(kInvalidJson, "InvalidJson: unknown decoder command");
             }
             return respond(c, 200, "{\n  \"code\": 200,\n  \"success\": true,\n  \"message\": \"OK\",\n  \"data\": {}\n}");                 // TellDecoderV1Response {} (v1.rs:177)
@@ -2523,6 +2592,13 @@ const struct imageflow_json_response* imageflow_context_send_json(struct imagefl
                 return respond(c, 200, "{\n  \"code\": 200,\n  \"success\": true,\n  \"message\": \"OK\",\n  \"data\": {\n    \"image_info\": {\"preferred_mime_type\": \"image/png\", "
                                        "\"preferred_extension\": \"png\", \"image_width\": " + std::to_string(pi.width) + ", \"image_height\": " + std::to_string(pi.height) +
                                        ", \"frame_decodes_into\": \"" + (pi.alpha_used ? "bgra_32" : "bgr_32") + "\"}\n  }\n}");
+            }
+            if (Job::is_webp(in)) {                                  // WebPDecoder: the features of the file, no EXIF orientation (webp.rs:130-179)
+                ifhip::WebpParsed P;
+                Job::walk_webp(in, &P);
+                return respond(c, 200, "{\n  \"code\": 200,\n  \"success\": true,\n  \"message\": \"OK\",\n  \"data\": {\n    \"image_info\": {\"preferred_mime_type\": \"image/webp\", "
+                                       "\"preferred_extension\": \"webp\", \"image_width\": " + std::to_string(P.w) + ", \"image_height\": " + std::to_string(P.h) +
+                                       ", \"frame_decodes_into\": \"" + (P.has_alpha ? "bgra_32" : "bgr_32") + "\"}\n  }\n}");
             }
             uint32_t w = 0, h = 0, bw[3], bh[3], ri = 0;
             int nc = 0;

@@ -585,6 +585,52 @@ IFHIP_API int ifhip_png_decode_batch_device(const uint8_t* const* files, const s
 IFHIP_API int ifhip_png_decode(const uint8_t* png, size_t len, uint8_t* bgra, uint32_t stride, size_t capacity,
                                uint32_t* status);
 
+/* Device WebP decoder, lossless files: what WebPDecoder (imageflow_core/src/codecs/webp.rs:20-248) gets from WebPGetFeatures
+ * and WebPDecode(MODE_BGRA) for a VP8L file -- BGRA bytes, the alpha bytes as coded whatever has_alpha says.  The host walks
+ * the RIFF container and prepares the stream (header, transforms with their sub-images, entropy image, every group's codes:
+ * csrc/webp_read.cpp); the main image's token loop and the inverse transforms run on the device (csrc/webp_decode.hip).
+ * Not built: lossy VP8 (+ ALPH), animation, libwebp's decode-time rescaler.
+ *
+ * has_alpha (-> frame_decodes_into bgra_32 / bgr_32, webp.rs:144-148,204) is what WebPGetFeatures reports: for a lossless
+ * file the VP8L header's bit, whatever a VP8X chunk's ALPHA flag says.  color_kind, in the convention of
+ * ifhip_jpeg_icc_profile_kind: 0 no ICCP chunk (or the VP8X ICC flag clear), 1 a profile that describes sRGB, 2 any other --
+ * this library has no colour management, so callers must refuse or be told discard_color_profile.
+ *
+ * Status word of a file (d_status[i]): 0, or why its stream is no image. */
+#define IFHIP_WEBP_DEC_TRUNCATED 1       /* a bit was used that the stream does not have                       */
+#define IFHIP_WEBP_DEC_CODE_LENGTHS 2    /* over-subscribed or incomplete code, no symbol, a repeat or max_symbol beyond the alphabet */
+#define IFHIP_WEBP_DEC_BAD_CODE 3        /* bits that are no code                                               */
+#define IFHIP_WEBP_DEC_DISTANCE 4        /* a copy from before the image's first pixel                          */
+#define IFHIP_WEBP_DEC_COPY_END 5        /* a copy past the image's last pixel                                  */
+#define IFHIP_WEBP_DEC_CACHE_SYMBOL 6    /* a colour cache symbol beyond the cache (no file reaches it: a guard) */
+#define IFHIP_WEBP_DEC_TRANSFORM 7       /* a transform twice, colour cache bits outside 1..11                  */
+#define IFHIP_WEBP_DEC_TOO_LITTLE 8      /* the payload ends inside the VP8L header (the container walk refuses it first: CONTAINER) */
+#define IFHIP_WEBP_DEC_CONTAINER 9       /* batch only: the RIFF container did not parse, or the file is lossy or animated */
+typedef struct ifhip_webp_file_info {
+    uint32_t width, height;
+    uint32_t has_alpha, lossless, animated;
+    int32_t color_kind;
+} ifhip_webp_file_info;
+/* Container facts (WebPGetFeatures).  A lossy file (lossless = 0) and an animation (animated = 1, the canvas size) are
+ * answered here and refused by the decode calls.  A truncated or inconsistent container is IFHIP_INVALID_ARGUMENT with an
+ * "ImageMalformed: libwebp decoding error ..." message.  Host only, no device needed. */
+IFHIP_API int ifhip_webp_info(const uint8_t* webp, size_t len, ifhip_webp_file_info* info);
+/* n files (host memory), each with its own size and transforms, into n device frames: d_frames[i] holds height_i rows of
+ * strides[i] bytes inside frame_bytes[i]; only the 4 * width_i bytes of a row are written.  d_status[i] (device) receives the
+ * file's status word; a damaged file leaves its frame untouched and never disturbs its neighbours.  A fixed number of
+ * launches per batch, every file in each: the token loop (one wave per file) and at most four inverse-transform steps.
+ * The streams are uploaded before the call returns; the kernels are asynchronous on hip_stream.  ICCP chunks are NOT acted
+ * on here (see color_kind).  Argument and frame checks come before the device check. */
+IFHIP_API int ifhip_webp_decode_batch_device(const uint8_t* const* files, const size_t* lens, uint32_t n_files,
+                                             uint8_t* const* d_frames, const size_t* frame_bytes, const uint32_t* strides,
+                                             uint32_t* d_status, void* hip_stream);
+/* The synchronous host-buffer drop-in for WebPDecode(MODE_BGRA): one file into `height` BGRA rows of `stride` bytes at bgra
+ * (capacity bytes; bytes between rows are kept).  A non-zero status word comes back in *status (nullable) with
+ * IFHIP_INVALID_ARGUMENT and an "ImageMalformed: libwebp decoding error" message; a lossy file is
+ * IFHIP_METHOD_NOT_IMPLEMENTED with an "ImageTypeNotSupported" message. */
+IFHIP_API int ifhip_webp_decode(const uint8_t* webp, size_t len, uint8_t* bgra, uint32_t stride, size_t capacity,
+                                uint32_t* status);
+
 /* Host, for tests: what the device coder works from -- the Annex K Huffman tables in encode form (dc0, ac0, dc1, ac1; 256
  * entries `code | length << 16`) and the marker segments in front of the scan (SOI ... SOS). */
 IFHIP_API int ifhip_jpeg_debug_encode_tables(uint32_t* tabs4x256, int n_components, const uint8_t* h_samp, const uint8_t* v_samp,

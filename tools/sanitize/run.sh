@@ -1,7 +1,8 @@
 #!/bin/bash
 # Host code of the JPEG stages under AddressSanitizer + UndefinedBehaviorSanitizer (no GPU): the file writer on random
 # coefficient planes with every option, and the header parser + un-stuffing + decode-table builders + host walkers
-# (ifhip_jpeg_debug_scan_report) on mutated copies of committed files.  Builds into /tmp; prints one summary line each.
+# (ifhip_jpeg_debug_scan_report) on mutated copies of committed files; the WebP decoder's container walk, prepare and token loop
+# on mutated copies of the tests' files.  Builds into /tmp; prints one summary line each.
 set -eu
 ROOT="$(cd "$(dirname "$0")/../.." && pwd)"
 W=/tmp/ifhip_sanitize; rm -rf $W; mkdir -p $W; cd $W
@@ -26,6 +27,21 @@ for i in (0, 5, 17, 33, 48, 60):
     open(f"/tmp/ifhip_sanitize/case_{i}.jpg", "wb").write(z[f"jpg_{i}"].tobytes())
 PY
 ASAN_OPTIONS=detect_leaks=0 ./parser_fuzz case_*.jpg
+# the WebP decoder's host side: container walk, prepare and the token loop on mutated copies of the tests' files
+/opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 --cuda-host-only $SAN $INC -c "$ROOT/imageflow_amd/csrc/webp_read.cpp" -o webp_read_host.o 2>/dev/null
+g++ $SAN -fno-sanitize=vptr $INC -c "$ROOT/tools/sanitize/webp_fuzz.cpp" -o webp_fuzz.o      # (vptr: g++ and the clang runtime that links disagree on it)
+/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o webp_fuzz webp_fuzz.o webp_read_host.o entropy_host.o devmem_host.o stubs.o fatbin_stub.o -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lpthread
+(cd "$ROOT" && python3 - <<'PY'
+from tests import webp_decode_fixtures as X
+files = X.good_files()
+for name in ("photo_q100_m6", "photo_cache", "indexed_16", "graphic", "own_two_bands", "gen_predictor_after_indexing", "gen_tile_bits_9_cache_11", "gen_meta_groups",
+             "gen_codes", "gen_simple_code_symbol_beyond_the_alphabet", "gen_vp8x_wrapped"):
+    open("/tmp/ifhip_sanitize/case_%s.webp" % name, "wb").write(files[name])
+for name, (data, _) in X.damaged_files().items():
+    open("/tmp/ifhip_sanitize/case_bad_%s.webp" % name, "wb").write(data)
+PY
+)
+ASAN_OPTIONS=detect_leaks=0 ./webp_fuzz case_*.webp
 # the whole library host-only (every translation unit, device blobs replaced by empty stand-ins) behind the libimageflow
 # ABI subset: damaged JSON jobs
 mkdir -p lib && : > fatbin_stubs.c
