@@ -7,6 +7,8 @@
 // -> encode -- as `steps` or as a `graph` with `input` edges (one producer per node, any number of consumers).  It is
 // NOT imageflow's router or graph engine: nodes outside that list answer ActionNotSupported, and everything a job
 // computes is computed by the ifhip_* entry points of this library on frames that stay in HBM.
+// A command_string's querystring is parsed and expanded into nodes by csrc/querystring.cpp (fit modes, crop, rotate, filters:
+// imageflow_riapi's Instructions and Ir4Layout::add_steps); the interpreter runs that node list like any other.
 //
 // Two labelled EXTENSIONS, because the reference's JSON API has no raw-pixel I/O:
 //   * decode accepts, besides JPEG and PNG (csrc/png_decode.hip), the container "IFBGRA1\0" + u32le w, h, stride, alpha_meaningful + rows;
@@ -44,6 +46,7 @@
 #include "png_read.hpp"         // the PNG chunk walk and the device decode of a walked file (png_read.cpp, png_decode.hip)
 #include "webp_read.hpp"        // the RIFF walk, the prepare and the device decode of a lossless WebP (webp_read.cpp, webp_decode.hip)
 #include "layout.hpp"           // imageflow_riapi's constraint layout (constrain / watermark)
+#include "querystring.hpp"      // imageflow_riapi's querystring: Instructions, their expansion into nodes (command_string)
 
 namespace {
 
@@ -269,35 +272,6 @@ uint32_t parse_color(const JVal* v, const char* node) {
     }
     return (ch[3] << 24) | (ch[0] << 16) | (ch[1] << 8) | ch[2];
 }
-std::string trim_ascii(const std::string& v) {
-    const size_t b = v.find_first_not_of(" \t\r\n\f\v"), e = v.find_last_not_of(" \t\r\n\f\v");
-    return b == std::string::npos ? std::string() : v.substr(b, e - b + 1);
-}
-// `str::parse::<f64>` (core dec2flt): an optional sign, then `inf`, `infinity` or `nan` in any case, or digits with an
-// optional fraction (at least one digit in all) and an optional exponent; no blanks, no hex.  The value: strtod's, which
-// rounds correctly as Rust does.
-bool rust_parse_f64(const std::string& s, double* out) {
-    size_t i = (!s.empty() && (s[0] == '+' || s[0] == '-')) ? 1 : 0;
-    std::string rest = s.substr(i);
-    for (char& ch : rest) ch = static_cast<char>(std::tolower(static_cast<unsigned char>(ch)));
-    bool ok = rest == "inf" || rest == "infinity" || rest == "nan";
-    if (!ok) {
-        size_t j = 0, digits = 0;
-        while (j < rest.size() && std::isdigit(static_cast<unsigned char>(rest[j]))) { ++j; ++digits; }
-        if (j < rest.size() && rest[j] == '.') { ++j; while (j < rest.size() && std::isdigit(static_cast<unsigned char>(rest[j]))) { ++j; ++digits; } }
-        ok = digits > 0;
-        if (ok && j < rest.size() && rest[j] == 'e') {
-            ++j;
-            if (j < rest.size() && (rest[j] == '+' || rest[j] == '-')) ++j;
-            const size_t e0 = j;
-            while (j < rest.size() && std::isdigit(static_cast<unsigned char>(rest[j]))) ++j;
-            ok = j > e0;
-        }
-        ok = ok && j == rest.size();
-    }
-    if (ok) *out = std::strtod(s.c_str(), nullptr);
-    return ok;
-}
 // s::Color::Transparent, the enum value (a missing colour reads as it): the only colour create_canvas.rs:79-82 turns into a
 // ReplaceSelf canvas -- an srgb colour whose alpha is 0 still makes a BlendWithMatte canvas
 bool keyword_transparent(const JVal* v) { return !v || v->is_null() || (v->t == JVal::Str && v->s == "transparent"); }
@@ -313,21 +287,32 @@ int parse_filter(const JVal* v, int dflt) {                      // imageflow_ty
     raise(kInvalidJson, "InvalidJson: unknown filter");
 }
 
-// `down.filter` / `up.filter` of a querystring: FilterStrings (imageflow_riapi/src/ir4/parsing.rs:159-193) spells every filter with
-// and without underscores, any case; -> the JSON name parse_filter takes.  A value the reference would drop with a warning
-// is refused here: a drop-in that cannot say "warning" must not pick another filter silently.
-std::string querystring_filter_name(std::string v) {
-    static const char* names[] = {"robidoux_fast", "robidoux", "robidoux_sharp", "ginseng", "ginseng_sharp", "lanczos", "lanczos_sharp", "lanczos_2",
-                                  "lanczos_2_sharp", "cubic", "cubic_sharp", "catmull_rom", "mitchell", "cubic_b_spline", "hermite", "jinc", "triangle",
-                                  "linear", "box", "fastest", "n_cubic", "n_cubic_sharp"};
-    auto squash = [](std::string t) {
-        std::string o;
-        for (char ch : t) if (ch != '_') o.push_back(static_cast<char>(std::tolower(static_cast<unsigned char>(ch))));
-        return o;
-    };
-    const std::string want = squash(v);
-    for (const char* n : names) if (squash(n) == want) return n;
-    raise(kArgumentInvalid, "InvalidNodeParams: querystring filter '%s' is not one of imageflow's filters", v.c_str());
+// JVal -> text: command_string.watermarks goes to the querystring expansion as text, and every number reads back as itself
+void to_json(const JVal& v, std::string* o) {
+    switch (v.t) {
+    case JVal::Null: *o += "null"; break;
+    case JVal::Bool: *o += v.b ? "true" : "false"; break;
+    case JVal::Num: { char buf[40]; std::snprintf(buf, sizeof buf, "%.17g", v.n); *o += buf; break; }
+    case JVal::Str:
+        o->push_back('"');
+        for (unsigned char ch : v.s) {
+            if (ch == '"' || ch == '\\') { o->push_back('\\'); o->push_back(static_cast<char>(ch)); }
+            else if (ch < 0x20) { char buf[8]; std::snprintf(buf, sizeof buf, "\\u%04x", ch); *o += buf; }
+            else o->push_back(static_cast<char>(ch));
+        }
+        o->push_back('"');
+        break;
+    case JVal::Arr:
+        o->push_back('[');
+        for (size_t i = 0; i < v.a.size(); ++i) { if (i) o->push_back(','); to_json(v.a[i], o); }
+        o->push_back(']');
+        break;
+    case JVal::Obj:
+        o->push_back('{');
+        for (size_t i = 0; i < v.o.size(); ++i) { if (i) o->push_back(','); to_json(JVal{JVal::Str, false, 0, v.o[i].first, {}, {}}, o); o->push_back(':'); to_json(v.o[i].second, o); }
+        o->push_back('}');
+        break;
+    }
 }
 
 // ---- frames in HBM ---------------------------------------------------------------------------------------------
@@ -569,44 +554,6 @@ const imageflow_json_response* respond_error(imageflow_context* c, int cat, cons
     const int code = http_code(cat);                             // JsonResponse::fail_with_message, json/mod.rs:170-181
     return respond(c, code, "{\n  \"code\": " + std::to_string(code) + ",\n  \"success\": false,\n  \"message\": \"" +
                                 json_escape(msg) + "\",\n  \"data\": \"none\"\n}");      // ResponsePayload::None, a unit variant renamed "none" (imageflow_types/src/lib.rs:2061-2062)
-}
-
-// ---- sizing: AspectRatio::proportional (imageflow_riapi/src/sizing.rs:118-185) ------------------------------------
-// The other side of a box that keeps `sw x sh`'s ratio, snapping to the source's own side or to the requested box when
-// the rounding loss of the requested box explains the difference (:83-116).
-double rust_round(double v) { return std::round(v); }            // f64::round: half away from zero, as C's round()
-int64_t proportional(int64_t sw, int64_t sh, int64_t basis, bool basis_is_width, bool have_target, int64_t tw, int64_t th) {
-    const double ratio = static_cast<double>(sw) / static_cast<double>(sh);
-    double snap_amount = 1.0 - 2.220446049250313e-16;
-    if (have_target) {
-        if (!basis_is_width) {                                    // rounding_loss_based_on_target_width (:83-98)
-            const double recreate_y = static_cast<double>(sh) * (static_cast<double>(tw) / static_cast<double>(sw));
-            snap_amount = std::fabs(static_cast<double>(tw) - rust_round(recreate_y) * ratio);
-        } else {                                                  // rounding_loss_based_on_target_height (:99-115)
-            const double recreate_x = static_cast<double>(sw) * (static_cast<double>(th) / static_cast<double>(sh));
-            snap_amount = std::fabs(static_cast<double>(th) - rust_round(recreate_x) / ratio);
-        }
-    }
-    const int64_t snap_a = basis_is_width ? sh : sw;
-    const int64_t snap_b = have_target ? (basis_is_width ? th : tw) : snap_a;
-    const double f = basis_is_width ? static_cast<double>(basis) / ratio : ratio * static_cast<double>(basis);
-    const double da = std::fabs(f - static_cast<double>(snap_a)), db = std::fabs(f - static_cast<double>(snap_b));
-    int64_t v;
-    if (da <= snap_amount && da <= db) v = snap_a;
-    else if (db <= snap_amount) v = snap_b;
-    else {
-        const double r = rust_round(f);
-        if (r <= -2147483648.0 || r >= 2147483647.0) raise(kArgumentInvalid, "LayoutError: ValueScalingFailed");
-        v = static_cast<int64_t>(r);
-    }
-    if (v < 0) raise(kArgumentInvalid, "LayoutError: ValueScalingFailed");
-    return v == 0 ? 1 : v;
-}
-// AspectRatio::box_of(target, Inner) (:189-197): the largest sw:sh box inside tw x th
-void inner_box(int64_t sw, int64_t sh, int64_t tw, int64_t th, int64_t* ow, int64_t* oh) {
-    const double rs = static_cast<double>(sw) / static_cast<double>(sh), rt = static_cast<double>(tw) / static_cast<double>(th);
-    if (rs > rt) { *ow = tw; *oh = proportional(sw, sh, tw, true, true, tw, th); }
-    else { *ow = proportional(sw, sh, th, false, true, tw, th); *oh = th; }
 }
 
 // ---- the job interpreter ---------------------------------------------------------------------------------------
@@ -1266,20 +1213,7 @@ struct Job {
         return canvas;
     }
 
-    // constrain (flow/nodes/constrain.rs:41-98 -> imageflow_riapi process_constraint): the aspect-preserving modes that
-    // need neither crop nor pad; sizes by AspectRatio::proportional / box_of (imageflow_riapi/src/sizing.rs:118-197).
-    static void constrain_size(const std::string& m, uint32_t sw, uint32_t sh, bool has_w, bool has_h, int64_t tw, int64_t th, uint32_t* ow, uint32_t* oh) {
-        int64_t w = sw, h = sh;
-        if (m == "distort") { w = has_w ? tw : (has_h ? proportional(sw, sh, th, false, false, 0, 0) : sw); h = has_h ? th : (has_w ? proportional(sw, sh, tw, true, false, 0, 0) : sh); }
-        else if (has_w && has_h) {
-            if (m == "fit" || sw > tw || sh > th) inner_box(sw, sh, tw, th, &w, &h);         // within never up-scales
-        } else if (has_w) {
-            if (m == "fit" || sw > tw) { w = tw; h = proportional(sw, sh, tw, true, false, 0, 0); }
-        } else if (has_h) {
-            if (m == "fit" || sh > th) { h = th; w = proportional(sw, sh, th, false, false, 0, 0); }
-        }
-        *ow = static_cast<uint32_t>(w); *oh = static_cast<uint32_t>(h);
-    }
+    // constrain (flow/nodes/constrain.rs:41-98 -> imageflow_riapi process_constraint, csrc/layout.cpp)
     static void constrain_params(const JVal& p, const char* node, std::string* mode, bool* has_w, bool* has_h, int64_t* tw, int64_t* th) {
         const JVal* jm = p.get("mode");
         *mode = jm && jm->t == JVal::Str ? jm->s : "";
@@ -1401,102 +1335,31 @@ struct Job {
         return copy_into_canvas(in, cv, 0, 0, in->w, in->h, l, t2);
     }
 
-    // command_string {kind: "ir4", value: "width=200&..."}: the querystring form of BASELINE config 1.  Only the sizing
-    // keys that reach the hot path (width/w, height/h, mode=max default; down.colorspace) -- imageflow_riapi is out of
-    // scope.  JPEG pre-shrink hint exactly as Ir4Expand::get_decode_commands (imageflow_riapi/src/ir4/mod.rs:155-210).
+    // command_string {kind: "ir4", value: "width=200&..."}: the querystring form of BASELINE config 1.  The text is parsed and
+    // expanded by csrc/querystring.cpp (Instructions -> Ir4Layout::add_steps / Ir4Expand::get_decode_commands, the function
+    // behind ifhip_shim_expand_command_string); what comes back -- decoder commands and a list of nodes in JSON -- runs through
+    // run_node like any other step, so the `performance` block names the nodes the reference's expansion would.  The encoder
+    // half (quality, jpeg.quality, format=jpg) is read here.
     FramePtr command_string(const JVal& p, FramePtr in, bool in_shared = false) {
         const JVal* kind = p.get("kind");
         const JVal* value = p.get("value");
         if (!kind || kind->t != JVal::Str || kind->s != "ir4" || !value || value->t != JVal::Str)
             raise(kInvalidJson, "InvalidJson: command_string needs kind \"ir4\" and a value");
-        double qw = 0, qh = 0;
-        bool srgb = false;
-        std::string down_filter;                 // `down.filter` (ir4/parsing.rs:580 -> layout.rs:527 ResampleHints::down_filter)
-        int quality = -1, jpeg_quality = -1;     // `quality` / `jpeg.quality` (ir4/encoder.rs:74: jpeg.quality, else quality)
-        bool jpeg_out = false;                   // `format=jpg|jpeg`
-        bool format_jpeg = false;                // `format=jpg|jpeg` itself (ir4/layout.rs:492-503: white corners); not `quality=abc`
-        bool round = false;                      // `s.roundcorners` (ir4/parsing.rs:811-840): 1 or 4 f64 values
-        double round_q[4] = {0, 0, 0, 0};
-        bool balance_white = false;              // `a.balancewhite=true|area` (:563-575)
-        bool trim = false;                       // `trim.threshold` (i32) given: trim; `trim.percentpadding` (f32)
-        int32_t trim_threshold = 0;
-        float trim_padding = 0.f;
-        size_t i = 0;
-        const std::string& q = value->s;
-        while (i < q.size()) {
-            const size_t amp = std::min(q.find('&', i), q.size());
-            const std::string kv = q.substr(i, amp - i);
-            i = amp + 1;
-            const size_t eq = kv.find('=');
-            if (eq == std::string::npos) continue;
-            std::string k = kv.substr(0, eq), v = kv.substr(eq + 1);
-            for (char& ch : k) ch = static_cast<char>(std::tolower(static_cast<unsigned char>(ch)));
-            if (k == "width" || k == "w" || k == "maxwidth") qw = std::atof(v.c_str());
-            else if (k == "height" || k == "h" || k == "maxheight") qh = std::atof(v.c_str());
-            else if (k == "down.colorspace") srgb = v == "srgb";
-            else if (k == "mode") { if (v != "max") raise(kActionNotSupported, "ActionNotSupported: querystring mode=%s (this shim: max)", v.c_str()); }
-            else if (k == "down.filter") down_filter = querystring_filter_name(v);
-            else if (k == "quality" || k == "jpeg.quality") {
-                char* end = nullptr;
-                const long q = std::strtol(v.c_str(), &end, 10);
-                // a value that is no integer is ignored with a warning by the reference (ir4/parsing.rs parse_i32): the encoder's
-                // default quality then applies -- the key still says "a JPEG comes out"
-                if (end == v.c_str() || *end) jpeg_out = true;
-                else (k == "quality" ? quality : jpeg_quality) = static_cast<int>(std::max(0l, std::min(100l, q)));
-            }
-            else if (k == "format") {
-                for (char& ch : v) ch = static_cast<char>(std::tolower(static_cast<unsigned char>(ch)));
-                if (v != "jpg" && v != "jpeg") raise(kActionNotSupported, "ActionNotSupported: querystring format=%s (this shim writes JPEG; PNG / GIF / WebP coders are out of scope)", v.c_str());
-                jpeg_out = true;
-                format_jpeg = true;
-            }
-            else if (k == "s.roundcorners") {
-                // warning_parse (:719-743) trims the value, and an empty one is no key; each comma-separated part is trimmed and
-                // parsed as an f64; a part that does not parse, or a count other than 1 or 4, is ignored with a warning
-                const std::string s = trim_ascii(v);
-                if (!s.empty()) {
-                    std::vector<double> vals;
-                    bool ok = true;
-                    size_t b = 0;
-                    while (ok) {
-                        const size_t c = std::min(s.find(',', b), s.size());
-                        double d = 0;
-                        ok = rust_parse_f64(trim_ascii(s.substr(b, c - b)), &d);
-                        vals.push_back(d);
-                        if (c == s.size()) break;
-                        b = c + 1;
-                    }
-                    if (ok && (vals.size() == 1 || vals.size() == 4)) {
-                        round = true;
-                        for (int j = 0; j < 4; ++j) round_q[j] = vals[vals.size() == 4 ? j : 0];
-                    }
-                }
-            }
-            else if (k == "a.balancewhite") {
-                // parse_white_balance (:1022-1033): a HistogramThresholdAlgorithm name in any case; only True and Area add the
-                // node (layout.rs:587-589), Simple and Gimp are kept with a warning and add nothing, other values are ignored
-                std::string s = trim_ascii(v);
-                for (char& ch : s) ch = static_cast<char>(std::tolower(static_cast<unsigned char>(ch)));
-                if (s == "true" || s == "area") balance_white = true;
-            }
-            else if (k == "trim.threshold" || k == "trim.percentpadding") {
-                // ir4/parsing.rs:534-537: parse_i32 / parse_f32 of the trimmed value; one that does not parse is ignored
-                const size_t b = v.find_first_not_of(" \t\r\n"), e = v.find_last_not_of(" \t\r\n");
-                const std::string s = b == std::string::npos ? std::string() : v.substr(b, e - b + 1);
-                char* end = nullptr;
-                errno = 0;
-                if (k == "trim.threshold") {
-                    const long long t2 = s.empty() ? 0 : std::strtoll(s.c_str(), &end, 10);
-                    if (end && end != s.c_str() && !*end && errno == 0 && t2 >= INT32_MIN && t2 <= INT32_MAX) { trim = true; trim_threshold = static_cast<int32_t>(t2); }
-                } else if (s.find_first_of("xXpP") == std::string::npos) {         // (Rust's f32 grammar has no hex floats)
-                    const float f = s.empty() ? 0.f : std::strtof(s.c_str(), &end);
-                    if (end && end != s.c_str() && !*end && std::isfinite(f)) trim_padding = f;
-                }
-            }
-            else raise(kActionNotSupported, "ActionNotSupported: querystring key '%s'", k.c_str());
-        }
-        if (!(qw >= 0 && qw <= 2147483647.0) || !(qh >= 0 && qh <= 2147483647.0)) raise(kArgumentInvalid, "InvalidNodeParams: querystring width/height out of range");
-        if (p.get("watermarks") && !p.get("watermarks")->is_null()) raise(kActionNotSupported, "ActionNotSupported: command_string.watermarks (use watermark nodes)");
+        ifhip::Ir4Instructions qs;
+        std::string err;
+        auto answer = [&](int rc) {
+            if (rc == ifhip::kQsRefused) raise(kActionNotSupported, "%s", err.c_str());
+            if (rc != ifhip::kQsOk) raise(err.rfind("InvalidJson", 0) == 0 ? kInvalidJson : kArgumentInvalid, "%s", err.c_str());
+        };
+        answer(ifhip::parse_querystring(value->s, &qs, &err));
+        std::string marks;
+        if (const JVal* wm = p.get("watermarks")) if (!wm->is_null()) to_json(*wm, &marks);
+        auto expansion = [&](uint32_t w, uint32_t h, uint32_t ref_w, uint32_t ref_h) {
+            std::string json;
+            answer(ifhip::expand_querystring(qs, static_cast<int32_t>(w), static_cast<int32_t>(h), static_cast<int32_t>(ref_w), static_cast<int32_t>(ref_h),
+                                             marks.empty() ? nullptr : marks.c_str(), &json, &err));
+            return parse_json(reinterpret_cast<const uint8_t*>(json.data()), json.size());
+        };
         const JVal* dec = p.get("decode");
         const JVal* enc = p.get("encode");
         uint32_t src_w = 0, src_h = 0;
@@ -1505,54 +1368,50 @@ struct Job {
         if (dec && dec->t == JVal::Num) image_size(static_cast<int32_t>(want_int(p, "decode", "command_string")), &src_w, &src_h, true);
         else if (in) { src_w = in->w; src_h = in->h; }
         else raise(kGraphInvalid, "GraphInvalid: command_string has neither a decode io nor an input frame");
-        if (trim) {
+        if (qs.trim_threshold.some) {
             // Ir4Expand::translate (ir4/mod.rs:97-121): a decode WITHOUT downscale hints, CropWhitespace on the decoded frame,
             // and the rest of the querystring laid out against the trimmed frame
             if (dec && dec->t == JVal::Num) { in = decode_oriented(static_cast<int32_t>(dec->n), 0, 0, false, false); dec = nullptr; }
-            in = crop_whitespace(in, static_cast<uint32_t>(std::max<int32_t>(0, trim_threshold)), trim_padding, false);
+            in = crop_whitespace(in, static_cast<uint32_t>(std::max<int32_t>(0, qs.trim_threshold.v)), qs.trim_padding, false);
             src_w = in->w; src_h = in->h;
         }
-        auto target = [&](uint32_t sw, uint32_t sh, uint32_t* ow, uint32_t* oh) {        // mode=max: fit inside, never up-scale
-            constrain_size("within", sw, sh, qw >= 1, qh >= 1, static_cast<int64_t>(qw), static_cast<int64_t>(qh), ow, oh);
-        };
         if (dec && dec->t == JVal::Num) {
+            // Ir4Expand::get_decode_commands against the file's size: discard_color_profile, the JPEG pre-shrink hints worked out
+            // from the CROPPED window (get_downscaling), the WebP hint that goes out only with down.colorspace=srgb
             uint32_t hint_w = 0, hint_h = 0;
+            bool spatial = qs.down_colorspace != ifhip::Ir4Instructions::kSrgb, gamma = spatial;
+            Io& src = input(static_cast<int32_t>(dec->n));
+            if (qs.ignoreicc.some && qs.ignoreicc.v) src.told_discard_profile = true;
             if (src_w) {
-                uint32_t ow, oh;
-                target(src_w, src_h, &ow, &oh);
-                const double downscale = std::min(static_cast<double>(src_w) / ow, static_cast<double>(src_h) / ow);   // sic: `to.w` twice (:161-162)
-                const double preshrink = 2.1 / downscale;
-                if (preshrink < 1.0) { hint_w = static_cast<uint32_t>(std::floor(src_w * preshrink)); hint_h = static_cast<uint32_t>(std::floor(src_h * preshrink)); }
+                const JVal ex = expansion(src_w, src_h, src_w, src_h);
+                for (const JVal& cmd : ex.get("decoder_commands")->a) {
+                    if (const JVal* j = cmd.get("jpeg_downscale_hints")) {
+                        hint_w = want_u32(*j, "width", "jpeg_downscale_hints"); hint_h = want_u32(*j, "height", "jpeg_downscale_hints");
+                        spatial = j->get("scale_luma_spatially")->b; gamma = j->get("gamma_correct_for_srgb_during_spatial_luma_scaling")->b;
+                    } else if (cmd.get("webp_decoder_hints") && hint_w && is_webp(src)) { src.told_webp = true; src.told_webp_w = hint_w; src.told_webp_h = hint_h; }
+                }
             }
-            if (srgb && hint_w) {                                        // the WebP hint goes out only with down.colorspace=srgb (ir4/mod.rs:187-199)
-                Io& src = input(static_cast<int32_t>(dec->n));
-                if (is_webp(src)) { src.told_webp = true; src.told_webp_w = hint_w; src.told_webp_h = hint_h; }
-            }
-            in = decode_oriented(static_cast<int32_t>(dec->n), hint_w, hint_h, !srgb, !srgb);
+            in = decode_oriented(static_cast<int32_t>(dec->n), hint_w, hint_h, spatial, gamma);
             if (!src_w) { src_w = in->w; src_h = in->h; }
         }
-        uint32_t ow, oh;
-        target(src_w, src_h, &ow, &oh);
-        JVal hints;
-        hints.t = JVal::Obj;
-        if (srgb) { JVal cs; cs.t = JVal::Str; cs.s = "srgb"; hints.o.emplace_back("scaling_colorspace", cs); }
-        if (!down_filter.empty()) { JVal f; f.t = JVal::Str; f.s = down_filter; hints.o.emplace_back("down_filter", f); }
-        {   // background_color: Some(bgcolor), Transparent unless the querystring names format=jpg, then white (ir4/layout.rs:492-503, :530)
-            JVal bg;
-            if (jpeg_out) { JVal hex; hex.t = JVal::Str; hex.s = "FFFFFFFF"; JVal srgb; srgb.t = JVal::Obj; srgb.o.emplace_back("hex", hex); bg.t = JVal::Obj; bg.o.emplace_back("srgb", srgb); }
-            else { bg.t = JVal::Str; bg.s = "transparent"; }
-            hints.o.emplace_back("background_color", bg);
+        // after a reduced decode the layout runs again on the decoded size, with the file's size as reference
+        const JVal ex = expansion(in->w, in->h, src_w, src_h);
+        const FramePtr given = in;
+        FramePtr out = in;
+        for (const JVal& n : ex.get("steps")->a) {
+            std::string name;
+            const JVal* params;
+            node_of(n, &name, &params);
+            bool shared = in_shared && out == given;
+            if (shared && mutates_input(name)) { out = clone(out, true); shared = false; }            // the expansion's nodes are MutProtect where the graph's are
+            if (name == "round_image_corners") {
+                // (the radii as parsed, not through JSON: `s.roundcorners=nan` is a value the reference runs with)
+                const double* q = qs.round_corners;
+                const float radii[4] = {static_cast<float>(q[0]), static_cast<float>(q[1]), static_cast<float>(q[2]), static_cast<float>(q[3])};
+                const bool all_eq = q[0] == q[1] && q[0] == q[2] && q[0] == q[3];
+                out = round_corners(out, all_eq ? IFHIP_ROUND_CORNERS_PERCENTAGE : IFHIP_ROUND_CORNERS_PERCENTAGE_CUSTOM, radii, parse_color(params->get("background_color"), "round_image_corners.background_color"));
+            } else out = run_node(name, *params, out, nullptr, shared);
         }
-        FramePtr out = resample(in, ow, oh, &hints);
-        if ((round || balance_white) && out == in && in_shared) out = clone(out, true);      // both nodes are MutProtect
-        if (round) {
-            // ir4/layout.rs:531-549: Percentage when all four values are equal, else PercentageCustom {tl, tr, br, bl}; the
-            // colour is bgcolor, which defaults to white only for format=jpg|jpeg (:492-503)
-            const float radii[4] = {static_cast<float>(round_q[0]), static_cast<float>(round_q[1]), static_cast<float>(round_q[2]), static_cast<float>(round_q[3])};
-            const bool all_eq = round_q[0] == round_q[1] && round_q[0] == round_q[2] && round_q[0] == round_q[3];   // iter_all_eq (NaN: never)
-            out = round_corners(out, all_eq ? IFHIP_ROUND_CORNERS_PERCENTAGE : IFHIP_ROUND_CORNERS_PERCENTAGE_CUSTOM, radii, format_jpeg ? 0xFFFFFFFFu : 0u);
-        }
-        if (balance_white) out = white_balance(out, 0.006f);                                // (:590-592) threshold None
         if (enc && enc->t == JVal::Num) {
             // The reference keeps the source's format (a JPEG stays a JPEG, ir4/encoder.rs:30-37 OutputFormat::Keep) and hands
             // `jpeg.quality`, else `quality`, to its JPEG encoder (encoder.rs:74; 90 when neither is given, codecs/auto.rs).  Here a
@@ -1561,8 +1420,8 @@ struct Job {
             // (trellis / scan search) is not built, so bytes and sizes differ from the reference's default for the same string
             // (README "Known differences", DESIGN "Encode").  One that names neither keeps this shim's labelled extension, the raw
             // BGRA container -- no key is accepted and then dropped.
-            const int q = jpeg_quality >= 0 ? jpeg_quality : quality;
-            if (jpeg_out || q >= 0) {
+            const int q = qs.jpeg_quality >= 0 ? qs.jpeg_quality : qs.quality;
+            if (qs.jpeg_out || q >= 0) {
                 JVal qv; qv.t = JVal::Num; qv.n = q >= 0 ? q : 90;
                 JVal classic; classic.t = JVal::Obj; classic.o.emplace_back("quality", qv);
                 JVal preset; preset.t = JVal::Obj; preset.o.emplace_back("libjpeg_turbo", classic);
@@ -2037,6 +1896,12 @@ struct Job {
             if (th && !th->is_null() && th->t != JVal::Num) raise(kInvalidJson, "InvalidJson: white_balance_histogram_area_threshold_srgb.threshold is a number or null");
             return white_balance(in, th && th->t == JVal::Num ? static_cast<float>(th->n) : 0.006f);
         }
+        if (name == "watermark_red_dot") {                                            // flow/nodes/watermark_red_dot.rs:26-40: FillRect over the last 3x3 pixels
+            if (!(in->w > 3 && in->h > 3)) return in;
+            char text[160];
+            std::snprintf(text, sizeof text, "{\"x1\":%u,\"y1\":%u,\"x2\":%u,\"y2\":%u,\"color\":{\"srgb\":{\"hex\":\"FF0000\"}}}", in->w - 3, in->h - 3, in->w, in->h);
+            return run_node("fill_rect", parse_json(reinterpret_cast<const uint8_t*>(text), std::strlen(text)), in, nullptr, in_shared);
+        }
         if (name == "crop_whitespace") {                                              // s::Node::CropWhitespace {threshold: u32, percent_padding: f32}
             const int64_t thr = want_int(p, "threshold", "crop_whitespace");
             if (thr < 0 || thr > 0xFFFFFFFFll) raise(kInvalidJson, "InvalidJson: crop_whitespace.threshold out of range");
@@ -2147,7 +2012,7 @@ struct Job {
         *params = &n.o[0].second;
     }
     static bool mutates_input(const std::string& nm) {
-        return nm == "fill_rect" || nm == "flip_v" || nm == "flip_h" || nm == "rotate_180" || nm == "color_matrix_srgb" || nm == "color_filter_srgb" ||
+        return nm == "fill_rect" || nm == "watermark_red_dot" || nm == "flip_v" || nm == "flip_h" || nm == "rotate_180" || nm == "color_matrix_srgb" || nm == "color_filter_srgb" ||
                nm == "apply_orientation" || nm == "watermark" || nm == "round_image_corners" || nm == "white_balance_histogram_area_threshold_srgb";
     }
 

@@ -2,10 +2,13 @@
 // the nine ConstraintMode values: AspectRatio (sizing.rs:14-222), Layout and its steps (sizing.rs:267-471), the step
 // programs per (mode, scale) pair (ir4/layout.rs:160-283), target size (:105-139), gravity (:673-698), results (:334-412).
 // Integer and f64 / f32 arithmetic in the reference's order, so that a size that rounds at .5 rounds the same way.
+// The querystring's own layout (ir4_crop_and_layout) runs the same step programs, plus the UpscaleCanvas rows that no
+// ConstraintMode reaches, behind get_precrop / get_initial_copy_window (:47-61, :700-775) and get_wh_from_all (:63-91).
 #include "layout.hpp"
 
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 
 namespace ifhip {
@@ -81,6 +84,12 @@ struct Layout {                                        // sizing::Layout (:267-2
         if (canvas.exceeds_any(t)) throw LayoutErr{"ImpossiblePad { target: " + dbg(t) + ", current: " + dbg(canvas) + " }"};
         canvas = t;
     }
+    void virtual_canvas(const AR& t) {                 // :333-337
+        const AR ni = intersection(image, t);
+        source = box_of(ni, source, kInner);
+        image = ni;
+        canvas = t;
+    }
     void crop(const AR& t) {                           // :339-346
         if (t.exceeds_any(canvas)) throw LayoutErr{"ImpossibleCrop { target: " + dbg(t) + ", current: " + dbg(canvas) + " }"};
         const AR ni = intersection(image, t);
@@ -95,12 +104,81 @@ struct Layout {                                        // sizing::Layout (:267-2
     bool larger_1d_smaller_1d() const { return (cmp_w() > 0 && cmp_h() < 0) || (cmp_w() < 0 && cmp_h() > 0); }   // :524-527
 };
 
+// `x as i32` of a float: NaN is 0, everything else saturates
+int32_t as_i32(double v) { return v != v ? 0 : v >= 2147483647.0 ? INT32_MAX : v <= -2147483648.0 ? INT32_MIN : static_cast<int32_t>(v); }
+
 // gravity1d (ir4/layout.rs:673-683)
 int32_t gravity1d(float align_percentage, int32_t inner, int32_t outer) {
-    const float ratio = std::min(std::max(align_percentage, 0.f), 100.f) / 100.f;
+    const float ratio = std::min(std::max(align_percentage, 0.f), 100.f) / 100.f;             // (f32::clamp keeps a NaN, as these do)
     if ((outer < inner && inner < 1) || outer < 1) throw LayoutErr{"Outer box should never be smaller than inner box. All values must > 0"};
     const float v = std::round(static_cast<float>(outer - inner) * ratio);
-    return std::max<int32_t>(0, std::min<int32_t>(static_cast<int32_t>(v), outer - inner));
+    return std::max<int32_t>(0, std::min<int32_t>(as_i32(v), outer - inner));
+}
+
+// the step programs of build_constraints (:160-283), run as execute_all runs them (sizing.rs:436-463): a failed SkipUnless / a
+// met SkipIf skips to the next BeginSequence; conditions compare the CURRENT canvas with the target
+void run_constraints(Layout& lay, int fit, int scale) {
+    const bool gate_down = lay.either(1), gate_up = lay.neither(1);                            // Either(Greater) / Neither(Greater)
+    const bool gate = scale == kIr4Both || ((scale == kIr4Down || scale == kIr4Canvas) && gate_down) || (scale == kIr4Up && gate_up);
+    if (fit == kIr4Max) {
+        if (gate) lay.scale_canvas(kInner);
+        if (scale == kIr4Canvas) lay.virtual_canvas(box_of(lay.canvas, lay.target, kInner));   // BoxOf {target: Target, ratio_source: CurrentCanvas, Inner}
+    } else if (fit == kIr4Pad) {
+        if (scale == kIr4Canvas) { if (gate) lay.scale_canvas(kInner); lay.pad_canvas(lay.target); }
+        else if (gate) { lay.scale_canvas(kInner); lay.pad_canvas(lay.target); }
+    } else if (fit == kIr4Stretch) {
+        if (gate) lay.distort_canvas(lay.target);
+        if (scale == kIr4Canvas) lay.pad_canvas(lay.target);
+    } else if (fit == kIr4Crop) {
+        if (scale == kIr4Both || (scale == kIr4Up && gate_up)) { lay.scale_canvas(kOuter); lay.crop(lay.target); }
+        else if (scale == kIr4Down || scale == kIr4Canvas) {
+            if (!lay.either(-1)) { lay.scale_canvas(kOuter); lay.crop(lay.target); }            // skip_if(Either(Less))
+            if (lay.larger_1d_smaller_1d()) {                                                  // new_seq().skip_unless(Larger1DSmaller1D)
+                if (scale == kIr4Down) lay.crop(intersection(lay.image, lay.target));          // .crop_intersection()
+                else lay.virtual_canvas(lay.target);                                           // .virtual_canvas(Exact(Target))
+            }
+        }
+    } else {
+        lay.crop(box_of(lay.target, lay.canvas, kInner));                                       // CropAspect (sizing.rs:419)
+    }
+}
+
+int32_t align1d(const Anchor1D& a, int32_t inner, int32_t outer) {                             // Ir4Layout::align1d (:649-660)
+    if ((outer < inner && inner < 1) || outer < 1) throw LayoutErr{"Outer box should never be smaller than inner box. All values must > 0"};
+    switch (a.kind) {
+    case Anchor1D::kNear: return 0;
+    case Anchor1D::kCenter: return (outer - inner) / 2;
+    case Anchor1D::kFar: return outer - inner;
+    default: return gravity1d(a.percent, inner, outer);
+    }
+}
+
+// get_wh_from_all (:63-91): 0 stands for None
+void wh_from_all(const Ir4LayoutParams& i, const AR& source, int32_t* ow, int32_t* oh) {
+    int32_t w = std::max(i.w.some ? i.w.v : -1, -1), h = std::max(i.h.some ? i.h.v : -1, -1);
+    int32_t mw = std::max(i.legacy_max_width.some ? i.legacy_max_width.v : -1, -1), mh = std::max(i.legacy_max_height.some ? i.legacy_max_height.v : -1, -1);
+    if (mw > 0 && w > 0) { w = std::min(mw, w); mw = -1; }
+    if (mh > 0 && h > 0) { h = std::min(mh, h); mh = -1; }
+    if (w != -1 && mh != -1) mh = std::min(mh, proportional(source, w, true, nullptr));
+    if (h != -1 && mw != -1) mw = std::min(mw, proportional(source, h, false, nullptr));
+    w = std::max(w, mw); h = std::max(h, mh);
+    *ow = w < 1 ? 0 : w; *oh = h < 1 ? 0 : h;
+}
+
+// get_ideal_target_size (:93-131)
+AR ideal_target_size(const Ir4LayoutParams& i, const AR& source, double preshrink_ratio) {
+    const int32_t unshrunk_w = as_i32(static_cast<double>(source.w) / preshrink_ratio), unshrunk_h = as_i32(static_cast<double>(source.h) / preshrink_ratio);
+    int32_t w, h;
+    wh_from_all(i, source, &w, &h);
+    if (!w && !h) { w = unshrunk_w; h = unshrunk_h; }
+    else if (!h) h = proportional(source, w, true, nullptr);
+    else if (!w) w = proportional(source, h, false, nullptr);
+    // float_min / float_max (:133-158) of comparable values: the parser lets only a finite zoom through
+    double zoom = i.zoom.some ? static_cast<double>(i.zoom.v) : 1.0;
+    if (!std::isfinite(zoom)) zoom = 80000.0;
+    zoom = std::max(0.00008, std::min(zoom, 80000.0));
+    auto side = [&](int32_t v) { return as_i32(std::max(1.0, std::min(std::round(static_cast<double>(v) * zoom), 2147483647.0))); };
+    return create(side(w), side(h));
 }
 
 }  // namespace
@@ -123,40 +201,22 @@ bool process_constraint(int mode, int32_t source_w, int32_t source_h, int64_t w,
         else if (some_w) target = create(w, proportional(initial, static_cast<int32_t>(w), true, nullptr));
         else if (some_h) target = create(proportional(initial, static_cast<int32_t>(h), false, nullptr), h);
         // build_constraints (:160-283): both sides ABSENT (not merely < 1) forces FitMode::Max
-        enum Fit { kMax, kPad, kStretch, kCrop, kAspect } fit;
-        enum Scale { kDown, kUp, kBoth } scale = kDown;
+        int fit, scale = kIr4Down;
         switch (mode) {                                                                        // get_instructions (:290-332)
-        case kDistort: fit = kStretch; scale = kBoth; break;
-        case kWithin: fit = kMax; scale = kDown; break;
-        case kFit: fit = kMax; scale = kBoth; break;
-        case kLargerThan: fit = kMax; scale = kUp; break;
-        case kWithinCrop: fit = kCrop; scale = kDown; break;
-        case kFitCrop: fit = kCrop; scale = kBoth; break;
-        case kAspectCrop: fit = kAspect; scale = kDown; break;
-        case kWithinPad: fit = kPad; scale = kDown; break;
-        case kFitPad: fit = kPad; scale = kBoth; break;
+        case kDistort: fit = kIr4Stretch; scale = kIr4Both; break;
+        case kWithin: fit = kIr4Max; scale = kIr4Down; break;
+        case kFit: fit = kIr4Max; scale = kIr4Both; break;
+        case kLargerThan: fit = kIr4Max; scale = kIr4Up; break;
+        case kWithinCrop: fit = kIr4Crop; scale = kIr4Down; break;
+        case kFitCrop: fit = kIr4Crop; scale = kIr4Both; break;
+        case kAspectCrop: fit = kIr4AspectCrop; scale = kIr4Down; break;
+        case kWithinPad: fit = kIr4Pad; scale = kIr4Down; break;
+        case kFitPad: fit = kIr4Pad; scale = kIr4Both; break;
         default: throw LayoutErr{"NotImplemented"};
         }
-        if (w < 0 && h < 0) fit = kMax;
+        if (w < 0 && h < 0) fit = kIr4Max;
         Layout lay{initial, target, initial, initial};                                         // Layout::create (:452-454)
-        // the step programs, run as execute_all runs them (:422-450): a failed SkipUnless / a met SkipIf skips to the next
-        // BeginSequence; conditions compare the CURRENT canvas with the target
-        const bool gate_down = lay.either(1), gate_up = lay.neither(1);                        // Either(Greater) / Neither(Greater)
-        if (fit == kMax) {
-            if (scale == kBoth || (scale == kDown && gate_down) || (scale == kUp && gate_up)) lay.scale_canvas(kInner);
-        } else if (fit == kPad) {
-            if (scale == kBoth || (scale == kDown && gate_down) || (scale == kUp && gate_up)) { lay.scale_canvas(kInner); lay.pad_canvas(lay.target); }
-        } else if (fit == kStretch) {
-            if (scale == kBoth || (scale == kDown && gate_down) || (scale == kUp && gate_up)) lay.distort_canvas(lay.target);
-        } else if (fit == kCrop) {
-            if (scale == kBoth || (scale == kUp && gate_up)) { lay.scale_canvas(kOuter); lay.crop(lay.target); }
-            else if (scale == kDown) {
-                if (!lay.either(-1)) { lay.scale_canvas(kOuter); lay.crop(lay.target); }        // skip_if(Either(Less))
-                if (lay.larger_1d_smaller_1d()) lay.crop(intersection(lay.image, lay.target));  // new_seq().skip_unless(Larger1DSmaller1D).crop_intersection()
-            }
-        } else {
-            lay.crop(box_of(lay.target, lay.canvas, kInner));                                   // CropAspect (:403)
-        }
+        run_constraints(lay, fit, scale);
         // results (:359-411)
         const float x = has_gravity ? gx : 50.f, y = has_gravity ? gy : 50.f;
         const AR new_crop = lay.source;
@@ -177,6 +237,75 @@ bool process_constraint(int mode, int32_t source_w, int32_t source_h, int64_t w,
             r.pad[0] = static_cast<uint32_t>(left); r.pad[1] = static_cast<uint32_t>(top);
             r.pad[2] = static_cast<uint32_t>(right); r.pad[3] = static_cast<uint32_t>(bottom);
         }
+        *out = r;
+        return true;
+    } catch (const LayoutErr& e) {
+        if (error) *error = e.text;
+        return false;
+    }
+}
+
+bool ir4_align(const Anchor1D& x, const Anchor1D& y, int32_t inner_w, int32_t inner_h, int32_t outer_w, int32_t outer_h, int32_t* left, int32_t* top) {
+    try {
+        *left = align1d(x, inner_w, outer_w);
+        *top = align1d(y, inner_h, outer_h);
+        return true;
+    } catch (const LayoutErr&) {
+        return false;
+    }
+}
+
+bool ir4_crop_and_layout(const Ir4LayoutParams& i, int32_t w, int32_t h, int32_t reference_w, int32_t reference_h, Ir4LayoutResult* out,
+                         std::string* error) {
+    try {
+        // get_precrop / get_precrop_reference (:47-61): srotate by a quarter turn swaps the sides
+        const bool swap = (((i.srotate.some ? i.srotate.v : 0) / 90 + 4) % 2) != 0;
+        const int32_t pw = swap ? h : w, ph = swap ? w : h, ref_w = swap ? reference_h : reference_w, ref_h = swap ? reference_w : reference_h;
+        // get_initial_copy_window_floats (:729-775) against the reference size
+        double fl[4] = {0, 0, static_cast<double>(ref_w), static_cast<double>(ref_h)};
+        if (i.has_crop) {
+            const double xunits = i.cropxunits.some && i.cropxunits.v != 0.0 ? i.cropxunits.v : static_cast<double>(ref_w);
+            const double yunits = i.cropyunits.some && i.cropyunits.v != 0.0 ? i.cropyunits.v : static_cast<double>(ref_h);
+            double v4[4];
+            for (int ix = 0; ix < 4; ++ix) {
+                const double relative_to = ix % 2 == 0 ? xunits : yunits, max_dimension = static_cast<double>(ix % 2 == 0 ? ref_w : ref_h);
+                double v = i.crop[ix] * max_dimension / relative_to;
+                if ((ix < 2 && v < 0.0) || (ix > 1 && v <= 0.0)) v += max_dimension;           // negative offsets from the far edge
+                if (v < 0.0) v = 0.0;
+                if (v > max_dimension) v = max_dimension;
+                v4[ix] = v;
+            }
+            if (!(std::round(v4[3]) <= std::round(v4[1]) || std::round(v4[2]) <= std::round(v4[0])))
+                for (int ix = 0; ix < 4; ++ix) fl[ix] = v4[ix];
+        }
+        // get_initial_copy_window (:700-725): re-scaled to the decoded size, rounded, clamped; the whole frame when x2 <= x1
+        if (ref_w != pw || ref_h != ph) {
+            fl[0] = fl[0] * static_cast<double>(pw) / static_cast<double>(ref_w); fl[2] = fl[2] * static_cast<double>(pw) / static_cast<double>(ref_w);
+            fl[1] = fl[1] * static_cast<double>(ph) / static_cast<double>(ref_h); fl[3] = fl[3] * static_cast<double>(ph) / static_cast<double>(ref_h);
+        }
+        int32_t win[4];
+        for (int ix = 0; ix < 4; ++ix) win[ix] = std::max<int32_t>(0, std::min<int32_t>(as_i32(std::round(fl[ix])), ix % 2 == 0 ? pw : ph));
+        if (win[3] <= win[1] || win[2] <= win[0]) { win[0] = 0; win[1] = 0; win[2] = pw; win[3] = ph; }
+        const AR initial = create(static_cast<int64_t>(win[2]) - win[0], static_cast<int64_t>(win[3]) - win[1]);
+        const AR target = ideal_target_size(i, initial, static_cast<double>(w) / static_cast<double>(reference_w));   // get_preshrink_ratio (:43-45)
+        const int fit = !i.w.some && !i.h.some ? kIr4Max : i.mode == kIr4FitUnset ? kIr4Pad : i.mode;                    // build_constraints (:164-168)
+        Layout lay{initial, target, initial, initial};
+        run_constraints(lay, fit, i.scale == kIr4ScaleUnset ? kIr4Down : i.scale);
+        const AR new_crop = lay.source;
+        // c.gravity before anchor, centre otherwise (:441-449)
+        Anchor1D ax, ay;
+        if (i.has_c_gravity) { ax.kind = ay.kind = Anchor1D::kPercent; ax.percent = static_cast<float>(i.c_gravity[0]); ay.percent = static_cast<float>(i.c_gravity[1]); }
+        else if (i.has_anchor) { ax = i.anchor_x; ay = i.anchor_y; }
+        const int64_t x1 = static_cast<int64_t>(win[0]) + align1d(ax, new_crop.w, initial.w), y1 = static_cast<int64_t>(win[1]) + align1d(ay, new_crop.h, initial.h);
+        Ir4LayoutResult r;
+        if (x1 > 0 || y1 > 0 || pw != new_crop.w || ph != new_crop.h) {                                                 // :455-468
+            r.has_crop = true;
+            r.crop[0] = static_cast<uint32_t>(x1); r.crop[1] = static_cast<uint32_t>(y1);
+            r.crop[2] = static_cast<uint32_t>(x1 + new_crop.w); r.crop[3] = static_cast<uint32_t>(y1 + new_crop.h);
+        }
+        r.source_w = new_crop.w; r.source_h = new_crop.h;
+        r.image_w = lay.image.w; r.image_h = lay.image.h;
+        r.canvas_w = lay.canvas.w; r.canvas_h = lay.canvas.h;
         *out = r;
         return true;
     } catch (const LayoutErr& e) {

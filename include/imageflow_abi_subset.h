@@ -129,6 +129,19 @@ IMAGEFLOW_SHIM_API int ifhip_shim_process_constraint(const char *mode, int32_t s
                                                      uint32_t *crop_x1y1x2y2, int32_t *scale_to_wh, uint32_t *pad_ltrb,
                                                      int32_t *canvas_wh, int *flags);
 
+/* What `command_string` {kind: "ir4", value} expands to, callable on its own (no GPU, no context): the querystring is parsed
+ * (imageflow_riapi Instructions) and laid out for a frame of source_w x source_h decoded from an image of reference_w x
+ * reference_h (the two differ after a reduced JPEG decode), as Ir4Layout::add_steps and Ir4Expand::get_decode_commands do.
+ * watermarks_json: the JSON text of command_string.watermarks (an array), or NULL.  Writes
+ * {"decoder_commands": [...], "steps": [...], "canvas": [w, h]} -- the steps in the JSON form v1/execute takes, without decode
+ * and encode -- and its length with the terminating 0 to *needed; the text is copied only when cap is large enough (out may be
+ * NULL with cap 0).  Returns 0; 1 for a layout error (the reference's Err); 2 for a key or value this library refuses
+ * (ActionNotSupported); 3 for an argument no querystring of the reference's could mean.  For 1, 2 and 3 the text is where
+ * ifhip_last_error_message() finds it.  command_string itself runs this expansion. */
+IMAGEFLOW_SHIM_API int ifhip_shim_expand_command_string(const char *value, int32_t source_w, int32_t source_h, int32_t reference_w,
+                                                        int32_t reference_h, const char *watermarks_json, char *out, size_t cap,
+                                                        size_t *needed);
+
 #ifdef __cplusplus
 }
 #endif

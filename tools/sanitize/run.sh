@@ -2,7 +2,8 @@
 # Host code of the JPEG stages under AddressSanitizer + UndefinedBehaviorSanitizer (no GPU): the file writer on random
 # coefficient planes with every option, and the header parser + un-stuffing + decode-table builders + host walkers
 # (ifhip_jpeg_debug_scan_report) on mutated copies of committed files; the WebP decoder's container walk, prepare and token loop
-# on mutated copies of the tests' files.  Builds into /tmp; prints one summary line each.
+# on mutated copies of the tests' files; the querystring parser and layout behind command_string on damaged strings.
+# Builds into /tmp; prints one summary line each.
 set -eu
 ROOT="$(cd "$(dirname "$0")/../.." && pwd)"
 W=/tmp/ifhip_sanitize; rm -rf $W; mkdir -p $W; cd $W
@@ -42,6 +43,9 @@ for name, (data, _) in X.damaged_files().items():
 PY
 )
 ASAN_OPTIONS=detect_leaks=0 ./webp_fuzz case_*.webp
+# the querystring layer (Instructions parser, colour reader, Ir4Layout, watermark splitter): untrusted text, plain host code
+g++ $SAN $INC -o querystring_fuzz "$ROOT/tools/sanitize/querystring_fuzz.cpp" "$ROOT/imageflow_amd/csrc/querystring.cpp" "$ROOT/imageflow_amd/csrc/layout.cpp" "$ROOT/tools/sanitize/stubs.cpp"
+./querystring_fuzz
 # the whole library host-only (every translation unit, device blobs replaced by empty stand-ins) behind the libimageflow
 # ABI subset: damaged JSON jobs
 mkdir -p lib && : > fatbin_stubs.c
