@@ -70,6 +70,8 @@ def _bind():
     L.ifhip_shim_context_set_device.restype = C.c_bool
     L.ifhip_shim_context_device.argtypes = [vp]
     L.ifhip_shim_context_device.restype = C.c_int
+    L.ifhip_shim_context_set_color_management.argtypes = [vp, C.c_int]
+    L.ifhip_shim_context_set_color_management.restype = C.c_bool
     L.imageflow_context_memory_allocate.argtypes = [vp, C.c_size_t, C.c_char_p, C.c_int32]
     L.imageflow_context_memory_allocate.restype = vp
     L.imageflow_context_memory_free.argtypes = [vp, vp, C.c_char_p, C.c_int32]
@@ -151,6 +153,12 @@ class Context:
     def set_device(self, ordinal):
         """Bind the context's jobs to a device ordinal (-1: the calling thread's current device); False + a context error otherwise."""
         return self.L.ifhip_shim_context_set_device(self.p, ordinal)
+
+    def set_color_management(self, on):
+        """EXTENSION, off by default: convert every input whose ICC profile or PNG gAMA + cHRM is not sRGB to sRGB on the device
+        behind its decode, instead of refusing the job (the decoder command "convert_color_profile" does it for one input;
+        "discard_color_profile" wins over both)."""
+        return self.L.ifhip_shim_context_set_color_management(self.p, 1 if on else 0)
 
     @property
     def device(self):

@@ -43,6 +43,7 @@
 #include "../../include/imageflow_abi_subset.h"
 #include "../../include/imageflow_hip.h"
 #include "common.hpp"           // the library's per-job memory cache and thread stream (devmem.cpp)
+#include "color_profile.hpp"   // a colour profile as a conversion plan (color_profile.cpp; the kernel: color_profile.hip)
 #include "png_read.hpp"         // the PNG chunk walk and the device decode of a walked file (png_read.cpp, png_decode.hip)
 #include "webp_read.hpp"        // the RIFF walk, the prepare and the device decode of a lossless WebP (webp_read.cpp, webp_decode.hip)
 #include "layout.hpp"           // imageflow_riapi's constraint layout (constrain / watermark)
@@ -54,6 +55,7 @@ namespace {
 enum Cat { kOk = 0, kOutOfMemory = 1, kArgumentInvalid = 2, kInvalidJson = 3, kImageMalformed = 4, kImageTypeNotSupported = 5,
            kNodeArgumentInvalid = 6, kGraphInvalid = 7, kActionNotSupported = 8, kIoError = 16, kInternalError = 18,
            kOperationCancelled = 21 };
+// (ErrorKind::ColorProfileError, a profile the CMS cannot read, is of category ImageMalformed: errors.rs:241 -- code 4, HTTP 400, exit 65)
 int http_code(int c) {
     switch (c) {
     case kOk: return 200;
@@ -81,7 +83,7 @@ struct FlowErr {
 };
 [[noreturn]] void raise(int cat, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 void raise(int cat, const char* fmt, ...) {
-    char buf[512];
+    char buf[768];
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(buf, sizeof buf, fmt, ap);
@@ -488,6 +490,8 @@ struct Io {
     uint32_t told_w = 0, told_h = 0;
     bool told_spatial = false, told_gamma = false;
     bool told_discard_profile = false;           // DecoderCommand::DiscardColorProfile (mozjpeg_decoder.rs:88-91)
+    bool told_ignore_profile_errors = false;     // DecoderCommand::IgnoreColorProfileErrors (:93-96): a profile that fails leaves the samples as they are
+    bool told_convert_profile = false;           // EXTENSION "convert_color_profile": this input is converted to sRGB (Job::color_plan_for)
     // DecoderCommand::WebPDecoderHints (codecs/webp.rs:181-188): the size libwebp's rescaler would decode to; acted on by a WebP input only
     bool told_webp = false;
     uint32_t told_webp_w = 0, told_webp_h = 0;
@@ -525,6 +529,7 @@ struct imageflow_context {
     std::atomic<int64_t> device_coded_files{0};          // JPEG outputs whose entropy coding ran on the device (diagnostic)
     std::atomic<int64_t> coalesced_decodes{0};           // decodes of this context that shared their device call with another thread's job
     std::atomic<int> device{-1};                         // device ordinal its jobs run on; -1: the calling thread's current device
+    std::atomic<bool> color_management{false};           // EXTENSION ifhip_shim_context_set_color_management: every input is converted to sRGB
     bool cancellation_requested() {
         if (cancel.load(std::memory_order_relaxed)) return true;
         if (poll_countdown.load(std::memory_order_relaxed) == INT64_MAX) return false;
@@ -945,6 +950,42 @@ struct Job {
         return b;
     }
 
+    // ---- colour management: codecs/cms.rs::transform_to_srgb, EXTENSION -- off unless the caller switches it on ------------
+    // A source that is not sRGB (kind 2 of the three classifiers) and was not told discard_color_profile.  Off (the default):
+    // the refusal, as ever.  On (ifhip_shim_context_set_color_management, or the decoder command "convert_color_profile"):
+    // the plan of csrc/color_profile.cpp from the ICC bytes (`icc` non-null) or from gAMA + cHRM (`gama_chrm`: gAMA, then the
+    // eight cHRM values, x 100000), true = apply it to the decoded frame.  A profile of a kind that is not converted here keeps
+    // the refusal; a malformed one is ErrorKind::ColorProfileError (category ImageMalformed, errors.rs:241), which
+    // ignore_color_profile_errors swallows as the reference does for every failure of its transform
+    // (mozjpeg_decoder.rs:409-415, libpng_decoder.rs:376-382): the samples stay as they are.
+    bool color_plan_for(int32_t io_id, const Io& in, const char* what, const char* reference_line, const uint8_t* icc, size_t icc_len,
+                        const uint32_t* gama_chrm, ifhip_color_plan* plan) {
+        if (!c->color_management.load(std::memory_order_relaxed) && !in.told_convert_profile)
+            raise(kActionNotSupported, "ActionNotSupported: io_id %d %s; this build has no colour management%s%s%s.  Tell the decoder "
+                  "\"discard_color_profile\" to decode the samples as they are, or keep the file on the reference.  (Conversion to sRGB on the device is an "
+                  "extension that is off by default: ifhip_shim_context_set_color_management, or the decoder command \"convert_color_profile\", switches it on.)",
+                  io_id, what, reference_line ? " (the reference converts such frames to sRGB, " : "", reference_line ? reference_line : "", reference_line ? ")" : "");
+        ifhip::ColorPlanResult r;
+        if (icc) r = ifhip::color_plan_from_icc(icc, icc_len, plan);
+        else {
+            double xy[8];
+            for (int k = 0; k < 8; ++k) xy[k] = gama_chrm[1 + k] / 100000.0;
+            r = ifhip::color_plan_from_gamma_primaries(gama_chrm[0] / 100000.0, xy, plan);
+        }
+        if (r.status == IFHIP_COLOR_PLANNED) return true;
+        if (r.status == IFHIP_COLOR_NOT_CONVERTIBLE)
+            raise(kActionNotSupported, "ActionNotSupported: io_id %d %s, and the profile is %s: %s (matrix/TRC RGB profiles and gAMA + cHRM are converted; GRAY, "
+                  "CMYK, Lab and LUT-based profiles and curves that lift black are not).  Tell the decoder \"discard_color_profile\" to decode the samples as they are, or keep the file on "
+                  "the reference.", io_id, what, ifhip::color_plan_status_text(r.status), r.reason);
+        if (in.told_ignore_profile_errors) return false;
+        raise(kImageMalformed, "ColorProfileError: the colour profile of io_id %d is %s: %s.  Tell the decoder \"ignore_color_profile_errors\" to decode the "
+              "samples as they are.", io_id, ifhip::color_plan_status_text(r.status), r.reason);
+    }
+    // in place, on the job's stream, behind the decode that filled the frame; the plan is copied by the launch
+    void convert_to_srgb(const FramePtr& f, const ifhip_color_plan& plan) {
+        check(ifhip_color_transform_batch_device(dev(f), f->bytes(), 1, f->w, f->h, f->stride, &plan, t_job_stream));
+    }
+
     // LibPngDecoder::read_frame (codecs/libpng_decoder.rs:82-104 -> c_components/lib/codec_png_wrapper.c:131-246) on the device:
     // the host walks the chunks, the IDAT stream is inflated, un-filtered and expanded to BGRA by csrc/png_decode.hip.  The
     // JPEG downscale hints do not apply (tell_decoder accepts and ignores them, libpng_decoder.rs:58-80).
@@ -952,13 +993,18 @@ struct Job {
         ifhip::PngParsed P;                                                           // ONE walk over the chunks: the facts and where the IDAT payloads lie
         check(ifhip::parse_png(in.in, in.in_len, &P, true));                          // a bad CRC, a malformed critical chunk: ImageMalformed
         check_size(sec.max_decode_size, "max_decode_size", P.w, P.h);                 // on the header, before anything is staged
-        // The colour policy of the JPEG path below (DESIGN 8 "Colour management: none"): the reference transforms a frame whose
-        // iCCP, or gAMA + cHRM, is not sRGB (libpng_decoder.rs:340-383); this build cannot, so it refuses -- never other colours.
-        if (!in.told_discard_profile && P.color_kind == 2)
-            raise(kActionNotSupported, "ActionNotSupported: io_id %d %s; this build has no colour "
-                  "management (the reference converts such frames to sRGB, codecs/libpng_decoder.rs:376).  Tell the decoder "
-                  "\"discard_color_profile\" to decode the samples as they are, or keep the file on the reference.", io_id,
-                  P.has_iccp ? "carries an embedded ICC profile that is not sRGB" : "carries gAMA and cHRM chunks that do not describe sRGB");
+        // The colour policy of the JPEG path below (DESIGN 8 "Colour management"): the reference transforms a frame whose iCCP,
+        // or gAMA + cHRM, is not sRGB (libpng_decoder.rs:340-383); so does this build once switched on, else it refuses -- never
+        // other colours.
+        ifhip_color_plan color_plan;
+        bool convert = false;
+        if (!in.told_discard_profile && P.color_kind == 2) {
+            static const uint8_t kNoProfile = 0;                                      // an iCCP that did not inflate: zero bytes of profile, malformed
+            uint32_t gama_chrm[9] = {P.gama};
+            std::memcpy(gama_chrm + 1, P.chrm, sizeof P.chrm);
+            convert = color_plan_for(io_id, in, P.has_iccp ? "carries an embedded ICC profile that is not sRGB" : "carries gAMA and cHRM chunks that do not describe sRGB",
+                                     "codecs/libpng_decoder.rs:376", P.has_iccp ? (P.icc.empty() ? &kNoProfile : P.icc.data()) : nullptr, P.icc.size(), gama_chrm, &color_plan);
+        }
         if (P.inflated > 0x7FFF0000ull) raise(kImageMalformed, "ImageMalformed: LibPNG error: the image data of io_id %d would inflate beyond 2^31 bytes", io_id);
         FramePtr f = new_frame(P.w, P.h, P.alpha_used, 0, true);                      // (max_frame_size inside)
         uint32_t* d_status = nullptr;
@@ -972,6 +1018,7 @@ struct Job {
         hip_check(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, t_job_stream), "download(status)");
         hip_check(static_cast<hipError_t>(ifhip::wait_stream(t_job_stream)), "decode(png)");
         if (status) raise(kImageMalformed, "ImageMalformed: LibPNG error: %s (io_id %d, status %u)", ifhip::png_status_text(status), io_id, status);
+        if (convert) convert_to_srgb(f, color_plan);
         decodes.push_back({io_id, P.w, P.h, "image/png", "png"});
         return f;
     }
@@ -984,9 +1031,9 @@ struct Job {
         ifhip::WebpParsed P;
         walk_webp(in, &P);
         check_size(sec.max_decode_size, "max_decode_size", P.w, P.h);                 // on the header, before anything is staged
-        if (!in.told_discard_profile && P.color_kind == 2)
-            raise(kActionNotSupported, "ActionNotSupported: io_id %d carries an embedded ICC profile that is not sRGB; this build has no colour "
-                  "management.  Tell the decoder \"discard_color_profile\" to decode the samples as they are, or keep the file on the reference.", io_id);
+        ifhip_color_plan color_plan;
+        const bool convert = !in.told_discard_profile && P.color_kind == 2 &&
+                             color_plan_for(io_id, in, "carries an embedded ICC profile that is not sRGB", nullptr, P.icc, P.icc_len, nullptr, &color_plan);
         if (in.told_webp && (in.told_webp_w != P.w || in.told_webp_h != P.h))
             raise(kActionNotSupported, "ActionNotSupported: webp_decoder_hints %ux%u for io_id %d (%ux%u): libwebp's decode-time rescaler is not built "
                   "(the reference shrinks during the decode, codecs/webp.rs:181-188); decode at full size and resample", in.told_webp_w, in.told_webp_h, io_id, P.w, P.h);
@@ -1005,6 +1052,7 @@ struct Job {
         hip_check(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, t_job_stream), "download(status)");
         hip_check(static_cast<hipError_t>(ifhip::wait_stream(t_job_stream)), "decode(webp)");
         if (status) raise(kImageMalformed, "ImageMalformed: libwebp decoding error %s (io_id %d, status %u)", ifhip::webp_status_text(status), io_id, status);
+        if (convert) convert_to_srgb(f, color_plan);
         decodes.push_back({io_id, P.w, P.h, "image/webp", "webp"});
         return f;
     }
@@ -1035,15 +1083,17 @@ struct Job {
             image_size(io_id, &hw, &hh);
             check_size(sec.max_decode_size, "max_decode_size", hw, hh);
         }
+        ifhip_color_plan color_plan;
+        bool convert = false;
         {   // MzDec::read_frame transforms the frame to sRGB whenever the file carries an ICC profile (mozjpeg_decoder.rs:370-420)
-            // unless the decoder was told discard_color_profile (:88-91).  Colour management is not part of this library: a
-            // profile that is not sRGB itself would come out with other colours than the reference's, so the job is refused --
-            // loudly -- instead (a profile that IS sRGB: the reference's transform is the identity up to its rounding).
+            // unless the decoder was told discard_color_profile (:88-91).  A profile that is not sRGB itself would come out with
+            // other colours than the reference's: the job is refused -- loudly -- unless colour management is switched on, and
+            // then the frame is converted behind its decode (a profile that IS sRGB: the reference's transform is the identity up
+            // to its rounding).
             int kind = 0;
-            if (!in.told_discard_profile && ifhip_jpeg_icc_profile_kind(in.in, in.in_len, &kind) == IFHIP_OK && kind == 2)
-                raise(kActionNotSupported, "ActionNotSupported: io_id %d carries an embedded ICC profile that is not sRGB; this build has no colour "
-                      "management (the reference converts such frames to sRGB, codecs/mozjpeg_decoder.rs:409).  Tell the decoder "
-                      "\"discard_color_profile\" to decode the samples as they are, or keep the file on the reference.", io_id);
+            std::vector<uint8_t> icc;
+            if (!in.told_discard_profile && ifhip::jpeg_icc_profile(in.in, in.in_len, &kind, &icc) == IFHIP_OK && kind == 2)
+                convert = color_plan_for(io_id, in, "carries an embedded ICC profile that is not sRGB", "codecs/mozjpeg_decoder.rs:409", icc.data(), icc.size(), nullptr, &color_plan);
         }
         // the entropy stage: this file, together with whatever other threads' jobs want decoded right now (DecodeCoalescer)
         DecodeRequest rq;
@@ -1096,6 +1146,9 @@ struct Job {
         f->w = ow; f->h = oh; f->stride = ifhip_stride_for_width(ow); f->alpha = false;
         f->pending = std::move(pend);
         if (!lazy_decode) (void)dev(f);                                               // several consumers: one bitmap for all of them
+        // a frame to convert never takes the fused decode + resample call, which forms no BGRA frame: its pixel stage runs now
+        // (dev), then the conversion; whoever resamples it -- a node, a command_string, a watermark -- finds an ordinary frame
+        if (convert) convert_to_srgb(f, color_plan);
         {   // Context::get_image_decodes reports get_unscaled_rotated_image_info (context.rs:519-538)
             const int flag = exif_flag(in);
             const bool swap = flag >= 5 && flag <= 8;
@@ -1839,6 +1892,10 @@ struct Job {
                     for (const JVal& cmd : cmds->a) {
                         if (cmd.t == JVal::Str && cmd.s == "discard_color_profile") {
                             input(static_cast<int32_t>(want_int(p, "io_id", "decode"))).told_discard_profile = true;
+                        } else if (cmd.t == JVal::Str && cmd.s == "ignore_color_profile_errors") {
+                            input(static_cast<int32_t>(want_int(p, "io_id", "decode"))).told_ignore_profile_errors = true;
+                        } else if (cmd.t == JVal::Str && cmd.s == "convert_color_profile") {  // EXTENSION: colour management for this input
+                            input(static_cast<int32_t>(want_int(p, "io_id", "decode"))).told_convert_profile = true;
                         } else if (const JVal* j = cmd.get("webp_decoder_hints")) {          // s::WebPDecoderHints {width, height}
                             tell_webp_hint(input(static_cast<int32_t>(want_int(p, "io_id", "decode"))), *j);
                         } else if (const JVal* j = cmd.get("jpeg_downscale_hints")) {        // s::JpegIDCTDownscaleHints
@@ -2311,6 +2368,13 @@ bool ifhip_shim_context_set_device(struct imageflow_context* c, int ordinal) {
     c->device.store(ordinal, std::memory_order_relaxed);
     return true;
 }
+// EXTENSION: colour management for every input of the context's jobs (see Job::color_plan_for); off by default.  Jobs written
+// for the reference run unmodified with it.  discard_color_profile still wins.
+bool ifhip_shim_context_set_color_management(struct imageflow_context* c, int on) {
+    CTX_OR_ABORT(c);
+    c->color_management.store(on != 0, std::memory_order_relaxed);
+    return true;
+}
 int ifhip_shim_context_device(struct imageflow_context* c) {
     CTX_OR_ABORT(c);
     return c->device.load(std::memory_order_relaxed);
@@ -2441,10 +2505,14 @@ const struct imageflow_json_response* imageflow_context_send_json(struct imagefl
                 b = j.get("gamma_correct_for_srgb_during_spatial_luma_scaling");
                 in.told_gamma = b && b->t == JVal::Bool && b->b;
             } else if (cmd->t == JVal::Str && cmd->s == "discard_color_profile") {
-                in.told_discard_profile = true;                                      // the samples as they are: what this library does anyway
+                in.told_discard_profile = true;                                      // the samples as they are; wins over colour management
             } else if (cmd->t == JVal::Obj && cmd->get("webp_decoder_hints")) {      // s::DecoderCommand::WebPDecoderHints: kept with the input
                 tell_webp_hint(in, *cmd->get("webp_decoder_hints"));
-            } else if (!(cmd->t == JVal::Str && cmd->s == "ignore_color_profile_errors")) {   // profile errors: there is no CMS to fail
+            } else if (cmd->t == JVal::Str && cmd->s == "ignore_color_profile_errors") {
+                in.told_ignore_profile_errors = true;                                // acted on where colour management is switched on
+            } else if (cmd->t == JVal::Str && cmd->s == "convert_color_profile") {   // EXTENSION: colour management for this input
+                in.told_convert_profile = true;
+            } else {
                 raise(kInvalidJson, "InvalidJson: unknown decoder command");
             }
             return respond(c, 200, "{\n  \"code\": 200,\n  \"success\": true,\n  \"message\": \"OK\",\n  \"data\": {}\n}");                 // TellDecoderV1Response {} (v1.rs:177)

@@ -43,6 +43,8 @@ int require_gfx950(int* device_out);                  // IFHIP_OK and the curren
 
 // An ICC profile that describes sRGB itself (csrc/jpeg_entropy.hip; the JPEG APP2 and the PNG iCCP readers share it)
 bool icc_describes_srgb(const uint8_t* profile, size_t profile_bytes);
+// ifhip_jpeg_icc_profile_kind with the profile it judged: the APP2 chunks put together (empty for kind 0)
+int jpeg_icc_profile(const uint8_t* jpeg, size_t len, int* kind, std::vector<uint8_t>* profile);
 
 // Development switches (tests and tools/ only).  The library never reads the environment: a switch exists only after
 // ifhip_debug_set(key, value) (include/imageflow_hip.h); unset -> nullptr.  One relaxed atomic load when none is set.

@@ -1252,8 +1252,17 @@ int ifhip_jpeg_exif_orientation(const uint8_t* d, size_t len, int* flag) {
 // mozjpeg_decoder_helpers.rs:42-83: the frame is decoded without a transform) and kind 0 here; so is a GRAY profile on a
 // colour frame (mozjpeg_decoder.rs:391-395 -> SourceProfile::Srgb).
 int ifhip_jpeg_icc_profile_kind(const uint8_t* d, size_t len, int* kind) {
+    std::vector<uint8_t> icc;
+    return ifhip::jpeg_icc_profile(d, len, kind, &icc);
+}
+
+}  // extern "C"
+
+int ifhip::jpeg_icc_profile(const uint8_t* d, size_t len, int* kind, std::vector<uint8_t>* profile) {
     if (!kind) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null out-pointer");
     *kind = 0;
+    std::vector<uint8_t>& icc = *profile;
+    icc.clear();
     if (!d || len < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: not a JPEG (no SOI)");
     std::vector<std::pair<const uint8_t*, size_t>> chunk(256, {nullptr, 0});
     uint32_t count = 0, seen = 0;
@@ -1281,15 +1290,12 @@ int ifhip_jpeg_icc_profile_kind(const uint8_t* d, size_t len, int* kind) {
         ++seen;
     }
     if (!seen || broken || seen != count) return IFHIP_OK;              // no profile, or a chunk set the reference drops
-    std::vector<uint8_t> icc;
     for (uint32_t k = 1; k <= count; ++k) icc.insert(icc.end(), chunk[k].first, chunk[k].first + chunk[k].second);
     if (icc.empty()) return IFHIP_OK;                                    // only empty markers: None
-    if (icc.size() >= 20 && std::memcmp(&icc[16], "GRAY", 4) == 0 && frame_components != 1) return IFHIP_OK;   // -> SourceProfile::Srgb
+    if (icc.size() >= 20 && std::memcmp(&icc[16], "GRAY", 4) == 0 && frame_components != 1) { icc.clear(); return IFHIP_OK; }   // -> SourceProfile::Srgb
     *kind = icc_describes_srgb(icc.data(), icc.size()) ? 1 : 2;
     return IFHIP_OK;
 }
-
-}  // extern "C"  (reopened below)
 
 // One file, prepared on the host by whoever owns it: parsed, its scan un-stuffed, cut at the restart markers and packed as
 // big-endian words (every segment padded to 1 024 bits) in PINNED memory, its decode tables derived.  A batch is then

@@ -38,7 +38,7 @@ int malformed(const char* what) { return fail(IFHIP_INVALID_ARGUMENT, "ImageMalf
 
 // iCCP: name (1..79 bytes), 0, compression method 0, a zlib stream.  The profile's size is in its own first four bytes.
 // -> 1: the profile describes sRGB, 2: any other (also one that does not inflate)
-int classify_iccp(const uint8_t* q, size_t n) {
+int classify_iccp(const uint8_t* q, size_t n, std::vector<uint8_t>* profile) {
     size_t k = 0;
     while (k < n && k < 80u && q[k]) ++k;
     if (k == 0u || k >= n || q[k] != 0 || k + 2u > n || q[k + 1u] != 0) return 2;
@@ -58,7 +58,8 @@ int classify_iccp(const uint8_t* q, size_t n) {
     std::vector<PngQuad> out((size + 15u) / 16u);
     r = png_inflate(x, *S, reinterpret_cast<const uint8_t*>(in.data()), static_cast<uint32_t>(zn), reinterpret_cast<uint8_t*>(out.data()), size);
     if (r.status != kPngDecOk) return 2;
-    return icc_describes_srgb(reinterpret_cast<const uint8_t*>(out.data()), size) ? 1 : 2;
+    profile->assign(reinterpret_cast<const uint8_t*>(out.data()), reinterpret_cast<const uint8_t*>(out.data()) + size);
+    return icc_describes_srgb(profile->data(), size) ? 1 : 2;
 }
 
 }  // namespace
@@ -68,6 +69,7 @@ int parse_png(const uint8_t* d, size_t len, PngParsed* out, bool gather) {
     if (!d || len < 8u || std::memcmp(d, sig, 8) != 0) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: not a PNG (no signature)");
     PngParsed& P = *out;
     P.idat.clear();
+    P.icc.clear();
     for (uint32_t i = 0; i < 256u; ++i) P.palette[i] = 0xFF000000u;
     size_t pos = 8, idat_total = 0;
     bool have_ihdr = false, have_plte = false, have_idat = false, have_iend = false, have_srgb = false, have_gama = false, have_chrm = false, have_iccp = false;
@@ -120,7 +122,7 @@ int parse_png(const uint8_t* d, size_t len, PngParsed* out, bool gather) {
         } else if (type == fourcc('c', 'H', 'R', 'M')) {
             if (n == 32u) { have_chrm = true; for (int k = 0; k < 8; ++k) chrm[k] = be32(q + 4 * k); }
         } else if (type == fourcc('i', 'C', 'C', 'P')) {
-            if (!have_iccp) { have_iccp = true; iccp_kind = classify_iccp(q, n); }
+            if (!have_iccp) { have_iccp = true; iccp_kind = classify_iccp(q, n, &P.icc); }
         } else if (!(type & 0x20000000u)) {                                          // bit 5 of the first letter clear: critical
             return malformed("unhandled critical chunk");
         }
@@ -141,6 +143,7 @@ int parse_png(const uint8_t* d, size_t len, PngParsed* out, bool gather) {
     // which are sRGB when they carry the values the specification gives for it; gAMA alone is ignored (honor_gama_only = false)
     static const uint32_t srgb_chrm[8] = {31270u, 32900u, 64000u, 33000u, 30000u, 60000u, 15000u, 6000u};
     P.has_iccp = have_iccp;
+    P.gama = gama; std::memcpy(P.chrm, chrm, sizeof chrm);
     if (have_iccp) P.color_kind = iccp_kind;
     else if (have_srgb) P.color_kind = 1;
     else if (have_gama && have_chrm) P.color_kind = gama == 45455u && std::memcmp(chrm, srgb_chrm, sizeof chrm) == 0 ? 1 : 2;

@@ -13,6 +13,8 @@ struct PngParsed {
     bool alpha_used = false, uses_palette = false;
     int color_kind = 0;                  // 0: no colour chunks (or gAMA alone); 1: declared sRGB; 2: a colour space that is not sRGB
     bool has_iccp = false;               // the verdict comes from an iCCP profile (else from sRGB / gAMA + cHRM)
+    std::vector<uint8_t> icc;            // the iCCP profile, inflated (empty where the chunk did not inflate)
+    uint32_t gama = 0, chrm[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // gAMA and cHRM as the chunks hold them (x 100000): white, red, green, blue x, y
     uint32_t palette[256];               // BGRA dwords, tRNS applied; beyond PLTE opaque black
     uint32_t has_trns = 0, key[3] = {0, 0, 0};   // the tRNS key of gray / RGB files, masked to the file's depth
     uint64_t inflated = 0;               // the expected size of the inflated stream

@@ -80,7 +80,7 @@ int parse_webp(const uint8_t* d, size_t len, WebpParsed* out) {
     else if (!have_image) return malformed("no image chunk");
     else if (vp8x && (canvas_w != P.w || canvas_h != P.h)) return malformed("the VP8X canvas is not the image's size");
     if (lossy && !P.animated && vp8x && (flags & 0x10u)) P.has_alpha = true;
-    if (vp8x && (flags & 0x20u) && iccp) P.color_kind = icc_describes_srgb(iccp, iccp_len) ? 1 : 2;
+    if (vp8x && (flags & 0x20u) && iccp) { P.color_kind = icc_describes_srgb(iccp, iccp_len) ? 1 : 2; P.icc = iccp; P.icc_len = iccp_len; }
     return IFHIP_OK;
 }
 

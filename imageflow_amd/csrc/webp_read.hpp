@@ -17,6 +17,8 @@ struct WebpParsed {
     int color_kind = 0;                  // 0: no ICCP; 1: an ICCP profile that describes sRGB; 2: any other profile
     const uint8_t* payload = nullptr;    // the VP8L chunk's bytes, inside the caller's file
     size_t payload_len = 0;
+    const uint8_t* icc = nullptr;        // the ICCP chunk's bytes behind color_kind 1 or 2, inside the caller's file
+    size_t icc_len = 0;
 };
 // IFHIP_OK, or IFHIP_INVALID_ARGUMENT with an "ImageMalformed: libwebp decoding error ..." message.  A lossy or an animated
 // file parses (lossless = false / animated = true): what to answer is the caller's.

@@ -117,6 +117,15 @@ IMAGEFLOW_SHIM_API int64_t ifhip_shim_coalesced_decodes(struct imageflow_context
 IMAGEFLOW_SHIM_API void ifhip_shim_spread_contexts(int enable);
 IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_device(struct imageflow_context *context, int ordinal);
 IMAGEFLOW_SHIM_API int ifhip_shim_context_device(struct imageflow_context *context);
+/* EXTENSION.  Colour management, off by default: with on != 0 every input of the context's jobs whose ICC profile (JPEG
+ * APP2, PNG iCCP, WebP ICCP) or PNG gAMA + cHRM is not sRGB is converted to sRGB on the device right behind its decode, as
+ * the reference does in codecs/cms.rs::transform_to_srgb (mozjpeg_decoder.rs:409, libpng_decoder.rs:376, webp.rs), pinned
+ * to its lcms2 back end -- instead of the ActionNotSupported refusal such inputs get otherwise.  Jobs written for the
+ * reference run unmodified.  The decoder command "convert_color_profile" (decode.commands, v1/tell_decoder) does the same
+ * for one input; "discard_color_profile" wins over both.  Converted: RGB matrix/TRC profiles (v2 / v4, XYZ PCS) and gAMA +
+ * cHRM.  Still refused, naming the case: GRAY / CMYK spaces, a Lab PCS, LUT-based profiles.  A malformed profile is a
+ * ColorProfileError (ImageMalformed) unless the decoder was told "ignore_color_profile_errors".  Returns true. */
+IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_color_management(struct imageflow_context *context, int on);
 
 /* The layout arithmetic behind the `constrain` and `watermark` nodes, callable on its own (no GPU, no context):
  * imageflow_riapi::ir4::process_constraint (imageflow_riapi/src/ir4/layout.rs:334-412) for a source of source_w x source_h

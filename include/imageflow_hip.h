@@ -280,8 +280,9 @@ IFHIP_API int ifhip_jpeg_parse_headers(const uint8_t* jpeg, size_t len, uint32_t
 IFHIP_API int ifhip_jpeg_exif_orientation(const uint8_t* jpeg, size_t len, int* flag);
 /* The embedded colour profile as MozJpegDecoder sees it (APP2 "ICC_PROFILE" chunks, codecs/mozjpeg_decoder.rs:370-420):
  * the reference transforms a frame to sRGB whenever the file carries ANY profile (:409, SourceProfile::is_srgb is true
- * only for "no profile") unless the job told the decoder discard_color_profile (:88-95).  This library has no colour
- * management (out of scope), so callers must know when a file needs it.  *kind = 0: no profile;
+ * only for "no profile") unless the job told the decoder discard_color_profile (:88-95).  This library converts only
+ * where the caller asks for it (ifhip_color_plan_from_icc / ifhip_color_transform below; the shim's colour-management
+ * switch), so callers must know when a file needs it.  *kind = 0: no profile;
  * (also: a chunk set libjpeg's reassembly rule rejects -- mozjpeg_decoder_helpers.rs:42-83 returns None -- and a GRAY
  * profile on a colour frame, which the reference maps to SourceProfile::Srgb, mozjpeg_decoder.rs:391-395);
  * 1: a profile that describes sRGB itself (RGB matrix profile, sRGB primaries within 0.003 after D50 adaptation, the sRGB
@@ -545,8 +546,9 @@ IFHIP_API int ifhip_encode_preset_coder(const char* preset_json, size_t len);
  * frame marked bgr_32.  uses_palette: colour type bit 0 (:270).  color_kind, in the convention of
  * ifhip_jpeg_icc_profile_kind: 0 no colour chunks, or gAMA alone (honor_gama_only = false, libpng_decoder.rs:234); 1 sRGB
  * declared (an sRGB chunk, an iCCP profile that describes sRGB, gAMA + cHRM with the specification's sRGB values); 2 any
- * other colour space (another iCCP profile, other gAMA + cHRM) -- the reference converts such frames (:340-383), this
- * library has no colour management, so callers must refuse or be told discard_color_profile.
+ * other colour space (another iCCP profile, other gAMA + cHRM) -- the reference converts such frames (:340-383); this
+ * decoder never does, so callers must refuse, be told discard_color_profile, or convert the decoded frame themselves
+ * (ifhip_color_plan_from_icc / _from_gamma_primaries + ifhip_color_transform_batch_device, as the shim does once switched on).
  *
  * Status word of a file (d_status[i]): 0, or why its stream is no image -- libpng's errors. */
 #define IFHIP_PNG_DEC_TRUNCATED 1        /* the zlib stream ends early                                        */
@@ -594,7 +596,8 @@ IFHIP_API int ifhip_png_decode(const uint8_t* png, size_t len, uint8_t* bgra, ui
  * has_alpha (-> frame_decodes_into bgra_32 / bgr_32, webp.rs:144-148,204) is what WebPGetFeatures reports: for a lossless
  * file the VP8L header's bit, whatever a VP8X chunk's ALPHA flag says.  color_kind, in the convention of
  * ifhip_jpeg_icc_profile_kind: 0 no ICCP chunk (or the VP8X ICC flag clear), 1 a profile that describes sRGB, 2 any other --
- * this library has no colour management, so callers must refuse or be told discard_color_profile.
+ * this decoder never converts, so callers must refuse, be told discard_color_profile, or convert the decoded frame themselves
+ * (ifhip_color_plan_from_icc + ifhip_color_transform_batch_device, as the shim does once switched on).
  *
  * Status word of a file (d_status[i]): 0, or why its stream is no image. */
 #define IFHIP_WEBP_DEC_TRUNCATED 1       /* a bit was used that the stream does not have                       */
@@ -748,6 +751,44 @@ IFHIP_API int ifhip_white_balance(uint8_t* bgra, uint32_t w, uint32_t h, uint32_
 IFHIP_API int ifhip_white_balance_batch_device(uint8_t* d_bgra, size_t image_bytes, uint32_t n_images, uint32_t w,
                                                uint32_t h, uint32_t stride, float threshold, uint64_t* d_histograms,
                                                void* hip_stream);
+
+/* ---- colour management: matrix/TRC sources to sRGB ------------------------------------------------------- */
+/* What a conversion to sRGB needs (codecs/cms.rs::transform_to_srgb for SourceProfile::IccProfile and ::GammaPrimaries,
+ * pinned to the reference's lcms2 back end, codecs/lcms2_transform.rs): the source's tone curves as linear light per byte
+ * value, R then G then B, and the row-major matrix from source linear RGB to sRGB linear RGB (row = output R, G, B). */
+typedef struct ifhip_color_plan {
+    float linear[3][256];
+    float matrix[9];
+} ifhip_color_plan;
+typedef enum ifhip_color_plan_status {
+    IFHIP_COLOR_PLANNED = 0,          /* *out is filled */
+    IFHIP_COLOR_NOT_CONVERTIBLE = 1,  /* a sound profile of a kind this library does not convert: GRAY / CMYK space, Lab PCS, LUT-based */
+    IFHIP_COLOR_MALFORMED = 2         /* the bytes are no usable profile (the reference: ErrorKind::ColorProfileError) */
+} ifhip_color_plan_status;
+/* "planned" / "not convertible here" / "malformed" */
+IFHIP_API const char* ifhip_color_plan_status_text(int status);
+/* Replaces lcms2_transform.rs:219-242 (Profile::new_icc + Transform::new, Intent::Perceptual) for RGB matrix/TRC profiles,
+ * v2 or v4, XYZ PCS: rXYZ / gXYZ / bXYZ as stored (lcms2's matrix-shaper does not consult chad or wtpt), rTRC / gTRC / bTRC
+ * as curv (0 entries: identity, 1: a u8.8 gamma, n: a 16-bit table read with linear interpolation) or para (types 0..4);
+ * matrix = inv(the colourants of lcms2's built-in sRGB profile, s15.16) x the source's, in f64, rounded to f32.  A profile
+ * with an A2B0 / D2B0 tag is LUT-based for lcms2 even when matrix tags are present, and is not converted here.  Every tag is
+ * bounds-checked against `len`.  Returns an ifhip_color_plan_status; other than PLANNED, ifhip_last_error_message() names the
+ * case.  Host only. */
+IFHIP_API int ifhip_color_plan_from_icc(const uint8_t* icc, size_t len, ifhip_color_plan* out);
+/* Replaces lcms2_transform.rs:245-283 (cmsCreateRGBProfile from PNG gAMA + cHRM, SourceProfile::GammaPrimaries): the curve
+ * x^(1/gamma), the primaries' RGB -> XYZ matrix adapted from the stated white to D50 with Bradford.  xy = white x, y, red
+ * x, y, green x, y, blue x, y.  Values the reference rejects or takes for sRGB (source_profile.rs:225-242: a gamma that is
+ * not positive and finite, a chromaticity that is not finite or has y = 0; a neutral gamma with sRGB's primaries) give the
+ * plan that changes nothing (sRGB's curve, the identity matrix).  Primaries on one line are MALFORMED.  Host only. */
+IFHIP_API int ifhip_color_plan_from_gamma_primaries(double gamma, const double xy[8], ifhip_color_plan* out);
+/* codecs/cms.rs::transform_to_srgb on the device, in place: per pixel three table reads, the matrix in f32 (per row
+ * fma(m2, b, fma(m1, g, m0 * r))), a clamp to [0, 1] with NaN -> 0 and LINEAR_TO_SRGB_LUT[(v * 16383) as usize]; the fourth
+ * byte keeps its value.  Row padding is neither read as pixels nor written.  One launch on hip_stream, no host wait; the plan
+ * is read during the call.  The host form stages one bitmap. */
+IFHIP_API int ifhip_color_transform(uint8_t* bgra, uint32_t w, uint32_t h, uint32_t stride, const ifhip_color_plan* plan);
+IFHIP_API int ifhip_color_transform_batch_device(uint8_t* d_bgra, size_t image_bytes, uint32_t n_images, uint32_t w,
+                                                 uint32_t h, uint32_t stride, const ifhip_color_plan* plan,
+                                                 void* hip_stream);
 
 /* ---- measurement helpers (bench.py) -------------------------------------------------------------------- */
 /* Runs `launches` back-to-back launches of the batch op on `hip_stream` bracketed by hipEvents on that stream
