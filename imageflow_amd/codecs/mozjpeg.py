@@ -103,7 +103,8 @@ ENC_BAD_COEFFICIENT, ENC_SCAN_OVERFLOW, ENC_FILE_OVERFLOW = 1, 2, 4     # includ
 class JpegEntropyStage:
     """ifhip_jpeg_enc_stage: the device entropy coder (csrc/jpeg_encode.hip) -- what compressor.write_scanlines / finish run
     behind the pixel stage (mozjpeg.rs:155-175) for a baseline file with the Annex K tables: coefficient planes in HBM in,
-    complete files in HBM out."""
+    complete files in HBM out.  progressive= / optimize_coding= select the preset's two options (csrc/jpeg_encode_progressive.hip);
+    their scratch is allocated by the first call that asks for them."""
 
     def __init__(self, width, height, h_samp, v_samp, blocks_w, blocks_h, max_images, device="cuda:0", scan_capacity=0):
         L = _bind()
@@ -115,6 +116,10 @@ class JpegEntropyStage:
         L.ifhip_jpeg_enc_stage_max_file_bytes.restype = C.c_size_t
         L.ifhip_jpeg_encode_batch_device.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p,
                                                      C.c_void_p]
+        L.ifhip_jpeg_enc_stage_max_file_bytes_for.argtypes = [C.c_void_p, C.c_int]
+        L.ifhip_jpeg_enc_stage_max_file_bytes_for.restype = C.c_size_t
+        L.ifhip_jpeg_encode_flags_batch_device.argtypes = [C.c_void_p] * 4 + [C.c_int, C.c_int, C.c_uint32, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                           C.c_void_p, C.c_void_p]
         self.device = torch.device(device)
         self.ncomp = len(list(blocks_w))
         self.max_images = max_images
@@ -127,13 +132,22 @@ class JpegEntropyStage:
                                                         bw.ctypes.data, bh.ctypes.data, max_images, scan_capacity))
         self.max_file_bytes = int(L.ifhip_jpeg_enc_stage_max_file_bytes(self._h))
 
-    def encode_device(self, coef, quality, file_pitch=None, files=None):
+    def max_file_bytes_for(self, progressive=False, optimize_coding=False):
+        """A file_pitch with which no file of these options overflows (ifhip_jpeg_enc_stage_max_file_bytes_for)."""
+        flags = (JPEG_PROGRESSIVE if progressive else 0) | (JPEG_OPTIMIZE_HUFFMAN if optimize_coding else 0)
+        bound = int(_bind().ifhip_jpeg_enc_stage_max_file_bytes_for(self._h, flags))
+        if bound == 0:
+            raise ValueError("the device coder refuses this geometry for these options (bound the streams with scan_capacity)")
+        return bound
+
+    def encode_device(self, coef, quality, file_pitch=None, files=None, progressive=False, optimize_coding=False):
         """coef: 1 or 3 int16 cuda tensors [n, bh_c, bw_c, 64].  Returns (files [n, file_pitch] uint8, lengths [n] int32,
         status [n] int32), all cuda tensors; nothing is synchronised."""
         L = _bind()
         n = coef[0].shape[0]
+        flags = (JPEG_PROGRESSIVE if progressive else 0) | (JPEG_OPTIMIZE_HUFFMAN if optimize_coding else 0)
         if file_pitch is None:
-            file_pitch = files.shape[1] if files is not None else (self.max_file_bytes + 15) // 16 * 16
+            file_pitch = files.shape[1] if files is not None else (self.max_file_bytes_for(progressive, optimize_coding) + 15) // 16 * 16
         if files is None:
             files = torch.empty((n, file_pitch), dtype=torch.uint8, device=self.device)
         lengths = torch.zeros(n, dtype=torch.int32, device=self.device)
@@ -141,13 +155,17 @@ class JpegEntropyStage:
         ptrs = [c.data_ptr() for c in coef] + [None] * (3 - len(coef))
         stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
-            _native.check(L.ifhip_jpeg_encode_batch_device(self._h, *ptrs, int(quality), n, files.data_ptr(), file_pitch,
-                                                           lengths.data_ptr(), status.data_ptr(), C.c_void_p(stream)))
+            if flags:
+                _native.check(L.ifhip_jpeg_encode_flags_batch_device(self._h, *ptrs, int(quality), flags, n, files.data_ptr(), file_pitch,
+                                                                     lengths.data_ptr(), status.data_ptr(), C.c_void_p(stream)))
+            else:
+                _native.check(L.ifhip_jpeg_encode_batch_device(self._h, *ptrs, int(quality), n, files.data_ptr(), file_pitch,
+                                                               lengths.data_ptr(), status.data_ptr(), C.c_void_p(stream)))
         return files, lengths, status
 
-    def encode(self, coef, quality, file_pitch=None):
+    def encode(self, coef, quality, file_pitch=None, progressive=False, optimize_coding=False):
         """The n files as bytes (None for a dropped image) and the status words."""
-        files, lengths, status = self.encode_device(coef, quality, file_pitch)
+        files, lengths, status = self.encode_device(coef, quality, file_pitch, progressive=progressive, optimize_coding=optimize_coding)
         lengths, status = lengths.cpu().numpy(), status.cpu().numpy()
         host = files[:, :max(int(lengths.max()), 1)].cpu().numpy()
         return [host[i, :int(k)].tobytes() if k else None for i, k in enumerate(lengths)], [int(s) for s in status]
@@ -270,18 +288,19 @@ class MozjpegEncoder:
         return write_jpeg(coef, bitmap.w, bitmap.h, hs, vs, self.quality, self.progressive, self.optimize_coding)
 
     def write_frames(self, bitmap: Bitmap, threads=0, device_entropy=True):
-        """Every frame of the bitmap: one device launch for the pixel stage; the files coded on the device (the preset's
-        default: baseline, Annex K tables) or -- progressive / optimize_coding, or device_entropy=False -- in parallel on
-        the host.  The two coders write the same bytes."""
+        """Every frame of the bitmap: one device launch for the pixel stage; the files coded on the device (baseline,
+        optimize_coding and progressive alike) or -- device_entropy=False -- in parallel on the host.  The two coders write
+        the same bytes."""
         from ..graphics.blend import apply_matte
         apply_matte(bitmap, self.matte)
         bitmap.alpha_meaningful = False
         hs, vs = sampling_factors((2, 2), (2, 2))
         stage = JpegForwardStage(bitmap.w, bitmap.h, hs, vs, bitmap.n, bitmap.data.device)
         qt = torch.from_numpy(np.stack([quant_tables_for_quality(self.quality)] * bitmap.n).view(np.int16)).to(bitmap.data.device)
-        if device_entropy and not self.progressive and not self.optimize_coding:
+        if device_entropy:
             coder = JpegEntropyStage(bitmap.w, bitmap.h, hs, vs, stage.blocks_w, stage.blocks_h, bitmap.n, bitmap.data.device)
-            files, status = coder.encode(stage.write_frames(bitmap, qt), self.quality)
+            files, status = coder.encode(stage.write_frames(bitmap, qt), self.quality, progressive=self.progressive,
+                                         optimize_coding=self.optimize_coding)
             if any(status):                                                   # (cannot happen with coefficients of the forward stage)
                 raise RuntimeError(f"device entropy coder dropped images: status {status}")
             return files

@@ -529,6 +529,7 @@ struct imageflow_context {
     std::atomic<int64_t> device_coded_files{0};          // JPEG outputs whose entropy coding ran on the device (diagnostic)
     std::atomic<int64_t> coalesced_decodes{0};           // decodes of this context that shared their device call with another thread's job
     std::atomic<int> device{-1};                         // device ordinal its jobs run on; -1: the calling thread's current device
+    std::atomic<bool> device_jpeg_options{false};        // EXTENSION ifhip_shim_context_set_device_jpeg_options: progressive / optimised tables coded on the device
     std::atomic<bool> color_management{false};           // EXTENSION ifhip_shim_context_set_color_management: every input is converted to sRGB
     bool cancellation_requested() {
         if (cancel.load(std::memory_order_relaxed)) return true;
@@ -1575,8 +1576,10 @@ struct Job {
             hip_check(static_cast<hipError_t>(ifhip::copy_to_device(d_qt, qt3, 384)), "upload(quant tables)");
             check(ifhip_jpeg_forward_batch_device(st, dev(f), f->bytes(), f->stride, d_qt, 1, d_coef + off[0], d_coef + off[1], d_coef + off[2], t_job_stream));
             poll_cancel();
-            if (write_flags == 0) {
-                // the preset's default (baseline, Annex K tables): the device entropy coder -- only the file leaves the device.
+            if (write_flags == 0 || c->device_jpeg_options.load(std::memory_order_relaxed)) {
+                // the preset's default (baseline, Annex K tables) -- and, where the caller switched it on
+                // (ifhip_shim_context_set_device_jpeg_options), progressive / optimize_huffman_coding:
+                // the device entropy coder -- only the file leaves the device.
                 // First with room for a scan half the size of its coefficients (what the host path assumes too), then, for an
                 // image that is denser than that, with the geometry's worst case.
                 for (int attempt = 0; attempt < 2; ++attempt) {
@@ -1586,10 +1589,15 @@ struct Job {
                     ifhip_jpeg_enc_stage* es = nullptr;
                     if (ifhip_jpeg_enc_stage_create(&es, f->w, f->h, 3, hs, vs, bw, bh, 1, scan_cap) != IFHIP_OK) break;
                     std::unique_ptr<ifhip_jpeg_enc_stage, void (*)(ifhip_jpeg_enc_stage*)> es_guard(es, [](ifhip_jpeg_enc_stage* q) { quiesce(); ifhip_jpeg_enc_stage_destroy(q); });
-                    const size_t pitch = ifhip_jpeg_enc_stage_max_file_bytes(es);
+                    const size_t pitch = ifhip_jpeg_enc_stage_max_file_bytes_for(es, write_flags);
+                    if (pitch == 0) break;                                               // (the flagged forms refuse the geometry)
                     CodedFile file;
                     if (file.alloc(pitch, (pitch + 3u) & ~static_cast<size_t>(3u)) != hipSuccess) break;
-                    check(ifhip_jpeg_encode_batch_device(es, d_coef + off[0], d_coef + off[1], d_coef + off[2], quality, 1, file.d, pitch, file.d_len, file.d_len + 1, t_job_stream));
+                    // (a flagged call allocates its scratch first; where that fails the host writer codes the file)
+                    const int erc = ifhip_jpeg_encode_flags_batch_device(es, d_coef + off[0], d_coef + off[1], d_coef + off[2], quality, write_flags, 1, file.d,
+                                                                         pitch, file.d_len, file.d_len + 1, t_job_stream);
+                    if (erc != IFHIP_OK && write_flags != 0) break;
+                    check(erc);
                     file.fetch(o);
                     if (file.status & IFHIP_ENC_BAD_COEFFICIENT)
                         raise(kArgumentInvalid, "InvalidArgument: coefficient out of range for 8-bit JPEG (more than 11 DC / 10 AC magnitude bits)");
@@ -2373,6 +2381,13 @@ bool ifhip_shim_context_set_device(struct imageflow_context* c, int ordinal) {
 bool ifhip_shim_context_set_color_management(struct imageflow_context* c, int on) {
     CTX_OR_ABORT(c);
     c->color_management.store(on != 0, std::memory_order_relaxed);
+    return true;
+}
+// EXTENSION: the libjpeg_turbo preset's progressive / optimize_huffman_coding files are entropy-coded on the device
+// (ifhip_jpeg_encode_flags_batch_device) instead of by the host writer; off by default.  The files are the same bytes.
+bool ifhip_shim_context_set_device_jpeg_options(struct imageflow_context* c, int on) {
+    CTX_OR_ABORT(c);
+    c->device_jpeg_options.store(on != 0, std::memory_order_relaxed);
     return true;
 }
 int ifhip_shim_context_device(struct imageflow_context* c) {

@@ -27,6 +27,7 @@
 #include "block_scan.hpp"
 #include "hip_entry.hpp"
 #include "jpeg_encode_core.hpp"
+#include "jpeg_encode_progressive.hpp"
 #include "stage_scratch.hpp"
 
 namespace ifhip {
@@ -346,7 +347,13 @@ struct ifhip_jpeg_enc_stage {
     uint8_t* d_header = nullptr;
     StageScratch blocks{&d_tabs, &d_nbits, &d_wg_bits, &d_tot_bits, &d_words, &d_ff, &d_tot_ff, &d_status, &d_header};
     uint8_t* h_header = nullptr;    // pinned
-    ~ifhip_jpeg_enc_stage() { if (h_header) (void)cached_host_free(h_header); }
+    // the optimised-table / progressive forms (jpeg_encode_progressive.hip): their scratch exists from the first flagged call on
+    size_t scan_capacity = 0;
+    ProgScratch* flagged = nullptr;
+    ~ifhip_jpeg_enc_stage() {
+        if (flagged) prog_scratch_destroy(flagged);
+        if (h_header) (void)cached_host_free(h_header);
+    }
 };
 
 namespace {
@@ -361,6 +368,23 @@ int make_enc_geom(uint32_t width, uint32_t height, int ncomp, const uint8_t* hs,
     default: return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: more than %llu blocks per image (32-bit bit positions)",
                          static_cast<unsigned long long>((1ull << 32) / kEncMaxBitsPerBlock));
     }
+}
+
+// The marker segments of a baseline file of this quality in d_header (uploaded when the quality changes).
+int ensure_header(ifhip_jpeg_enc_stage* stage, int quality, hipStream_t st) {
+    if (quality == stage->header_quality) return IFHIP_OK;
+    uint16_t qt[2][64];
+    jpeg_quality_tables(quality, qt);
+    std::vector<uint8_t> h;
+    int rc = jpeg_baseline_header(static_cast<int>(stage->g.ncomp), stage->hs, stage->vs, stage->width, stage->height, qt, &h);
+    if (rc) return rc;
+    if (h.size() > kHeaderCap) return fail(IFHIP_INVALID_STATE, "InvalidState: marker segments of %zu bytes", h.size());
+    HIP_TRY(static_cast<hipError_t>(ifhip::wait_stream(st)));                 // (the pinned copy may still be on its way to the device from the previous call)
+    std::memcpy(stage->h_header, h.data(), h.size());
+    stage->header_len = static_cast<uint32_t>(h.size());
+    HIP_TRY(hipMemcpyAsync(stage->d_header, stage->h_header, h.size(), hipMemcpyHostToDevice, st));
+    stage->header_quality = quality;
+    return IFHIP_OK;
 }
 }  // namespace
 
@@ -431,6 +455,7 @@ int ifhip_jpeg_enc_stage_create(ifhip_jpeg_enc_stage** stage, uint32_t width, ui
     s->cap_words = static_cast<size_t>(cap / 4u);
     s->max_chunks = static_cast<uint32_t>(cap / kEncChunkBytes);
     s->max_images = max_images;
+    s->scan_capacity = scan_capacity;
     const size_t n = max_images;
     if (int arc = s->blocks.ensure([&]() -> int {
         HIP_TRY(DEV_MALLOC(&s->d_tabs, 4096));
@@ -460,6 +485,17 @@ size_t ifhip_jpeg_enc_stage_max_file_bytes(const ifhip_jpeg_enc_stage* stage) {
     return stage ? static_cast<size_t>(kHeaderCap) + 2u * (stage->cap_words * 4u - kEncChunkBytes) + 2u : 0u;
 }
 
+size_t ifhip_jpeg_debug_enc_max_file_bytes_for(uint32_t width, uint32_t height, int n_components, const uint8_t* h_samp, const uint8_t* v_samp,
+                                               const uint32_t* blocks_w3, const uint32_t* blocks_h3, int flags, size_t scan_capacity) {
+    EncGeom g;
+    if (!h_samp || !v_samp || !blocks_w3 || !blocks_h3 || (flags & ~3) || enc_make_geom(width, height, n_components, h_samp, v_samp, blocks_w3, blocks_h3, &g))
+        return 0u;
+    if (flags) return prog_max_file_bytes(g, width, height, flags, scan_capacity);
+    const uint64_t worst = (static_cast<uint64_t>(g.nblocks) * kEncMaxBitsPerBlock + 7u) / 8u;     // as ifhip_jpeg_enc_stage_create sizes the stream
+    const uint64_t cap = scan_capacity ? std::min<uint64_t>(scan_capacity, worst) : worst;
+    return static_cast<size_t>(kHeaderCap + 2u * ((cap + kEncChunkBytes - 1u) / kEncChunkBytes * kEncChunkBytes) + 2u);
+}
+
 int ifhip_jpeg_encode_batch_device(ifhip_jpeg_enc_stage* stage, const int16_t* d_coef0, const int16_t* d_coef1, const int16_t* d_coef2,
                                    int quality, uint32_t n_images, uint8_t* d_files, size_t file_pitch, uint32_t* d_lengths,
                                    uint32_t* d_status, void* hip_stream) {
@@ -473,19 +509,7 @@ int ifhip_jpeg_encode_batch_device(ifhip_jpeg_enc_stage* stage, const int16_t* d
     if (file_pitch < kHeaderCap) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: file_pitch below %u bytes", kHeaderCap);
     if (int rc = stage->blocks.check_device()) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    if (quality != stage->header_quality) {
-        uint16_t qt[2][64];
-        jpeg_quality_tables(quality, qt);
-        std::vector<uint8_t> h;
-        int rc = jpeg_baseline_header(static_cast<int>(stage->g.ncomp), stage->hs, stage->vs, stage->width, stage->height, qt, &h);
-        if (rc) return rc;
-        if (h.size() > kHeaderCap) return fail(IFHIP_INVALID_STATE, "InvalidState: marker segments of %zu bytes", h.size());
-        HIP_TRY(static_cast<hipError_t>(ifhip::wait_stream(st)));                 // (the pinned copy may still be on its way to the device from the previous call)
-        std::memcpy(stage->h_header, h.data(), h.size());
-        stage->header_len = static_cast<uint32_t>(h.size());
-        HIP_TRY(hipMemcpyAsync(stage->d_header, stage->h_header, h.size(), hipMemcpyHostToDevice, st));
-        stage->header_quality = quality;
-    }
+    if (int rc = ensure_header(stage, quality, st)) return rc;
     EncArgs a;
     std::memset(&a, 0, sizeof a);
     a.g = stage->g;
@@ -506,6 +530,41 @@ int ifhip_jpeg_encode_batch_device(ifhip_jpeg_enc_stage* stage, const int16_t* d
     hipLaunchKernelGGL(enc_stuff_kernel, chunk_grid, dim3(256), 0, st, a);
     HIP_TRY(hipGetLastError());
     return IFHIP_OK;
+}
+
+
+size_t ifhip_jpeg_enc_stage_max_file_bytes_for(const ifhip_jpeg_enc_stage* stage, int flags) {
+    if (!stage || (flags & ~3)) return 0u;
+    if (flags == 0) return ifhip_jpeg_enc_stage_max_file_bytes(stage);
+    return prog_max_file_bytes(stage->g, stage->width, stage->height, flags, stage->scan_capacity);
+}
+
+int ifhip_jpeg_encode_flags_batch_device(ifhip_jpeg_enc_stage* stage, const int16_t* d_coef0, const int16_t* d_coef1, const int16_t* d_coef2,
+                                         int quality, int flags, uint32_t n_images, uint8_t* d_files, size_t file_pitch, uint32_t* d_lengths,
+                                         uint32_t* d_status, void* hip_stream) {
+    if (flags & ~3) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: unknown flags 0x%x", flags);
+    if (flags == 0) return ifhip_jpeg_encode_batch_device(stage, d_coef0, d_coef1, d_coef2, quality, n_images, d_files, file_pitch, d_lengths, d_status, hip_stream);
+    if (!stage) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null stage");
+    if (n_images == 0) return IFHIP_OK;
+    if (n_images > stage->max_images) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: %u images exceed the stage capacity %u", n_images, stage->max_images);
+    if (!d_coef0 || (stage->g.ncomp == 3 && (!d_coef1 || !d_coef2)) || !d_files || !d_lengths)
+        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
+    if ((reinterpret_cast<uintptr_t>(d_coef0) | reinterpret_cast<uintptr_t>(d_coef1) | reinterpret_cast<uintptr_t>(d_coef2)) & 15u)
+        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: coefficient planes must be 16-byte aligned");
+    if (file_pitch < kHeaderCap) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: file_pitch below %u bytes", kHeaderCap);
+    if (int rc = stage->blocks.check_device()) return rc;
+    if (!stage->flagged) {                                 // the first flagged call allocates the scratch of both forms
+        if (int rc = prog_scratch_create(&stage->flagged, stage->g, stage->width, stage->height, stage->max_images, stage->scan_capacity)) return rc;
+    }
+    if (int rc = prog_scratch_check_device(stage->flagged)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (int rc = ensure_header(stage, quality, st)) return rc;
+    ProgCall call;
+    call.coef[0] = d_coef0; call.coef[1] = d_coef1; call.coef[2] = d_coef2;
+    for (int c = 0; c < 3; ++c) call.plane_blocks[c] = stage->plane_blocks[c];
+    call.n_images = n_images; call.d_header = stage->d_header; call.files = d_files; call.file_pitch = file_pitch;
+    call.lengths = d_lengths; call.status_out = d_status;
+    return prog_encode(stage->flagged, call, flags, hip_stream);
 }
 
 

@@ -104,7 +104,8 @@ IMAGEFLOW_SHIM_API int64_t ifhip_shim_cancellation_polls_remaining(struct imagef
  * HBM (ifhip_jpeg_decode_resample_batch_device reporting fused = 1). */
 IMAGEFLOW_SHIM_API int64_t ifhip_shim_fused_decode_resamples(struct imageflow_context *context);
 /* Diagnostic: how many JPEG outputs of this context's jobs were entropy-coded on the device (libjpeg_turbo preset without
- * progressive / optimize_huffman_coding: ifhip_jpeg_encode_batch_device; only the file is downloaded). */
+ * progressive / optimize_huffman_coding: ifhip_jpeg_encode_batch_device; with them only after
+ * ifhip_shim_context_set_device_jpeg_options; only the file is downloaded). */
 IMAGEFLOW_SHIM_API int64_t ifhip_shim_device_coded_files(struct imageflow_context *context);
 /* Diagnostic: how many decodes of this context's jobs shared their entropy-decode device call with the job of another
  * thread (concurrent decodes of one geometry are coalesced into one batch; one context per thread, lib.rs:20-27). */
@@ -126,6 +127,13 @@ IMAGEFLOW_SHIM_API int ifhip_shim_context_device(struct imageflow_context *conte
  * cHRM.  Still refused, naming the case: GRAY / CMYK spaces, a Lab PCS, LUT-based profiles.  A malformed profile is a
  * ColorProfileError (ImageMalformed) unless the decoder was told "ignore_color_profile_errors".  Returns true. */
 IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_color_management(struct imageflow_context *context, int on);
+/* EXTENSION.  Device coding of the libjpeg_turbo preset's options, off by default: with on != 0 an encode with
+ * "progressive" and / or "optimize_huffman_coding" is entropy-coded on the device (ifhip_jpeg_encode_flags_batch_device:
+ * only the file is downloaded, not the coefficient planes) -- first with room for streams half the size of the
+ * coefficients, then with the geometry's worst case; the host writer codes the file when a stage cannot be made or the
+ * geometry is refused.  The files are byte-identical either way; ifhip_shim_device_coded_files counts those coded on the
+ * device.  Off, such encodes go to the host writer as before.  Returns true. */
+IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_device_jpeg_options(struct imageflow_context *context, int on);
 
 /* The layout arithmetic behind the `constrain` and `watermark` nodes, callable on its own (no GPU, no context):
  * imageflow_riapi::ir4::process_constraint (imageflow_riapi/src/ir4/layout.rs:334-412) for a source of source_w x source_h

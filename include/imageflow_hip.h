@@ -412,6 +412,36 @@ IFHIP_API size_t ifhip_jpeg_enc_stage_max_file_bytes(const ifhip_jpeg_enc_stage*
 IFHIP_API int ifhip_jpeg_encode_batch_device(ifhip_jpeg_enc_stage* stage, const int16_t* d_coef0, const int16_t* d_coef1,
                                              const int16_t* d_coef2, int quality, uint32_t n_images, uint8_t* d_files,
                                              size_t file_pitch, uint32_t* d_lengths, uint32_t* d_status, void* hip_stream);
+/* The preset's two options on the device: flags = IFHIP_JPEG_OPTIMIZE_HUFFMAN | IFHIP_JPEG_PROGRESSIVE as for
+ * ifhip_jpeg_write; files are byte-identical to ifhip_jpeg_write's (and libjpeg-turbo's) for the same flags.  flags == 0
+ * IS ifhip_jpeg_encode_batch_device.  Optimised tables alone: one interleaved sequential scan against per-image tables
+ * (jpeg_gen_optimal_table).  Progressive: SOF2, jpeg_simple_progression's 10 scans (6 for gray), every scan with optimal
+ * tables of its own.  Passes of one call, all images and scans in each, no host round trip between them: symbol statistics
+ * per (scan, block); end-of-band runs (a maximal sequence of blocks without a symbol of their own, cut greedily at 0x7FFF
+ * blocks or more than 937 buffered correction bits, resolved by one wave per 2048 blocks walking the runs that start there);
+ * one wave per table builds the code; bit counts; prefix sums per scan; the write pass; byte stuffing, every scan a stream
+ * of its own behind its DHT and SOS segments, whose offsets come from a per-image scan on the device.
+ * The stage allocates the extra scratch on the FIRST flagged call (about 6 bytes per block and scan, 20 KiB of tables per
+ * image, and a word stream of its own) and keeps it until the stage is destroyed; that call can therefore fail with
+ * IFHIP_ALLOCATION_FAILED / IFHIP_GPU_ERROR, or with IFHIP_INVALID_ARGUMENT when the streams of an image could exceed
+ * 2^32 bit positions (bound them with scan_capacity).  scan_capacity bounds an image's entropy-coded bytes before stuffing
+ * SUMMED over its scans.  Status bits, drop semantics (length 0, neighbours untouched, nothing stored behind a slot) and the
+ * one-stream-per-stage rule are those of ifhip_jpeg_encode_batch_device.
+ *
+ * ifhip_jpeg_enc_stage_max_file_bytes_for(stage, flags): an arithmetic file_pitch with which no file of these flags
+ * overflows (0: unknown flags, or the geometry is refused); for flags == 0 exactly ifhip_jpeg_enc_stage_max_file_bytes.
+ * Derivation.  Bits of one block in one scan, with codes of at most 16 bits: sequential 16 + 11 + 63 * (16 + 10); DC
+ * first 16 + 11; DC refinement 1; AC first (Se - Ss + 1) * (16 + 10) + 30 (the EOBn field, 16 + 14, charged to a run's
+ * first block); AC refinement (Se - Ss + 1) * 17 + 4 * 16 + 30 + 63 (code and sign per new coefficient, ZRLs, EOBn, 63
+ * correction bits).  worst = the sum over scans of ceil(blocks * bits / 8); stream = min(scan_capacity, worst) rounded up
+ * to 4 KiB chunks, plus one chunk per scan and one to spare (every scan starts on a chunk boundary of the word stream; an
+ * image whose scans need more chunks is dropped with IFHIP_ENC_SCAN_OVERFLOW).  Every stream byte may be stuffed, so
+ * bound = 177 (SOI, APP0, two DQT, SOF) + 14 per SOS + 277 per DHT (one per table of every scan) + 2 * stream + 2 (EOI). */
+IFHIP_API size_t ifhip_jpeg_enc_stage_max_file_bytes_for(const ifhip_jpeg_enc_stage* stage, int flags);
+IFHIP_API int ifhip_jpeg_encode_flags_batch_device(ifhip_jpeg_enc_stage* stage, const int16_t* d_coef0, const int16_t* d_coef1,
+                                                   const int16_t* d_coef2, int quality, int flags, uint32_t n_images,
+                                                   uint8_t* d_files, size_t file_pitch, uint32_t* d_lengths,
+                                                   uint32_t* d_status, void* hip_stream);
 
 /* Device PNG coder: EncoderPreset::Libpng {depth, matte, zlib_compression} (imageflow_types/src/lib.rs:751-755, chosen in
  * codecs/auto.rs:241-268) without the host: what LibPngEncoder::write_frame (codecs/libpng_encoder.rs:43-72,134-160) has
@@ -639,6 +669,10 @@ IFHIP_API int ifhip_webp_decode(const uint8_t* webp, size_t len, uint8_t* bgra, 
 IFHIP_API int ifhip_jpeg_debug_encode_tables(uint32_t* tabs4x256, int n_components, const uint8_t* h_samp, const uint8_t* v_samp,
                                              uint32_t width, uint32_t height, int quality, uint8_t* header, size_t capacity,
                                              size_t* header_len);
+/* Host, for tests: ifhip_jpeg_enc_stage_max_file_bytes_for without a stage (0: the geometry or the flags are refused). */
+IFHIP_API size_t ifhip_jpeg_debug_enc_max_file_bytes_for(uint32_t width, uint32_t height, int n_components, const uint8_t* h_samp,
+                                                         const uint8_t* v_samp, const uint32_t* blocks_w3, const uint32_t* blocks_h3,
+                                                         int flags, size_t scan_capacity);
 
 /* imageflow's 8x8 -> NxN spatial block scalers for the luma plane of a scaled decode: replaces
  * flow_scale_spatial[_srgb]_{1..7}x{1..7} (c_components/lib/codecs_jpeg_idct_fast.c, .h:17-43), the functions the IDCT
