@@ -3,7 +3,9 @@ classic preset: Defaults::LibJPEGv6 -> set_fastest_defaults, so no trellis quant
 what libjpeg runs between write_scanlines and the entropy coder -- BGRA -> YCbCr, chroma down-sampling with edge
 expansion, islow forward DCT, quantisation, dummy blocks -- runs in libimageflow_hip.so on frames that stay in HBM.
 The entropy coder runs on the device too for the preset's default (baseline, Annex K tables: JpegEntropyStage), on the
-host for its progressive / optimize_coding options (write_jpeg*); evalchroma's sampling decision stays on the host."""
+host for its progressive / optimize_coding options (write_jpeg*); evalchroma's sampling decision stays on the host.
+The `mozjpeg` preset (MozjpegEncoder::create, mozjpeg.rs:37-59) adds trellis quantisation between the forward stage's raw
+form and the entropy coder (JpegTrellisStage, MozjpegEncoder.create)."""
 import ctypes as C
 
 import numpy as np
@@ -13,6 +15,7 @@ from .. import _native
 from ..graphics.bitmaps import Bitmap
 
 DEFAULT_QUALITY = 90          # mozjpeg.rs:21
+DEFAULT_TRELLIS_QUALITY = 75  # the `mozjpeg` preset without a quality
 
 # ITU T.81 Annex K.1 / K.2 in natural order: the base tables jpeg_set_quality scales (jcparam.c std_*_quant_tbl)
 STD_LUMINANCE_QUANT_TBL = (
@@ -55,6 +58,13 @@ def _bind():
     L.ifhip_jpeg_forward_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32,
                                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifhip_jpeg_forward.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32] + [C.c_void_p] * 6
+    L.ifhip_jpeg_forward_raw_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32,
+                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ifhip_jpeg_trellis_stage_create.argtypes = [C.POINTER(C.c_void_p), C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint32]
+    L.ifhip_jpeg_trellis_stage_destroy.argtypes = [C.c_void_p]
+    L.ifhip_jpeg_trellis_stage_destroy.restype = None
+    L.ifhip_jpeg_trellis_batch_device.argtypes = [C.c_void_p] * 5 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 4
+    L.ifhip_jpeg_trellis.argtypes = [C.c_void_p] * 3 + [C.c_uint32, C.c_uint32] + [C.c_void_p] * 3 + [C.c_uint32] + [C.c_void_p] * 3
     L._jpeg_fwd_bound = True
     return L
 
@@ -74,15 +84,21 @@ class JpegForwardStage:
         _native.check(L.ifhip_jpeg_fwd_stage_block_dims(self._h, bw.ctypes.data, bh.ctypes.data))
         self.blocks_w, self.blocks_h = [int(v) for v in bw], [int(v) for v in bh]
 
-    def write_frames(self, frames: Bitmap, qt, coef=None):
+    def write_frames(self, frames: Bitmap, qt, coef=None, raw=False):
         """frames: n BGRA frames (already matted, mozjpeg.rs:88-94); qt: cuda tensor [n, 3, 64] of uint16 bit patterns.
-        Returns int16 cuda tensors [n, bh_c, bw_c, 64]: what the entropy coder consumes."""
+        Returns int16 cuda tensors [n, bh_c, bw_c, 64]: what the entropy coder consumes.  raw=True (qt is not read): the
+        unquantised DCT outputs, scaled by 8 -- what JpegTrellisStage consumes."""
         L = _bind()
         n = frames.n
         if coef is None:
             coef = [torch.empty((n, self.blocks_h[c], self.blocks_w[c], 64), dtype=torch.int16, device=self.device) for c in range(3)]
         stream = torch.cuda.current_stream(self.device).cuda_stream
         with torch.cuda.device(self.device):
+            if raw:
+                _native.check(L.ifhip_jpeg_forward_raw_batch_device(self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride, n,
+                                                                    coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(),
+                                                                    C.c_void_p(stream)))
+                return coef
             _native.check(L.ifhip_jpeg_forward_batch_device(self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride,
                                                             qt.data_ptr(), n, coef[0].data_ptr(), coef[1].data_ptr(),
                                                             coef[2].data_ptr(), C.c_void_p(stream)))
@@ -95,6 +111,57 @@ class JpegForwardStage:
                 self._h = C.c_void_p()
         except Exception:
             pass
+
+
+TRELLIS_LAMBDA_ONE = 256      # include/imageflow_hip.h IFHIP_JPEG_TRELLIS_LAMBDA_ONE
+
+
+class JpegTrellisStage:
+    """ifhip_jpeg_trellis_stage (csrc/jpeg_trellis.hip): the mozjpeg preset's rate-distortion optimised quantisation of the raw
+    planes JpegForwardStage.write_frames(raw=True) leaves -- this project's integer restatement of mozjpeg's quantize_trellis
+    (AC only), which the reference's default encoder selects (mozjpeg.rs:37-59)."""
+
+    def __init__(self, width, height, h_samp, v_samp, max_images, device="cuda:0"):
+        L = _bind()
+        self.device = torch.device(device)
+        self._h = C.c_void_p()
+        hs, vs = np.array(list(h_samp), np.uint8), np.array(list(v_samp), np.uint8)
+        with torch.cuda.device(self.device):
+            _native.check(L.ifhip_jpeg_trellis_stage_create(C.byref(self._h), width, height, hs.ctypes.data, vs.ctypes.data, max_images))
+
+    def quantize(self, raw, qt, lambda_scale=TRELLIS_LAMBDA_ONE, coef=None):
+        """raw: 3 int16 cuda tensors [n, bh_c, bw_c, 64]; qt: cuda tensor [n, 3, 64] of uint16 bit patterns.  Returns the
+        quantised planes (same shapes); lambda_scale=0 gives the plain quantiser's."""
+        L = _bind()
+        n = raw[0].shape[0]
+        if coef is None:
+            coef = [torch.empty_like(r) for r in raw]
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            _native.check(L.ifhip_jpeg_trellis_batch_device(self._h, raw[0].data_ptr(), raw[1].data_ptr(), raw[2].data_ptr(), qt.data_ptr(),
+                                                            int(lambda_scale), n, coef[0].data_ptr(), coef[1].data_ptr(), coef[2].data_ptr(),
+                                                            C.c_void_p(stream)))
+        return coef
+
+    def __del__(self):
+        try:
+            if self._h:
+                _bind().ifhip_jpeg_trellis_stage_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+
+def jpeg_trellis_host(raw, width, height, h_samp, v_samp, qt, lambda_scale=TRELLIS_LAMBDA_ONE):
+    """Host-buffer drop-in (numpy): raw planes [bh_c][bw_c][64] int16 + tables [3][64] -> the quantised planes."""
+    L = _bind()
+    hs, vs = np.array(list(h_samp), np.uint8), np.array(list(v_samp), np.uint8)
+    planes = [np.ascontiguousarray(r, np.int16) for r in raw]
+    coef = [np.zeros_like(p) for p in planes]
+    q = np.ascontiguousarray(qt, np.uint16)
+    _native.check(L.ifhip_jpeg_trellis(*[p.ctypes.data for p in planes], width, height, hs.ctypes.data, vs.ctypes.data, q.ctypes.data,
+                                       int(lambda_scale), *[c.ctypes.data for c in coef]))
+    return coef
 
 
 ENC_BAD_COEFFICIENT, ENC_SCAN_OVERFLOW, ENC_FILE_OVERFLOW = 1, 2, 4     # include/imageflow_hip.h IFHIP_ENC_*
@@ -269,13 +336,26 @@ class MozjpegEncoder:
     (default white, :88-92), the forward pixel stage at 4:2:0 (the maximum evalchroma may choose, :133) and the file
     writer with the preset's progressive / optimize_coding options.  Returns the file's bytes."""
 
-    def __init__(self, quality=None, progressive=None, optimize_coding=None, matte=0xFFFFFFFF):
-        self.quality = min(100, DEFAULT_QUALITY if quality is None else int(quality))
-        self.progressive, self.optimize_coding, self.matte = bool(progressive), bool(optimize_coding), matte
+    def __init__(self, quality=None, progressive=None, optimize_coding=None, matte=0xFFFFFFFF, trellis=False):
+        self.quality = min(100, (DEFAULT_TRELLIS_QUALITY if trellis else DEFAULT_QUALITY) if quality is None else int(quality))
+        self.progressive, self.optimize_coding, self.matte, self.trellis = bool(progressive), bool(optimize_coding), matte, trellis
 
     @classmethod
     def create_classic(cls, quality=None, progressive=None, optimize_coding=None, matte=None):
         return cls(quality, progressive, optimize_coding, 0xFFFFFFFF if matte is None else matte)
+
+    @classmethod
+    def create(cls, quality=None, progressive=None, matte=None):
+        """MozjpegEncoder::create (mozjpeg.rs:37-59), the `mozjpeg` preset: mozjpeg's defaults -- trellis quantisation
+        (JpegTrellisStage), optimised tables (:56), always progressive (the reference only ever switches it on, :121-125)."""
+        return cls(quality, True, True, 0xFFFFFFFF if matte is None else matte, trellis=True)
+
+    def _planes(self, stage, bitmap, qt):
+        if not self.trellis:
+            return stage.write_frames(bitmap, qt)
+        hs, vs = sampling_factors((2, 2), (2, 2))
+        trellis = JpegTrellisStage(bitmap.w, bitmap.h, hs, vs, bitmap.n, bitmap.data.device)
+        return trellis.quantize(stage.write_frames(bitmap, None, raw=True), qt)
 
     def write_frame(self, bitmap: Bitmap, frame=0):
         from ..graphics.blend import apply_matte
@@ -284,7 +364,7 @@ class MozjpegEncoder:
         hs, vs = sampling_factors((2, 2), (2, 2))
         stage = JpegForwardStage(bitmap.w, bitmap.h, hs, vs, bitmap.n, bitmap.data.device)
         qt = torch.from_numpy(np.stack([quant_tables_for_quality(self.quality)] * bitmap.n).view(np.int16)).to(bitmap.data.device)
-        coef = [c[frame].cpu().numpy() for c in stage.write_frames(bitmap, qt)]
+        coef = [c[frame].cpu().numpy() for c in self._planes(stage, bitmap, qt)]
         return write_jpeg(coef, bitmap.w, bitmap.h, hs, vs, self.quality, self.progressive, self.optimize_coding)
 
     def write_frames(self, bitmap: Bitmap, threads=0, device_entropy=True):
@@ -299,10 +379,10 @@ class MozjpegEncoder:
         qt = torch.from_numpy(np.stack([quant_tables_for_quality(self.quality)] * bitmap.n).view(np.int16)).to(bitmap.data.device)
         if device_entropy:
             coder = JpegEntropyStage(bitmap.w, bitmap.h, hs, vs, stage.blocks_w, stage.blocks_h, bitmap.n, bitmap.data.device)
-            files, status = coder.encode(stage.write_frames(bitmap, qt), self.quality, progressive=self.progressive,
+            files, status = coder.encode(self._planes(stage, bitmap, qt), self.quality, progressive=self.progressive,
                                          optimize_coding=self.optimize_coding)
             if any(status):                                                   # (cannot happen with coefficients of the forward stage)
                 raise RuntimeError(f"device entropy coder dropped images: status {status}")
             return files
-        coef = [c.cpu().numpy() for c in stage.write_frames(bitmap, qt)]
+        coef = [c.cpu().numpy() for c in self._planes(stage, bitmap, qt)]
         return write_jpeg_batch(coef, bitmap.w, bitmap.h, hs, vs, self.quality, self.progressive, self.optimize_coding, threads)

@@ -13,6 +13,7 @@
 // Two labelled EXTENSIONS, because the reference's JSON API has no raw-pixel I/O:
 //   * decode accepts, besides JPEG and PNG (csrc/png_decode.hip), the container "IFBGRA1\0" + u32le w, h, stride, alpha_meaningful + rows;
 //   * encode writes a real JPEG for the libjpeg_turbo preset -- baseline, optimised tables, progressive (device pixel stage + host Huffman coder, jpeg_write.cpp),
+//     a progressive JPEG with optimised tables for the mozjpeg preset (raw forward stage + trellis quantisation + device coder, jpeg_trellis.hip),
 //     a real PNG for the libpng preset (the device coder, png_encode.hip),
 //     a palette PNG for the pngquant preset (the device quantiser, png_quantize.hip),
 //     a lossless WebP for the webplossless preset (the device coder, webp_encode.hip),
@@ -234,6 +235,7 @@ int encode_coder(const JVal* preset) {
     if (preset->get("libjpeg_turbo")) return IFHIP_ENCODE_CODER_JPEG;
     if (preset->get("libpng")) return IFHIP_ENCODE_CODER_PNG;
     if (preset->get("pngquant")) return IFHIP_ENCODE_CODER_PNGQUANT;
+    if (preset->get("mozjpeg")) return IFHIP_ENCODE_CODER_MOZJPEG;
     if (preset->t == JVal::Str && preset->s == "webplossless") return IFHIP_ENCODE_CODER_WEBP_LOSSLESS;
     return IFHIP_ENCODE_CODER_RAW;
 }
@@ -1541,19 +1543,28 @@ struct Job {
         if (o.out_state == OutState::Taken) raise(kArgumentInvalid, "InvalidArgument: Output buffer for io_id %d has already been taken", io_id);
         poll_cancel();
         const int coder = encode_coder(preset);
-        const JVal* classic = coder == IFHIP_ENCODE_CODER_JPEG ? preset->get("libjpeg_turbo") : nullptr;
+        // EncoderPreset::Mozjpeg {quality, progressive, matte} -> MozjpegEncoder::create (codecs/mozjpeg.rs:37-59): mozjpeg's own
+        // defaults.  Of those the trellis quantisation is built (csrc/jpeg_trellis.hip, this project's restatement of
+        // jcdctmgr.c quantize_trellis, AC only) between the raw forward stage and the device entropy coder; tables are always
+        // optimised (:56) and the file always progressive (`progressive` only ever switches it on, :121-125, over defaults
+        // that already are).  Annex K tables, libjpeg's standard scan script, no deringing, 4:2:0.
+        const bool moz = coder == IFHIP_ENCODE_CODER_MOZJPEG;
+        const JVal* classic = coder == IFHIP_ENCODE_CODER_JPEG ? preset->get("libjpeg_turbo") : moz ? preset->get("mozjpeg") : nullptr;
         if (classic) {
             auto flag = [&](const char* k) { const JVal* v = classic->get(k); return v && v->t == JVal::Bool && v->b; };
-            const int write_flags = (flag("progressive") ? IFHIP_JPEG_PROGRESSIVE : 0) | (flag("optimize_huffman_coding") ? IFHIP_JPEG_OPTIMIZE_HUFFMAN : 0);
+            const int write_flags = moz ? (IFHIP_JPEG_PROGRESSIVE | IFHIP_JPEG_OPTIMIZE_HUFFMAN)
+                                        : (flag("progressive") ? IFHIP_JPEG_PROGRESSIVE : 0) | (flag("optimize_huffman_coding") ? IFHIP_JPEG_OPTIMIZE_HUFFMAN : 0);
             const JVal* q = classic->get("quality");
             int quality = 75;                                                            // mozjpeg.rs:32 DEFAULT_QUALITY
+            if (moz) check_mozjpeg_preset(preset);
+            if (moz && q && q->t == JVal::Num) quality = std::min(100, static_cast<int>(q->n));   // Option<u8> -> u8::min(100, ..) (mozjpeg.rs:53)
             // Option<i32> -> `q as u8` (codecs/auto.rs:201: the value WRAPS, 300 is 44 and -5 is 251) -> u8::min(100, ..) (mozjpeg.rs:71)
-            if (q && q->t == JVal::Num) {
+            if (!moz && q && q->t == JVal::Num) {
                 if (q->n != std::floor(q->n) || q->n < -2147483648.0 || q->n > 2147483647.0) raise(kInvalidJson, "InvalidJson: encode.preset.libjpeg_turbo.quality is a 32-bit integer");
                 quality = std::min(100, static_cast<int>(static_cast<uint8_t>(static_cast<int32_t>(q->n))));
             }
             const JVal* m = classic->get("matte");
-            const uint32_t matte = m && !m->is_null() ? parse_color(m, "encode.preset.libjpeg_turbo.matte") : 0xFFFFFFFFu;   // :88-92
+            const uint32_t matte = m && !m->is_null() ? parse_color(m, moz ? "encode.preset.mozjpeg.matte" : "encode.preset.libjpeg_turbo.matte") : 0xFFFFFFFFu;   // :88-92
             if (shared && f->alpha) f = clone(f);
             check(ifhip_apply_matte_batch_device(dev(f), f->bytes(), 1, f->w, f->h, f->stride, f->alpha ? 1 : 0, matte, t_job_stream));
             f->alpha = false;                                                            // :94 set_alpha_meaningful(false)
@@ -1570,13 +1581,25 @@ struct Job {
             for (int k = 0; k < 3; ++k) off[k + 1] = off[k] + static_cast<size_t>(bw[k]) * bh[k] * 64u;
             int16_t* d_coef = nullptr;
             uint16_t* d_qt = nullptr;
-            hip_check(job_malloc(reinterpret_cast<void**>(&d_coef), off[3] * 2u + 384u), "hipMalloc(coefficients)");
+            // (the mozjpeg preset: the raw planes of the trellis stage lie behind the quantised ones)
+            hip_check(job_malloc(reinterpret_cast<void**>(&d_coef), off[3] * (moz ? 4u : 2u) + 384u), "hipMalloc(coefficients)");
             std::unique_ptr<int16_t, void (*)(int16_t*)> coef_guard(d_coef, [](int16_t* p) { job_free(p); });
-            d_qt = reinterpret_cast<uint16_t*>(d_coef + off[3]);
+            int16_t* d_raw = d_coef + off[3];
+            d_qt = reinterpret_cast<uint16_t*>(d_coef + off[3] * (moz ? 2u : 1u));
             hip_check(static_cast<hipError_t>(ifhip::copy_to_device(d_qt, qt3, 384)), "upload(quant tables)");
-            check(ifhip_jpeg_forward_batch_device(st, dev(f), f->bytes(), f->stride, d_qt, 1, d_coef + off[0], d_coef + off[1], d_coef + off[2], t_job_stream));
+            if (moz) {
+                ifhip_jpeg_trellis_stage* ts = nullptr;
+                check(ifhip_jpeg_trellis_stage_create(&ts, f->w, f->h, hs, vs, 1));
+                std::unique_ptr<ifhip_jpeg_trellis_stage, void (*)(ifhip_jpeg_trellis_stage*)> ts_guard(ts, [](ifhip_jpeg_trellis_stage* q) { quiesce(); ifhip_jpeg_trellis_stage_destroy(q); });
+                check(ifhip_jpeg_forward_raw_batch_device(st, dev(f), f->bytes(), f->stride, 1, d_raw + off[0], d_raw + off[1], d_raw + off[2], t_job_stream));
+                check(ifhip_jpeg_trellis_batch_device(ts, d_raw + off[0], d_raw + off[1], d_raw + off[2], d_qt, IFHIP_JPEG_TRELLIS_LAMBDA_ONE, 1, d_coef + off[0],
+                                                      d_coef + off[1], d_coef + off[2], t_job_stream));
+            } else {
+                check(ifhip_jpeg_forward_batch_device(st, dev(f), f->bytes(), f->stride, d_qt, 1, d_coef + off[0], d_coef + off[1], d_coef + off[2], t_job_stream));
+            }
             poll_cancel();
-            if (write_flags == 0 || c->device_jpeg_options.load(std::memory_order_relaxed)) {
+            // (the mozjpeg preset goes to the device coder without the switch: that guards what older callers pinned for libjpeg_turbo)
+            if (write_flags == 0 || moz || c->device_jpeg_options.load(std::memory_order_relaxed)) {
                 // the preset's default (baseline, Annex K tables) -- and, where the caller switched it on
                 // (ifhip_shim_context_set_device_jpeg_options), progressive / optimize_huffman_coding:
                 // the device entropy coder -- only the file leaves the device.
@@ -2081,9 +2104,24 @@ struct Job {
                nm == "apply_orientation" || nm == "watermark" || nm == "round_image_corners" || nm == "white_balance_histogram_area_threshold_srgb";
     }
 
+    // EncoderPreset::Mozjpeg's quality is an Option<u8>: the reference refuses the message when it is deserialised, before any
+    // node runs -- so every encode node's mozjpeg preset is looked at before the first node runs, and again where it is used
+    static void check_mozjpeg_preset(const JVal* preset) {
+        const JVal* moz = preset ? preset->get("mozjpeg") : nullptr;
+        const JVal* q = moz ? moz->get("quality") : nullptr;
+        if (q && q->t == JVal::Num && (q->n != std::floor(q->n) || q->n < 0.0 || q->n > 255.0))
+            raise(kInvalidJson, "InvalidJson: encode.preset.mozjpeg.quality is an integer 0..255");
+    }
+    static void check_encode_node(const JVal& n) {
+        if (n.t != JVal::Obj || n.o.size() != 1 || n.o[0].first != "encode") return;
+        const JVal* preset = n.o[0].second.get("preset");
+        if (encode_coder(preset) == IFHIP_ENCODE_CODER_MOZJPEG) check_mozjpeg_preset(preset);
+    }
+
     void run_framewise(const JVal& fw) {
         if (const JVal* steps = fw.get("steps")) {
             if (steps->t != JVal::Arr) raise(kInvalidJson, "InvalidJson: framewise.steps must be an array");
+            for (const JVal& n : steps->a) check_encode_node(n);
             FramePtr cur;
             for (const JVal& n : steps->a) {
                 std::string name;
@@ -2111,6 +2149,7 @@ struct Job {
             if (slot.count(to)) raise(kGraphInvalid, "GraphInvalid: node %lld has two %s edges", static_cast<long long>(to), is_canvas ? "canvas" : "input");
             slot[to] = from;
         }
+        for (const auto& kv : nodes->o) check_encode_node(kv.second);
         std::map<int64_t, FramePtr> done;
         std::map<int64_t, int> state;                                                  // 1 = on the stack (cycle check)
         // nodes that mutate a parent's frame in place (their input, or the canvas they draw on) must not see a frame

@@ -25,6 +25,7 @@
 #include "hip_entry.hpp"
 #include "jpeg_encode_progressive.hpp"
 #include "jpeg_encode_progressive_core.hpp"
+#include "jpeg_huff_wave.hpp"
 #include "stage_scratch.hpp"
 
 namespace ifhip {
@@ -285,15 +286,6 @@ __global__ __launch_bounds__(64) void prog_run_kernel(const ProgArgs a, const ui
 }
 
 // ---- tables -------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t wave_min64(uint64_t k) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        const uint64_t o = __shfl_xor(static_cast<unsigned long long>(k), d, 64);
-        k = o < k ? o : k;
-    }
-    return k;
-}
-
 __global__ __launch_bounds__(64) void prog_table_kernel(const ProgArgs a, const uint32_t which) {
     __shared__ uint32_t freq[257], codesize[257], bits[33], codes[256];
     __shared__ int32_t others[257];
@@ -305,14 +297,7 @@ __global__ __launch_bounds__(64) void prog_table_kernel(const ProgArgs a, const 
     huff_init(a.hist + at * 256u, lane, freq, codesize, others);
     for (uint32_t i = lane; i < 256u; i += 64u) { codes[i] = 0u; vals[i] = 0; }
     __syncthreads();
-    for (;;) {
-        const uint64_t k1 = wave_min64(huff_lane_key(freq, lane, 0xFFFFFFFFu));
-        const uint32_t c1 = huff_key_index(k1);
-        const uint64_t k2 = wave_min64(huff_lane_key(freq, lane, c1));
-        if (k2 == ~0ull) break;                            // (uniform) one tree left
-        if (lane == 0u) huff_merge(c1, huff_key_index(k2), freq, codesize, others);
-        __syncthreads();
-    }
+    huff_wave_merge(lane, freq, codesize, others);
     if (lane == 0u) huff_limit(codesize, bits);
     for (uint32_t i = lane; i < 256u; i += 64u) if (codesize[i] && codesize[i] <= 32u) vals[huff_rank(codesize, i)] = static_cast<uint8_t>(i);
     __syncthreads();

@@ -15,17 +15,10 @@
 #include <memory>
 
 #include "hip_entry.hpp"
+#include "jpeg_forward_geom.hpp"
 #include "stage_scratch.hpp"
 
 namespace ifhip {
-
-struct FwdGeom {
-    uint32_t width, height;
-    uint32_t hs[3], vs[3], hmax, vmax;
-    uint32_t bw[3], bh[3];          // coefficient blocks per row / column, MCU padded
-    uint32_t rbw[3], rbh[3];        // real blocks (ceil(downsampled size / 8)); the rest are dummy blocks
-    uint32_t dw[3], dh[3];          // downsampled component size
-};
 
 struct FwdArgs {
     FwdGeom g;
@@ -112,7 +105,11 @@ __device__ __forceinline__ void wave_lds_sync() {       // the 8 lanes of a bloc
 // Phase 2: 32 blocks per pass, 8 lanes per block: row pass (lane = row), column pass + quantisation (lane = column),
 //   16-byte coefficient rows out (a wave writes 8 consecutive blocks = 1 KiB).
 // Dummy blocks are written as zeros; their DC is patched by jpeg_dummy_dc_kernel.
-template <int HS, int VS>
+// RAW (the trellis stage's input, csrc/jpeg_trellis.hip): quantize_coef is skipped and jpeg_fdct_islow's outputs are stored
+// as jfdctint.c leaves them, scaled by 8.  int16 holds them: the samples are level-shifted to [-128, 127], the 8 x 8 DCT in
+// JPEG's normalisation has a gain of at most 8 (DC: 64 samples / 8; every AC basis sums to less), so |output| <= 8 * 1024
+// plus the rounding of two descales -- below 2^14, as libjpeg-turbo's 16-bit DCTELEM relies on for 8-bit samples.
+template <int HS, int VS, bool RAW = false>
 __global__ void __launch_bounds__(256) jpeg_forward_fused_kernel(const FwdArgs a) {
     constexpr int TW = 256, YP = 288, CW = TW / HS, CP = CW + 32;
     constexpr int NPASS = VS + (HS == 2 ? 1 : 2);
@@ -125,7 +122,7 @@ __global__ void __launch_bounds__(256) jpeg_forward_fused_kernel(const FwdArgs a
     const uint32_t t = threadIdx.x, img = blockIdx.z;
     const uint32_t W = a.g.width, H = a.g.height;
     const uint8_t* src = a.bgra + static_cast<size_t>(img) * a.image_bytes;
-    if (t < 192u) {
+    if (!RAW && t < 192u) {
         const int32_t qv = static_cast<int32_t>(a.qt[static_cast<size_t>(img) * 192u + t]) << 3;
         qtab[t] = make_uint4(static_cast<uint32_t>(qv - 1), __float_as_uint(__builtin_amdgcn_rcpf(static_cast<float>(qv))),   // 1 ulp is enough
                              static_cast<uint32_t>(qv >> 1), static_cast<uint32_t>(-qv));
@@ -237,7 +234,7 @@ __global__ void __launch_bounds__(256) jpeg_forward_fused_kernel(const FwdArgs a
         if (real) {
             const uint4* q = qtab + c * 64u + lane8;
 #pragma unroll
-            for (int r = 0; r < 8; ++r) w[r * 8 + lane8] = quantize_coef(o[r], q[r * 8]);
+            for (int r = 0; r < 8; ++r) w[r * 8 + lane8] = RAW ? o[r] : quantize_coef(o[r], q[r * 8]);
         }
         wave_lds_sync();
         if (real) {
@@ -284,26 +281,6 @@ struct ifhip_jpeg_fwd_stage {
     uint32_t max_images = 0;
 };
 
-static int make_fwd_geom(uint32_t width, uint32_t height, const uint8_t* hs, const uint8_t* vs, FwdGeom* g) {
-    if (width == 0 || height == 0) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Bitmap dimensions cannot be zero");
-    if (!hs || !vs) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null sampling factors");
-    std::memset(g, 0, sizeof *g);
-    g->width = width; g->height = height;
-    for (int c = 0; c < 3; ++c) { g->hs[c] = hs[c]; g->vs[c] = vs[c]; }
-    g->hmax = hs[0]; g->vmax = vs[0];
-    const bool ok = hs[1] == 1 && vs[1] == 1 && hs[2] == 1 && vs[2] == 1 && (g->hmax == 1 || g->hmax == 2) &&
-                    (g->vmax == 1 || g->vmax == 2) && !(g->hmax == 1 && g->vmax == 2);
-    if (!ok) return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: only 4:4:4, 4:2:2 (h2v1) and 4:2:0 sampling");
-    const uint32_t mw = (width + 8u * g->hmax - 1u) / (8u * g->hmax), mh = (height + 8u * g->vmax - 1u) / (8u * g->vmax);
-    for (int c = 0; c < 3; ++c) {
-        g->bw[c] = mw * g->hs[c]; g->bh[c] = mh * g->vs[c];
-        g->dw[c] = (width * g->hs[c] + g->hmax - 1u) / g->hmax;
-        g->dh[c] = (height * g->vs[c] + g->vmax - 1u) / g->vmax;
-        g->rbw[c] = (g->dw[c] + 7u) / 8u; g->rbh[c] = (g->dh[c] + 7u) / 8u;
-    }
-    return IFHIP_OK;
-}
-
 extern "C" {
 
 int ifhip_jpeg_fwd_stage_create(ifhip_jpeg_fwd_stage** stage, uint32_t width, uint32_t height, const uint8_t* h_samp,
@@ -329,13 +306,13 @@ int ifhip_jpeg_fwd_stage_block_dims(const ifhip_jpeg_fwd_stage* stage, uint32_t*
     return IFHIP_OK;
 }
 
-int ifhip_jpeg_forward_batch_device(ifhip_jpeg_fwd_stage* stage, const uint8_t* d_bgra, size_t image_bytes, uint32_t stride,
-                                    const uint16_t* d_qt, uint32_t n_images, int16_t* d_coef0, int16_t* d_coef1,
-                                    int16_t* d_coef2, void* hip_stream) {
+// the checks and the launches of both forms (raw: no quantisation tables, no dummy DC values)
+static int forward_batch(ifhip_jpeg_fwd_stage* stage, const uint8_t* d_bgra, size_t image_bytes, uint32_t stride, const uint16_t* d_qt, bool raw,
+                         uint32_t n_images, int16_t* d_coef0, int16_t* d_coef1, int16_t* d_coef2, void* hip_stream) {
     if (!stage) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null stage");
     if (n_images == 0) return IFHIP_OK;
     if (n_images > stage->max_images) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: %u images exceed the stage capacity %u", n_images, stage->max_images);
-    if (!d_bgra || !d_qt || !d_coef0 || !d_coef1 || !d_coef2) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
+    if (!d_bgra || (!raw && !d_qt) || !d_coef0 || !d_coef1 || !d_coef2) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
     if (int rc = check_frames(d_bgra, image_bytes, stage->g.width, stage->g.height, stride, "BGRA")) return rc;
     if ((reinterpret_cast<uintptr_t>(d_coef0) | reinterpret_cast<uintptr_t>(d_coef1) | reinterpret_cast<uintptr_t>(d_coef2)) & 15u)
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: coefficient planes must be 16-byte aligned");
@@ -350,6 +327,13 @@ int ifhip_jpeg_forward_batch_device(ifhip_jpeg_fwd_stage* stage, const uint8_t* 
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     const uint32_t mh = a.g.bh[0] / a.g.vs[0];
     const dim3 grid((a.g.bw[0] * 8u + 255u) / 256u, mh, n_images);
+    if (raw) {
+        if (a.g.hmax == 1) hipLaunchKernelGGL((jpeg_forward_fused_kernel<1, 1, true>), grid, dim3(256), 0, st, a);
+        else if (a.g.vmax == 1) hipLaunchKernelGGL((jpeg_forward_fused_kernel<2, 1, true>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((jpeg_forward_fused_kernel<2, 2, true>), grid, dim3(256), 0, st, a);
+        HIP_TRY(hipGetLastError());
+        return IFHIP_OK;
+    }
     if (a.g.hmax == 1) hipLaunchKernelGGL((jpeg_forward_fused_kernel<1, 1>), grid, dim3(256), 0, st, a);
     else if (a.g.vmax == 1) hipLaunchKernelGGL((jpeg_forward_fused_kernel<2, 1>), grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL((jpeg_forward_fused_kernel<2, 2>), grid, dim3(256), 0, st, a);
@@ -359,6 +343,32 @@ int ifhip_jpeg_forward_batch_device(ifhip_jpeg_fwd_stage* stage, const uint8_t* 
         HIP_TRY(hipGetLastError());
     }
     return IFHIP_OK;
+}
+
+}  // extern "C"
+
+// jpeg_forward_geom.hpp: the dummy blocks' DC values of planes whose real blocks are final (the trellis stage's last step)
+int ifhip::launch_dummy_dc(const FwdGeom& g, int16_t* d_coef0, uint32_t n_images, void* hip_stream) {
+    if (g.rbw[0] == g.bw[0] && g.rbh[0] == g.bh[0]) return IFHIP_OK;
+    FwdArgs a;
+    std::memset(&a, 0, sizeof a);
+    a.g = g; a.n_images = n_images; a.coef[0] = d_coef0;
+    hipLaunchKernelGGL(jpeg_dummy_dc_kernel, dim3((g.bw[0] * g.bh[0] + 255u) / 256u, n_images), dim3(256), 0, static_cast<hipStream_t>(hip_stream), a);
+    HIP_TRY(hipGetLastError());
+    return IFHIP_OK;
+}
+
+extern "C" {
+
+int ifhip_jpeg_forward_batch_device(ifhip_jpeg_fwd_stage* stage, const uint8_t* d_bgra, size_t image_bytes, uint32_t stride,
+                                    const uint16_t* d_qt, uint32_t n_images, int16_t* d_coef0, int16_t* d_coef1,
+                                    int16_t* d_coef2, void* hip_stream) {
+    return forward_batch(stage, d_bgra, image_bytes, stride, d_qt, false, n_images, d_coef0, d_coef1, d_coef2, hip_stream);
+}
+
+int ifhip_jpeg_forward_raw_batch_device(ifhip_jpeg_fwd_stage* stage, const uint8_t* d_bgra, size_t image_bytes, uint32_t stride,
+                                        uint32_t n_images, int16_t* d_raw0, int16_t* d_raw1, int16_t* d_raw2, void* hip_stream) {
+    return forward_batch(stage, d_bgra, image_bytes, stride, nullptr, true, n_images, d_raw0, d_raw1, d_raw2, hip_stream);
 }
 
 int ifhip_jpeg_forward(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, const uint8_t* h_samp,

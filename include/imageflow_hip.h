@@ -347,6 +347,38 @@ IFHIP_API int ifhip_jpeg_forward_batch_device(ifhip_jpeg_fwd_stage* stage, const
 IFHIP_API int ifhip_jpeg_forward(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride,
                                  const uint8_t* h_samp, const uint8_t* v_samp, const uint16_t* qt,
                                  int16_t* coef0, int16_t* coef1, int16_t* coef2);
+/* The same stage without quantize_coef, for the trellis stage below: jpeg_fdct_islow's outputs as jfdctint.c leaves them
+ * (scaled by 8) in int16 planes of the same layout; dummy blocks are zero, DC included.  Same stage object and argument
+ * checks as ifhip_jpeg_forward_batch_device; no quantisation tables are read. */
+IFHIP_API int ifhip_jpeg_forward_raw_batch_device(ifhip_jpeg_fwd_stage* stage, const uint8_t* d_bgra, size_t image_bytes,
+                                                  uint32_t stride, uint32_t n_images, int16_t* d_raw0, int16_t* d_raw1,
+                                                  int16_t* d_raw2, void* hip_stream);
+/* Trellis quantisation for the mozjpeg preset: the interface this stands in for is the reference's default JPEG encoder
+ * (codecs/mozjpeg.rs:37-59: MozjpegEncoder::create selects mozjpeg's own defaults, whose quantiser is mozjpeg's
+ * jcdctmgr.c quantize_trellis).  Rate-distortion optimised quantisation of the raw planes, AC only: per frame and table
+ * class (luma; Cb and Cr together) the plain quantiser's sequential AC symbols are counted, libjpeg's optimal code lengths
+ * for them (every legal symbol counted once more) are the rate model, and every real block's levels minimise
+ * sum w_i (|x_i| - level_i 8 Q_i)^2 + lambda_b * bits over the candidates 0, q_i and q_i - 1 (q_i the plain level; the
+ * sign is x_i's), w_i = 1 / Q_i^2, lambda_b falling with the block's AC energy (mozjpeg's published lambda_log_scale1 /
+ * lambda_log_scale2 = 14.75 / 16.5).  DC keeps its plain level; dummy blocks are as ifhip_jpeg_forward_batch_device
+ * leaves them.  Integer arithmetic (csrc/jpeg_trellis_core.hpp): this project's restatement of the published algorithm,
+ * pinned to its CPU emulation and not to mozjpeg's bytes.  lambda_scale: in 1/256ths of the tuned factor, at most 65535;
+ * 256 is the preset's, 0 gives exactly the planes of ifhip_jpeg_forward_batch_device.  d_qt: [n_images][3][64] as there.
+ * Planes are 16-byte aligned; every store is inside the planes' block counts.  Asynchronous on hip_stream. */
+#define IFHIP_JPEG_TRELLIS_LAMBDA_ONE 256
+typedef struct ifhip_jpeg_trellis_stage ifhip_jpeg_trellis_stage;
+IFHIP_API int ifhip_jpeg_trellis_stage_create(ifhip_jpeg_trellis_stage** stage, uint32_t width, uint32_t height,
+                                              const uint8_t* h_samp, const uint8_t* v_samp, uint32_t max_images);
+IFHIP_API void ifhip_jpeg_trellis_stage_destroy(ifhip_jpeg_trellis_stage* stage);
+IFHIP_API int ifhip_jpeg_trellis_batch_device(ifhip_jpeg_trellis_stage* stage, const int16_t* d_raw0, const int16_t* d_raw1,
+                                              const int16_t* d_raw2, const uint16_t* d_qt, uint32_t lambda_scale,
+                                              uint32_t n_images, int16_t* d_coef0, int16_t* d_coef1, int16_t* d_coef2,
+                                              void* hip_stream);
+/* The synchronous host-buffer drop-in (same stand-in, codecs/mozjpeg.rs:37-59 / jcdctmgr.c quantize_trellis): one frame's
+ * raw planes and tables [3][64] in host memory, staged through the device. */
+IFHIP_API int ifhip_jpeg_trellis(const int16_t* raw0, const int16_t* raw1, const int16_t* raw2, uint32_t width, uint32_t height,
+                                 const uint8_t* h_samp, const uint8_t* v_samp, const uint16_t* qt, uint32_t lambda_scale,
+                                 int16_t* coef0, int16_t* coef1, int16_t* coef2);
 /* Host half of the same encoder: jpeg_set_quality's tables (jcparam.c: Annex K tables scaled, force_baseline; [0] luma,
  * [1] chroma, natural order) and the baseline file writer -- markers in jcmarker.c's order plus the sequential Huffman
  * coder with the Annex K tables (set_fastest_defaults: no optimised tables, not progressive).  Byte-identical to
@@ -554,7 +586,7 @@ IFHIP_API int ifhip_webp_encode(const uint8_t* bgra, uint32_t width, uint32_t he
                                 uint8_t* out, size_t capacity, size_t* len);
 
 /* Which coder the shim's `encode` node hands an EncoderPreset to (imageflow_types/src/lib.rs:745-774, chosen in
- * codecs/auto.rs), given the preset's JSON text: an object with the key libjpeg_turbo / libpng / pngquant, or the string
+ * codecs/auto.rs), given the preset's JSON text: an object with the key libjpeg_turbo / libpng / pngquant / mozjpeg, or the string
  * "webplossless" (a unit variant); every other preset ("gif", webplossy in any form, lodepng, ...) gets the raw BGRA
  * container.  -1: the text is no JSON.  Host only: it lets a test see the dispatch without a device. */
 #define IFHIP_ENCODE_CODER_RAW 0
@@ -562,6 +594,7 @@ IFHIP_API int ifhip_webp_encode(const uint8_t* bgra, uint32_t width, uint32_t he
 #define IFHIP_ENCODE_CODER_PNG 2
 #define IFHIP_ENCODE_CODER_PNGQUANT 3
 #define IFHIP_ENCODE_CODER_WEBP_LOSSLESS 4
+#define IFHIP_ENCODE_CODER_MOZJPEG 5      /* the key mozjpeg: the libjpeg_turbo chain with the trellis stage, always progressive */
 IFHIP_API int ifhip_encode_preset_coder(const char* preset_json, size_t len);
 
 /* Device PNG decoder: what LibPngDecoder (imageflow_core/src/codecs/libpng_decoder.rs:36-104,297-299,340-383) gets from
