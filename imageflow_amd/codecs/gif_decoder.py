@@ -1,0 +1,97 @@
+"""Host mirror of GifDecoder (imageflow_core/src/codecs/gif/mod.rs:21-309) on the device GIF decoder of libimageflow_hip.so
+(csrc/gif_read.cpp, csrc/gif_decode.hip): GIF files -> the logical screen after the selected frame as 8-bit BGRA in HBM --
+segment-parallel LZW and the frame replay (dispose, blit) on the GPU.  For tests and tools; the job path is `decode` with a
+GIF io_id and the decoder command {"select_frame": N} (csrc/abi_shim.cpp)."""
+import ctypes as C
+
+import numpy as np
+import torch
+
+from .. import _native
+from ..errors import ErrorKind, FlowError
+from ..graphics.bitmaps import Bitmap, get_stride
+
+# include/imageflow_hip.h IFHIP_GIF_DEC_*
+STATUS = {0: "ok", 1: "too_little", 2: "bad_code", 3: "container", 4: "min_code_size", 5: "no_palette", 6: "frame_too_large", 7: "no_such_frame"}
+
+
+class GifFileInfo(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("width", "height", "has_global_palette", "background_index")]
+
+
+def _bind():
+    L = _native.lib()
+    if getattr(L, "_gif_dec_bound", False):
+        return L
+    L.ifhip_gif_info.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(GifFileInfo)]
+    L.ifhip_gif_decode_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.ifhip_gif_decode.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_size_t, C.POINTER(C.c_uint32)]
+    L._gif_dec_bound = True
+    return L
+
+
+def gif_info(data):
+    """GifDecoder::create + get_unscaled_image_info (mod.rs:45-101,181-194): the header's facts; no frame has been read.  Host only."""
+    L = _bind()
+    buf = np.frombuffer(bytes(data), np.uint8)
+    info = GifFileInfo()
+    _native.check(L.ifhip_gif_info(buf.ctypes.data, buf.size, C.byref(info)))
+    out = {n: int(getattr(info, n)) for n, _ in GifFileInfo._fields_}
+    out["has_global_palette"] = bool(out["has_global_palette"])
+    out.update(preferred_mime_type="image/gif", preferred_extension="gif", image_width=out["width"], image_height=out["height"],
+               frame_decodes_into="bgra_32", lossless=False, multiple_frames=False)
+    return out
+
+
+def decode_gif_batch(files, frame_index=None, device="cuda:0", frames=None, fill=None):
+    """files: n GIF files (bytes) of any size, decoded and composed in one batch of five launches.  frame_index: the frame of
+    each file to hand on (None: frame 0 of each).  Returns (frames, status): frames[i] a Bitmap of the logical screen (None
+    where the header did not parse or describes no pixels), status[i] the file's status word.  frames: Bitmaps to decode into
+    (their strides are honoured); fill: a byte the new frames are filled with first."""
+    L = _bind()
+    device = torch.device(device)
+    n = len(files)
+    bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
+    out = list(frames) if frames is not None else [None] * n
+    for i, b in enumerate(bufs):
+        if out[i] is not None:
+            continue
+        info = GifFileInfo()
+        if L.ifhip_gif_info(b.ctypes.data, b.size, C.byref(info)) != 0 or not info.width or not info.height:
+            continue
+        stride = get_stride(info.width)
+        data = torch.full((1, info.height * stride), 0 if fill is None else fill, dtype=torch.uint8, device=device)
+        out[i] = Bitmap(data, info.width, info.height, stride, alpha_meaningful=True)
+    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (C.c_size_t * n)(*[b.size for b in bufs])
+    want = (C.c_uint32 * n)(*[int(v) for v in frame_index]) if frame_index is not None else None
+    d_frames = (C.c_void_p * n)(*[o.data.data_ptr() if o is not None else None for o in out])
+    frame_bytes = (C.c_size_t * n)(*[o.data.shape[1] if o is not None else 0 for o in out])
+    strides = (C.c_uint32 * n)(*[o.stride if o is not None else 0 for o in out])
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    with torch.cuda.device(device):
+        _native.check(L.ifhip_gif_decode_batch_device(ptrs, lens, n, want, d_frames, frame_bytes, strides, status.data_ptr(), C.c_void_p(stream)))
+    return out, [int(s) for s in status.cpu().numpy()[:n]]
+
+
+def decode_gif(data, frame_index=0, device="cuda:0"):
+    """GifDecoder::read_frame with SelectFrame(frame_index): one file -> a Bitmap.  A damaged file raises."""
+    frames, status = decode_gif_batch([data], [frame_index], device)
+    if status[0]:
+        raise FlowError(ErrorKind.InvalidArgument, f"ImageMalformed: GIF decoding error: {STATUS.get(status[0], status[0])}")
+    return frames[0]
+
+
+def decode_gif_host(data, frame_index=0, stride=None, out=None):
+    """Host-buffer drop-in (numpy): the file -> BGRA rows [h, stride] uint8."""
+    L = _bind()
+    buf = np.frombuffer(bytes(data), np.uint8)
+    info = GifFileInfo()
+    _native.check(L.ifhip_gif_info(buf.ctypes.data, buf.size, C.byref(info)))
+    stride = stride or 4 * info.width
+    if out is None:
+        out = np.zeros((info.height, stride), np.uint8)
+    status = C.c_uint32(0)
+    _native.check(L.ifhip_gif_decode(buf.ctypes.data, buf.size, frame_index, out.ctypes.data, stride, out.size, C.byref(status)))
+    return out

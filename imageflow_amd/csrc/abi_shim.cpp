@@ -46,6 +46,7 @@
 #include "common.hpp"           // the library's per-job memory cache and thread stream (devmem.cpp)
 #include "color_profile.hpp"   // a colour profile as a conversion plan (color_profile.cpp; the kernel: color_profile.hip)
 #include "png_read.hpp"         // the PNG chunk walk and the device decode of a walked file (png_read.cpp, png_decode.hip)
+#include "gif_read.hpp"         // the container walk and the device decode of a GIF (gif_read.cpp, gif_decode.hip)
 #include "webp_read.hpp"        // the RIFF walk, the prepare and the device decode of a lossless WebP (webp_read.cpp, webp_decode.hip)
 #include "layout.hpp"           // imageflow_riapi's constraint layout (constrain / watermark)
 #include "querystring.hpp"      // imageflow_riapi's querystring: Instructions, their expansion into nodes (command_string)
@@ -497,7 +498,16 @@ struct Io {
     // DecoderCommand::WebPDecoderHints (codecs/webp.rs:181-188): the size libwebp's rescaler would decode to; acted on by a WebP input only
     bool told_webp = false;
     uint32_t told_webp_w = 0, told_webp_h = 0;
+    // DecoderCommand::SelectFrame (codecs/gif/mod.rs:200-205): the frame a GIF input hands on; the other decoders ignore it
+    bool told_frame = false;
+    int32_t told_frame_n = 0;
 };
+// select_frame: an integer (s::DecoderCommand::SelectFrame(i32))
+void tell_select_frame(Io& in, const JVal& j) {
+    if (j.t != JVal::Num || !(j.n >= -2147483648.0 && j.n <= 2147483647.0)) return;
+    in.told_frame = true;
+    in.told_frame_n = static_cast<int32_t>(j.n);
+}
 // webp_decoder_hints is accepted whatever it holds, as it was before a WebP input could act on it: only a hint that
 // carries both sizes is kept with the input
 void tell_webp_hint(Io& in, const JVal& j) {
@@ -873,6 +883,11 @@ struct Job {
     static bool is_webp(const Io& in) {                                  // codecs/mod.rs:130-131: RIFF....WEBP, 12 bytes
         return in.in_len >= 12 && std::memcmp(in.in, "RIFF", 4) == 0 && std::memcmp(in.in + 8, "WEBP", 4) == 0;
     }
+    // "GIF87a" / "GIF89a" and a logical screen with pixels.  A GIF8?a buffer whose screen is 0 x 0 describes no canvas to
+    // decode into and stays ImageTypeNotSupported (known difference: the reference reports a GIF decoding error)
+    static bool is_gif(const Io& in) {
+        return in.in_len >= 13 && (std::memcmp(in.in, "GIF87a", 6) == 0 || std::memcmp(in.in, "GIF89a", 6) == 0) && (in.in[6] | in.in[7]) && (in.in[8] | in.in[9]);
+    }
     // the walk of a WebP input for a decode: a lossy file is ImageTypeNotSupported (known difference: the reference decodes it)
     static void walk_webp(const Io& in, ifhip::WebpParsed* P) {
         const int rc = ifhip::parse_webp_for_decode(in.in, in.in_len, P);
@@ -911,6 +926,12 @@ struct Job {
         if (is_webp(in)) {                                               // WebPDecoder: no EXIF orientation (webp.rs:176-179)
             ifhip::WebpParsed P;
             walk_webp(in, &P);
+            *w = P.w; *h = P.h;
+            return;
+        }
+        if (is_gif(in)) {                                                // GifDecoder: the logical screen, no EXIF orientation (gif/mod.rs:181-198)
+            ifhip::GifParsed P;
+            check(ifhip::parse_gif_header(in.in, in.in_len, &P));
             *w = P.w; *h = P.h;
             return;
         }
@@ -1060,6 +1081,41 @@ struct Job {
         return f;
     }
 
+    // GifDecoder::read_frame (codecs/gif/mod.rs:207-298) on the device: the host walks the container up to the selected frame
+    // (csrc/gif_read.cpp), the LZW streams of frames 0..N are decoded and the frames composed with their disposal by
+    // csrc/gif_decode.hip; frame N's screen enters the graph as bgra_32 with meaningful alpha.  The limits come first, on the
+    // header (mod.rs:55-85: max_decode_size, else max_frame_size, on the logical screen).  GIF carries neither EXIF nor a
+    // colour profile; the JPEG and WebP hints are accepted and ignored.
+    FramePtr decode_gif(int32_t io_id, Io& in) {
+        ifhip::GifParsed P;
+        check(ifhip::parse_gif_header(in.in, in.in_len, &P));
+        check_size(sec.max_decode_size, "max_decode_size", P.w, P.h);
+        check_size(sec.max_frame_size, "max_frame_size", P.w, P.h);
+        const int32_t target = in.told_frame ? in.told_frame_n : 0;
+        check(ifhip::parse_gif(in.in, in.in_len, static_cast<uint32_t>(std::max<int32_t>(target, 0)), &P));
+        auto refuse = [&](uint32_t status) {
+            if (status == IFHIP_GIF_DEC_NO_SUCH_FRAME)                                // mod.rs:217-224
+                raise(kArgumentInvalid, "InvalidArgument: frame=%d requested but GIF only has %zu frames", target, P.frames.size());
+            if (status == IFHIP_GIF_DEC_FRAME_TOO_LARGE) raise(kArgumentInvalid, "SizeLimitExceeded: %s (io_id %d)", ifhip::gif_status_text(status), io_id);
+            raise(kImageMalformed, "ImageMalformed: GIF decoding error: %s (io_id %d, status %u)", ifhip::gif_status_text(status), io_id, status);
+        };
+        if (P.status) refuse(P.status);
+        FramePtr f = new_frame(P.w, P.h, true, 0, true);
+        uint32_t* d_status = nullptr;
+        hip_check(job_malloc(reinterpret_cast<void**>(&d_status), 16), "hipMalloc(status)");
+        struct Guard { void* p; ~Guard() { job_free(p); } } guard{d_status};
+        const ifhip::GifParsed* parsed = &P;
+        const size_t bytes = f->bytes();
+        poll_cancel();
+        check(ifhip::gif_decode_parsed_device(&parsed, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream));
+        uint32_t status = 0;
+        hip_check(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, t_job_stream), "download(status)");
+        hip_check(static_cast<hipError_t>(ifhip::wait_stream(t_job_stream)), "decode(gif)");
+        if (status) refuse(status);
+        decodes.push_back({io_id, P.w, P.h, "image/gif", "gif"});
+        return f;
+    }
+
     // decode: MozJpegDecoder::read_frame (codecs/mozjpeg_decoder.rs:295-420) on the device, or the raw extension
     FramePtr decode(int32_t io_id, uint32_t hint_w, uint32_t hint_h, bool luma_spatial, bool luma_srgb) {
         Timed t(this, "primitive_decoder");
@@ -1079,6 +1135,7 @@ struct Job {
         }
         if (is_png(in)) return decode_png(io_id, in);
         if (is_webp(in)) return decode_webp(io_id, in);
+        if (is_gif(in)) return decode_gif(io_id, in);
         if (in.in_len < 3 || in.in[0] != 0xFF || in.in[1] != 0xD8)                        // codecs/mod.rs:398-415 sniffing
             raise(kImageTypeNotSupported, "ImageTypeNotSupported: io_id %d is neither a JPEG nor the raw BGRA extension", io_id);
         {   // limits before anything is staged (mozjpeg_decoder.rs:196-214 checks max_decode_size on the header)
@@ -1927,6 +1984,8 @@ struct Job {
                             input(static_cast<int32_t>(want_int(p, "io_id", "decode"))).told_ignore_profile_errors = true;
                         } else if (cmd.t == JVal::Str && cmd.s == "convert_color_profile") {  // EXTENSION: colour management for this input
                             input(static_cast<int32_t>(want_int(p, "io_id", "decode"))).told_convert_profile = true;
+                        } else if (const JVal* j = cmd.get("select_frame")) {                // s::DecoderCommand::SelectFrame(i32): a GIF input acts on it
+                            tell_select_frame(input(static_cast<int32_t>(want_int(p, "io_id", "decode"))), *j);
                         } else if (const JVal* j = cmd.get("webp_decoder_hints")) {          // s::WebPDecoderHints {width, height}
                             tell_webp_hint(input(static_cast<int32_t>(want_int(p, "io_id", "decode"))), *j);
                         } else if (const JVal* j = cmd.get("jpeg_downscale_hints")) {        // s::JpegIDCTDownscaleHints
@@ -2562,6 +2621,8 @@ const struct imageflow_json_response* imageflow_context_send_json(struct imagefl
                 in.told_discard_profile = true;                                      // the samples as they are; wins over colour management
             } else if (cmd->t == JVal::Obj && cmd->get("webp_decoder_hints")) {      // s::DecoderCommand::WebPDecoderHints: kept with the input
                 tell_webp_hint(in, *cmd->get("webp_decoder_hints"));
+            } else if (cmd->t == JVal::Obj && cmd->get("select_frame")) {            // s::DecoderCommand::SelectFrame: kept with the input
+                tell_select_frame(in, *cmd->get("select_frame"));
             } else if (cmd->t == JVal::Str && cmd->s == "ignore_color_profile_errors") {
                 in.told_ignore_profile_errors = true;                                // acted on where colour management is switched on
             } else if (cmd->t == JVal::Str && cmd->s == "convert_color_profile") {   // EXTENSION: colour management for this input
@@ -2586,6 +2647,13 @@ const struct imageflow_json_response* imageflow_context_send_json(struct imagefl
                 return respond(c, 200, "{\n  \"code\": 200,\n  \"success\": true,\n  \"message\": \"OK\",\n  \"data\": {\n    \"image_info\": {\"preferred_mime_type\": \"image/webp\", "
                                        "\"preferred_extension\": \"webp\", \"image_width\": " + std::to_string(P.w) + ", \"image_height\": " + std::to_string(P.h) +
                                        ", \"frame_decodes_into\": \"" + (P.has_alpha ? "bgra_32" : "bgr_32") + "\"}\n  }\n}");
+            }
+            if (Job::is_gif(in)) {                                   // GifDecoder::get_unscaled_image_info: no frame read yet (gif/mod.rs:181-194)
+                ifhip::GifParsed P;
+                check(ifhip::parse_gif_header(in.in, in.in_len, &P));
+                return respond(c, 200, "{\n  \"code\": 200,\n  \"success\": true,\n  \"message\": \"OK\",\n  \"data\": {\n    \"image_info\": {\"preferred_mime_type\": \"image/gif\", "
+                                       "\"preferred_extension\": \"gif\", \"image_width\": " + std::to_string(P.w) + ", \"image_height\": " + std::to_string(P.h) +
+                                       ", \"frame_decodes_into\": \"bgra_32\", \"lossless\": false, \"multiple_frames\": false}\n  }\n}");
             }
             uint32_t w = 0, h = 0, bw[3], bh[3], ri = 0;
             int nc = 0;

@@ -697,6 +697,51 @@ IFHIP_API int ifhip_webp_decode_batch_device(const uint8_t* const* files, const 
 IFHIP_API int ifhip_webp_decode(const uint8_t* webp, size_t len, uint8_t* bgra, uint32_t stride, size_t capacity,
                                 uint32_t* status);
 
+/* Device GIF decoder: what GifDecoder (imageflow_core/src/codecs/gif/mod.rs:21-309) hands on for one frame of a file -- the
+ * logical screen after frames 0..frame_index were composed in order with their disposal (gif/screen.rs:25-95,
+ * gif/disposal.rs:29-77), as BGRA with meaningful alpha.  The host walks the container (csrc/gif_read.cpp: header, screen,
+ * colour tables, graphic control extensions, image descriptors, the data sub-blocks gathered into one LZW stream per frame;
+ * unknown extensions are skipped, a missing trailer is the end of the file, mod.rs:123-129); the LZW streams are decoded
+ * and the frames composed on the device (csrc/gif_decode.hip): segment-parallel, a segment being what lies between two
+ * clear codes.
+ * Known differences: the reference's LZW reader (the gif crate) is not on hand -- a stream that yields fewer indices than
+ * width x height is refused (TOO_LITTLE) as Pillow refuses it; indices beyond width x height and bytes behind the end code
+ * are ignored; a code that names an entry the table does not hold yet is BAD_CODE wherever it stands in the stream.  Not
+ * built: multi-frame output, the GIF encoder.
+ *
+ * Status word of a file (d_status[i]): 0, or why no frame was written. */
+#define IFHIP_GIF_DEC_TOO_LITTLE 1       /* a frame's stream holds fewer indices than width x height            */
+#define IFHIP_GIF_DEC_BAD_CODE 2         /* a code that names a table entry which does not exist yet            */
+#define IFHIP_GIF_DEC_CONTAINER 3        /* no GIF signature / screen descriptor, a screen without pixels, a colour table cut short, an unknown block */
+#define IFHIP_GIF_DEC_MIN_CODE_SIZE 4    /* a minimum code size outside 1..8                                    */
+#define IFHIP_GIF_DEC_NO_PALETTE 5       /* a frame with neither a local nor a global colour table (screen.rs:52-57) */
+#define IFHIP_GIF_DEC_FRAME_TOO_LARGE 6  /* a frame of more than 16 Mi indices (mod.rs:226-233)                 */
+#define IFHIP_GIF_DEC_NO_SUCH_FRAME 7    /* frame_index beyond the file's last frame (mod.rs:217-224)           */
+typedef struct ifhip_gif_file_info {
+    uint32_t width, height;              /* the logical screen */
+    uint32_t has_global_palette;
+    uint32_t background_index;
+} ifhip_gif_file_info;
+/* The header's facts (what GifDecoder::create has read, mod.rs:45-101): no frame has been looked at, so a frame count is
+ * not promised.  IFHIP_INVALID_ARGUMENT with an "ImageMalformed: GIF decoding error" message where the signature or the
+ * screen descriptor is missing.  Host only, no device needed. */
+IFHIP_API int ifhip_gif_info(const uint8_t* gif, size_t len, ifhip_gif_file_info* info);
+/* n files (host memory) into n device frames of their logical screens' sizes: file i is decoded and composed up to frame
+ * frame_index[i] (null: frame 0 of every file; GifDecoder::read_frame with SelectFrame, mod.rs:207-298).  d_frames[i] holds
+ * height_i rows of strides[i] bytes inside frame_bytes[i]; only the 4 * width_i bytes of a row are written.  d_status[i]
+ * (device) receives the file's status word; a damaged file leaves its frame untouched and never disturbs its neighbours.
+ * Five launches per batch, every frame of every file in each.  The streams are uploaded before the call returns; the
+ * kernels are asynchronous on hip_stream.  Argument and frame checks come before the device check. */
+IFHIP_API int ifhip_gif_decode_batch_device(const uint8_t* const* files, const size_t* lens, uint32_t n_files, const uint32_t* frame_index,
+                                            uint8_t* const* d_frames, const size_t* frame_bytes, const uint32_t* strides,
+                                            uint32_t* d_status, void* hip_stream);
+/* The synchronous host-buffer drop-in: frame `frame_index` of one file into `height` BGRA rows of `stride` bytes at bgra
+ * (capacity bytes; bytes between rows are kept).  A non-zero status word comes back in *status (nullable) with
+ * IFHIP_INVALID_ARGUMENT and an "ImageMalformed: GIF decoding error" message (NO_SUCH_FRAME: "InvalidArgument: frame=N
+ * requested but GIF only has M frames"). */
+IFHIP_API int ifhip_gif_decode(const uint8_t* gif, size_t len, uint32_t frame_index, uint8_t* bgra, uint32_t stride, size_t capacity,
+                               uint32_t* status);
+
 /* Host, for tests: what the device coder works from -- the Annex K Huffman tables in encode form (dc0, ac0, dc1, ac1; 256
  * entries `code | length << 16`) and the marker segments in front of the scan (SOI ... SOS). */
 IFHIP_API int ifhip_jpeg_debug_encode_tables(uint32_t* tabs4x256, int n_components, const uint8_t* h_samp, const uint8_t* v_samp,

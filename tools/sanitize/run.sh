@@ -2,7 +2,7 @@
 # Host code of the JPEG stages under AddressSanitizer + UndefinedBehaviorSanitizer (no GPU): the file writer on random
 # coefficient planes with every option, and the header parser + un-stuffing + decode-table builders + host walkers
 # (ifhip_jpeg_debug_scan_report) on mutated copies of committed files; the WebP decoder's container walk, prepare and token loop
-# on mutated copies of the tests' files; the querystring parser and layout behind command_string on damaged strings.
+# on mutated copies of the tests' files; the GIF decoder's container walk and the whole batch on the CPU, likewise; the querystring parser and layout behind command_string on damaged strings.
 # Builds into /tmp; prints one summary line each.
 set -eu
 ROOT="$(cd "$(dirname "$0")/../.." && pwd)"
@@ -43,6 +43,21 @@ for name, (data, _) in X.damaged_files().items():
 PY
 )
 ASAN_OPTIONS=detect_leaks=0 ./webp_fuzz case_*.webp
+# the GIF decoder: container walk and the whole batch as the device runs it (plain host code, no HIP) on mutated copies of the tests' files
+g++ $SAN $INC -o gif_fuzz "$ROOT/tools/sanitize/gif_fuzz.cpp" "$ROOT/imageflow_amd/csrc/gif_read.cpp" "$ROOT/tools/sanitize/stubs.cpp"
+(cd "$ROOT" && python3 - <<'PY'
+from tests import gif_fixtures as X
+good = X.good_files()
+for name in ("m1_noise", "m8_runs", "widths_m2_clear_at_full", "deferred_m8_long_tail", "clear_at_64", "mixed_segments", "flat_kwkwk_chain", "interlaced_h9",
+             "dispose_previous_frame2", "dispose_mixed_frame2", "zero_size_frame_then_one", "gif87a_with_extensions", "no_global_palette"):
+    open("/tmp/ifhip_sanitize/case_%s.gif" % name, "wb").write(good[name][0])
+for name, (data, _, _) in X.damaged_files().items():
+    open("/tmp/ifhip_sanitize/case_bad_%s.gif" % name, "wb").write(data)
+for name, data in X.golden_files().items():
+    open("/tmp/ifhip_sanitize/case_golden_%s" % name, "wb").write(data)
+PY
+)
+ASAN_OPTIONS=detect_leaks=0 ./gif_fuzz case_*.gif
 # the querystring layer (Instructions parser, colour reader, Ir4Layout, watermark splitter): untrusted text, plain host code
 g++ $SAN $INC -o querystring_fuzz "$ROOT/tools/sanitize/querystring_fuzz.cpp" "$ROOT/imageflow_amd/csrc/querystring.cpp" "$ROOT/imageflow_amd/csrc/layout.cpp" "$ROOT/tools/sanitize/stubs.cpp"
 ./querystring_fuzz
