@@ -123,10 +123,13 @@ static int parse_headers(const uint8_t* d, size_t len, jo_info* I, size_t* scan_
             uint32_t q = 0;
             while (q < n) {
                 int pq = s[q] >> 4, tq = s[q] & 15;
-                if (pq != 0 || tq > 3) return JO_ERR_UNSUPPORTED;
-                for (int i = 0; i < 64; i++) I->qt[tq][ZIGZAG[i]] = s[q + 1 + i];
+                if (pq > 1 || tq > 3) return JO_ERR_UNSUPPORTED;
+                if (q + 1 + (pq ? 128u : 64u) > n) return JO_ERR_FORMAT;
+                /* Pq = 1: 16-bit entries, high byte first (T.81 B.2.4.1; libjpeg reads them for 8-bit frames as well) */
+                for (int i = 0; i < 64; i++)
+                    I->qt[tq][ZIGZAG[i]] = pq ? (uint16_t)((s[q + 1 + 2 * i] << 8) | s[q + 2 + 2 * i]) : s[q + 1 + i];
                 I->qt_present[tq] = 1;
-                q += 65;
+                q += pq ? 129 : 65;
             }
         } else if (m == 0xC0 || m == 0xC1) {                      /* SOF0 / SOF1 (8-bit) */
             if (s[0] != 8) return JO_ERR_UNSUPPORTED;
