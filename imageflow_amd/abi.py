@@ -72,6 +72,8 @@ def _bind():
     L.ifhip_shim_context_device.restype = C.c_int
     L.ifhip_shim_context_set_color_management.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_color_management.restype = C.c_bool
+    L.ifhip_shim_context_set_gif_encoder.argtypes = [vp, C.c_int]
+    L.ifhip_shim_context_set_gif_encoder.restype = C.c_bool
     L.ifhip_shim_context_set_device_jpeg_options.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_device_jpeg_options.restype = C.c_bool
     L.imageflow_context_memory_allocate.argtypes = [vp, C.c_size_t, C.c_char_p, C.c_int32]
@@ -161,6 +163,11 @@ class Context:
         behind its decode, instead of refusing the job (the decoder command "convert_color_profile" does it for one input;
         "discard_color_profile" wins over both)."""
         return self.L.ifhip_shim_context_set_color_management(self.p, 1 if on else 0)
+
+    def set_gif_encoder(self, on):
+        """EXTENSION, off by default: `encode` with the preset "gif" writes a GIF89a file on the device (image/gif) instead of
+        the raw BGRA container; a GIF input of the job hands on its loop count, delay and user-input flag."""
+        return self.L.ifhip_shim_context_set_gif_encoder(self.p, 1 if on else 0)
 
     def set_device_jpeg_options(self, on):
         """EXTENSION, off by default: entropy-code the libjpeg_turbo preset's progressive / optimize_huffman_coding files on the

@@ -18,7 +18,8 @@
 //     a palette PNG for the pngquant preset (the device quantiser, png_quantize.hip),
 //     a lossless WebP for the webplossless preset (the device coder, webp_encode.hip),
 //     and that container for every other preset (preferred_extension "ifbgra", mime "application/x-imageflow-bgra"):
-//     the lodepng / GIF / lossy WebP coders are out of scope, the caller's encoder takes the frame.
+//     the lodepng / lossy WebP coders are out of scope, the caller's encoder takes the frame;
+//     "gif" is that container too unless ifhip_shim_context_set_gif_encoder switched the device GIF coder on (gif_encode.hip).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -542,6 +543,7 @@ struct imageflow_context {
     std::atomic<int64_t> coalesced_decodes{0};           // decodes of this context that shared their device call with another thread's job
     std::atomic<int> device{-1};                         // device ordinal its jobs run on; -1: the calling thread's current device
     std::atomic<bool> device_jpeg_options{false};        // EXTENSION ifhip_shim_context_set_device_jpeg_options: progressive / optimised tables coded on the device
+    std::atomic<bool> gif_encoder{false};                // EXTENSION ifhip_shim_context_set_gif_encoder: the "gif" preset writes a GIF on the device
     std::atomic<bool> color_management{false};           // EXTENSION ifhip_shim_context_set_color_management: every input is converted to sRGB
     bool cancellation_requested() {
         if (cancel.load(std::memory_order_relaxed)) return true;
@@ -1086,6 +1088,7 @@ struct Job {
     // csrc/gif_decode.hip; frame N's screen enters the graph as bgra_32 with meaningful alpha.  The limits come first, on the
     // header (mod.rs:55-85: max_decode_size, else max_frame_size, on the logical screen).  GIF carries neither EXIF nor a
     // colour profile; the JPEG and WebP hints are accepted and ignored.
+    struct GifSource { bool seen; int repeat; uint32_t delay; bool user_input; } gif_source{false, -1, 0u, false};   // of the first GIF the job decoded
     FramePtr decode_gif(int32_t io_id, Io& in) {
         ifhip::GifParsed P;
         check(ifhip::parse_gif_header(in.in, in.in_len, &P));
@@ -1112,6 +1115,10 @@ struct Job {
         hip_check(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, t_job_stream), "download(status)");
         hip_check(static_cast<hipError_t>(ifhip::wait_stream(t_job_stream)), "decode(gif)");
         if (status) refuse(status);
+        if (!gif_source.seen) {                                                  // what GifEncoder::write_frame asks the job's GIF decoder for (mod.rs:436-483)
+            const ifhip::GifFrameInfo& last = P.frames.back();
+            gif_source = {true, P.repeat < 0 ? 0 : P.repeat, last.delay, last.user_input != 0u};   // (no NETSCAPE2.0 block: get_repeat's Infinite, mod.rs:167-170)
+        }
         decodes.push_back({io_id, P.w, P.h, "image/gif", "gif"});
         return f;
     }
@@ -1592,7 +1599,8 @@ struct Job {
     // EncoderPreset::Libpng is written as a real PNG by the device coder (csrc/png_encode.hip), EncoderPreset::Pngquant as
     // a palette PNG by the device quantiser (csrc/png_quantize.hip), or losslessly where it misses minimum_quality.
     // EncoderPreset::WebPLossless is written as a real lossless WebP by the device coder (csrc/webp_encode.hip).
-    // EXTENSION: every other preset writes the raw BGRA container (lodepng / GIF / lossy WebP coders are out of scope).
+    // EXTENSION: every other preset writes the raw BGRA container (lodepng / lossy WebP coders are out of scope) -- "gif" too,
+    // unless the context's GIF encoder is switched on (ifhip_shim_context_set_gif_encoder): then it is a GIF89a file of the device coder.
     // `shared`: other consumers still read this frame -- the matte is then applied to a private copy.
     void encode(FramePtr f, int32_t io_id, const JVal* preset, bool shared) {
         Timed t(this, "primitive_encoder");
@@ -1788,6 +1796,26 @@ struct Job {
             if (file.status != 0 || file.len == 0) raise(kInternalError, "InternalError: the WebP coder dropped a file sized for its worst case (status %u)", file.status);
             o.written = true;
             encodes.push_back({io_id, f->w, f->h, "image/webp", "webp"});
+            return;
+        }
+        if (preset && preset->t == JVal::Str && preset->s == "gif" && c->gif_encoder.load(std::memory_order_relaxed)) {
+            // EXTENSION (ifhip_shim_context_set_gif_encoder): EncoderPreset::Gif -> GifEncoder::write_frame (codecs/gif/mod.rs:385-592):
+            // the alpha rule, the palette and the LZW stream on the device (csrc/gif_encode.hip), only the file leaves it.  The
+            // frame itself is left as it is (the rule is applied where the pixels are read); a side above 65535 is size_16()'s
+            // InvalidArgument.  A GIF decoder of the job hands on its repeat count and its last frame's delay and user-input flag.
+            ifhip_gif_enc_stage* gs = nullptr;
+            check(ifhip_gif_enc_stage_create(&gs, f->w, f->h, 1));
+            std::unique_ptr<ifhip_gif_enc_stage, void (*)(ifhip_gif_enc_stage*)> gs_guard(gs, [](ifhip_gif_enc_stage* q) { quiesce(); ifhip_gif_enc_stage_destroy(q); });
+            const size_t pitch = (ifhip_gif_enc_stage_max_file_bytes(gs) + 15u) & ~static_cast<size_t>(15u);
+            CodedFile file;
+            hip_check(file.alloc(pitch, pitch), "hipMalloc(gif file)");
+            check(ifhip_gif_encode_batch_device(gs, dev(f), f->bytes(), f->stride, f->alpha ? 1 : 0, 1, gif_source.seen ? gif_source.repeat : -1, gif_source.delay,
+                                                gif_source.user_input ? 1 : 0, file.d, pitch, file.d_len, file.d_len + 1, nullptr, nullptr, t_job_stream));
+            poll_cancel();
+            file.fetch(o);
+            if (file.status != 0 || file.len == 0) raise(kInternalError, "InternalError: the GIF coder dropped a file sized for its worst case (status %u)", file.status);
+            o.written = true;
+            encodes.push_back({io_id, f->w, f->h, "image/gif", "gif"});
             return;
         }
         o.owned.assign(kRawHeader + f->bytes(), 0);
@@ -2476,6 +2504,13 @@ bool ifhip_shim_context_set_device(struct imageflow_context* c, int ordinal) {
 }
 // EXTENSION: colour management for every input of the context's jobs (see Job::color_plan_for); off by default.  Jobs written
 // for the reference run unmodified with it.  discard_color_profile still wins.
+// EXTENSION: the "gif" preset of `encode` writes a GIF on the device (see Job::encode); off by default, where the preset
+// stays the raw-container tap it has always been.
+bool ifhip_shim_context_set_gif_encoder(struct imageflow_context* c, int on) {
+    CTX_OR_ABORT(c);
+    c->gif_encoder.store(on != 0, std::memory_order_relaxed);
+    return true;
+}
 bool ifhip_shim_context_set_color_management(struct imageflow_context* c, int on) {
     CTX_OR_ABORT(c);
     c->color_management.store(on != 0, std::memory_order_relaxed);

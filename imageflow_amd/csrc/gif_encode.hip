@@ -1,0 +1,260 @@
+// gif_encode.hip -- gfx950 kernels + C ABI of the device GIF coder: BGRA / BGRX frames in HBM -> GIF89a files in HBM.
+//
+// Replaces what EncoderPreset::Gif runs on the host (imageflow_core/src/codecs/gif/mod.rs:385-592: gif::Frame::from_rgba's
+// quantisation and the gif crate's LZW writer).  Every rule lives in gif_encode_core.hpp, shared with the CPU emulation of
+// the tests (tests/gif_encode_emulate.cpp); the palette is the quantiser's of png_quantize.hip under the key rule
+// kPqKeyGif.  Launches per batch (all images in each), whatever the frames hold:
+//   * the two clears, the six histogram levels and the palette of png_quantize.hip (pq_launch_palette);
+//   * remap, grid-wide: the nearest palette entry of every pixel, the palette in LDS, an index byte per pixel;
+//   * lzw: a wave per segment of kGifEncSegmentPixels indices, the string table an open-addressed hash in LDS; the
+//     segment's bits go to its private slot, its bit length to the segment's word;
+//   * scan (a workgroup per image): the segments' bit offsets and the total;
+//   * gather: every dword of the frame's stream is assembled by the lane that owns it;
+//   * finish: the stream into 255-byte sub-blocks, the head, the terminator and ';'.
+// The palette's size -- and with it the minimum code size and the head's length -- is read on the device.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+
+#include "block_scan.hpp"
+#include "gif_encode_core.hpp"
+#include "hip_entry.hpp"
+#include "png_quantize.hpp"
+#include "stage_scratch.hpp"
+
+namespace ifhip {
+
+struct GifEncArgs {
+    uint32_t n_seg, slot_words, stream_words;   // per image
+    size_t index_pitch;                         // bytes of an image's indices in the stage
+    uint8_t* indices;                           // [n_images][index_pitch]
+    uint32_t* slots;                            // [n_images][n_seg][slot_words]
+    uint32_t* seg_bits;                         // [n_images][n_seg + 1]: lengths, then exclusive offsets and the total
+    uint32_t* stream;                           // [n_images][stream_words]
+    int32_t repeat;
+    uint32_t delay, user_input;
+};
+
+// ---- remap: grid-wide, no dithering ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kGifEncThreads) void gif_remap_kernel(const QuantArgs a, const GifEncArgs g) {
+    __shared__ PqColor pal[kPqMaxColors];
+    const uint32_t tid = threadIdx.x, img = blockIdx.y;
+    const uint32_t* r = a.result + static_cast<size_t>(img) * kPqResultWords;
+    const uint32_t count = r[0];
+    if (tid < count) pal[tid] = pq_premultiply(r[8u + tid]);
+    __syncthreads();
+    const uint8_t* frame = a.images + static_cast<size_t>(img) * a.image_bytes;
+    uint8_t* out = g.indices + static_cast<size_t>(img) * g.index_pitch;
+    uint8_t* tap = a.indices ? a.indices + static_cast<size_t>(img) * a.w * a.h : nullptr;
+    const uint32_t npix = a.w * a.h;
+    for (uint32_t i = blockIdx.x * kGifEncThreads + tid; i < npix; i += gridDim.x * kGifEncThreads) {
+        const uint32_t y = i / a.w, x = i - y * a.w;
+        const uint32_t px = *reinterpret_cast<const uint32_t*>(frame + static_cast<size_t>(y) * a.stride + 4u * x);
+        uint64_t d;
+        const uint8_t idx = static_cast<uint8_t>(pq_nearest(pal, count, pq_premultiply(pq_key(px, a.alpha != 0u, kPqKeyGif)), &d));
+        out[i] = idx;
+        if (tap) tap[i] = idx;
+    }
+}
+
+// ---- lzw: a wave per segment -------------------------------------------------------------------------------------------------------------
+struct GifEncWave {
+    uint32_t held = 0;
+    __device__ __forceinline__ void fetch(const uint8_t* p, uint32_t base, uint32_t n) { held = base + threadIdx.x < n ? p[base + threadIdx.x] : 0u; }
+    __device__ __forceinline__ uint32_t byte(uint32_t j) const { return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(held), static_cast<int>(j))); }
+    __device__ __forceinline__ uint32_t uniform(uint32_t v) const { return static_cast<uint32_t>(__builtin_amdgcn_readfirstlane(static_cast<int>(v))); }
+    __device__ __forceinline__ void clear(uint32_t* table) {
+        __syncthreads();                                         // (one wave: what the lanes wrote before is ordered before the clear)
+        for (uint32_t i = threadIdx.x; i < kGifEncHashSlots; i += 64u) table[i] = 0u;
+        __syncthreads();
+    }
+    template <typename F> __device__ __forceinline__ void one(F f) { if (threadIdx.x == 0u) f(); }
+};
+
+__global__ __launch_bounds__(64) void gif_lzw_kernel(const QuantArgs a, const GifEncArgs g) {
+    __shared__ uint32_t table[kGifEncHashSlots];
+    const uint32_t seg = blockIdx.x, img = blockIdx.y;
+    const uint32_t npix = a.w * a.h, first_pixel = seg * kGifEncSegmentPixels;
+    const uint32_t n = npix - first_pixel < kGifEncSegmentPixels ? npix - first_pixel : kGifEncSegmentPixels;
+    const uint32_t count = a.result[static_cast<size_t>(img) * kPqResultWords];
+    GifEncWave x;
+    const uint32_t bits = gifenc_segment(x, table, g.indices + static_cast<size_t>(img) * g.index_pitch + first_pixel, n, x.uniform(gifenc_min_code(count)),
+                                         seg == 0u, seg + 1u == g.n_seg, g.slots + (static_cast<size_t>(img) * g.n_seg + seg) * g.slot_words);
+    if (threadIdx.x == 0u) g.seg_bits[static_cast<size_t>(img) * (g.n_seg + 1u) + seg] = bits;
+}
+
+// ---- scan: a workgroup per image -----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kGifEncThreads) void gif_enc_scan_kernel(const GifEncArgs g) {
+    __shared__ uint32_t scratch[kGifEncThreads / 64u];
+    uint32_t* bits = g.seg_bits + static_cast<size_t>(blockIdx.x) * (g.n_seg + 1u);
+    uint32_t base = 0;
+    for (uint32_t s0 = 0; s0 < g.n_seg; s0 += kGifEncThreads) {
+        const uint32_t s = s0 + threadIdx.x, v = s < g.n_seg ? bits[s] : 0u;
+        uint32_t total = 0;
+        const uint32_t before = block_exclusive_scan<kGifEncThreads>(v, scratch, &total);
+        if (s < g.n_seg) bits[s] = base + before;
+        base += total;
+    }
+    if (threadIdx.x == 0u) bits[g.n_seg] = base;
+}
+
+// ---- gather: a lane per dword of the stream -------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kGifEncThreads) void gif_gather_kernel(const GifEncArgs g) {
+    const uint32_t img = blockIdx.y;
+    const uint32_t* off = g.seg_bits + static_cast<size_t>(img) * (g.n_seg + 1u);
+    const uint32_t* slots = g.slots + static_cast<size_t>(img) * g.n_seg * g.slot_words;
+    uint32_t* stream = g.stream + static_cast<size_t>(img) * g.stream_words;
+    const uint32_t words = (off[g.n_seg] + 31u) / 32u;           // (<= stream_words: gifenc_max_data_bytes)
+    for (uint32_t j = blockIdx.x * kGifEncThreads + threadIdx.x; j < words && j < g.stream_words; j += gridDim.x * kGifEncThreads)
+        stream[j] = gifenc_gather_word(off, g.n_seg, slots, g.slot_words, j);
+}
+
+// ---- finish: sub-blocks, head and tail ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kGifEncThreads) void gif_finish_kernel(const QuantArgs a, const GifEncArgs g) {
+    const uint32_t tid = threadIdx.x, img = blockIdx.y;
+    const uint32_t* r = a.result + static_cast<size_t>(img) * kPqResultWords;
+    const uint32_t count = r[0], n_trans = r[1];
+    const uint32_t data = (g.seg_bits[static_cast<size_t>(img) * (g.n_seg + 1u) + g.n_seg] + 7u) / 8u;
+    const uint32_t head = gifenc_head_bytes(count, g.repeat);
+    const uint64_t total = gifenc_file_bytes(head, data);
+    if (total > a.file_pitch) {                                  // (uniform) no file: the neighbours' are not touched
+        if (blockIdx.x == 0u && tid == 0u) { a.lengths[img] = 0u; if (a.status_out) a.status_out[img] = kGifEncFileOverflow; }
+        return;
+    }
+    uint8_t* file = a.files + static_cast<size_t>(img) * a.file_pitch;
+    const uint8_t* src = reinterpret_cast<const uint8_t*>(g.stream + static_cast<size_t>(img) * g.stream_words);
+    for (uint32_t i = blockIdx.x * kGifEncThreads + tid; i < data; i += gridDim.x * kGifEncThreads) {
+        const uint64_t at = head + gifenc_data_position(i);
+        file[at] = src[i];
+        if (i % 255u == 0u) file[at - 1u] = static_cast<uint8_t>(data - i < 255u ? data - i : 255u);
+    }
+    if (blockIdx.x != 0u || tid != 0u) return;
+    gifenc_write_head(file, a.w, a.h, r + 8, count, n_trans, g.repeat, g.delay, g.user_input);
+    file[total - 2u] = 0; file[total - 1u] = 0x3B;
+    a.lengths[img] = static_cast<uint32_t>(total);
+    if (a.status_out) a.status_out[img] = 0u;
+}
+
+}  // namespace ifhip
+
+using namespace ifhip;
+
+struct ifhip_gif_enc_stage {
+    uint32_t width = 0, height = 0, max_images = 0;
+    uint32_t n_seg = 0, stream_words = 0;
+    size_t index_pitch = 0;
+    uint8_t* d_indices = nullptr;
+    uint32_t *d_slots = nullptr, *d_seg_bits = nullptr, *d_stream = nullptr;
+    uint32_t *d_tables = nullptr, *d_ekey = nullptr, *d_ew = nullptr, *d_result = nullptr;   // the quantiser's (the state words lie behind the tables)
+    uint64_t* d_edmin = nullptr;
+    StageScratch blocks{&d_indices, &d_slots, &d_seg_bits, &d_stream, &d_tables, &d_ekey, &d_ew, &d_edmin, &d_result};
+};
+
+namespace {
+int gif_enc_stage_allocate(ifhip_gif_enc_stage* s) {
+    const size_t n = s->max_images;
+    return s->blocks.ensure([&]() -> int {
+        HIP_TRY(DEV_MALLOC(&s->d_indices, n * s->index_pitch));
+        HIP_TRY(DEV_MALLOC(&s->d_slots, n * s->n_seg * gifenc_slot_words() * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_seg_bits, n * (s->n_seg + 1u) * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_stream, n * s->stream_words * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_tables, (quant_table_words(n) + n * kPqStateWords) * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_ekey, n * kPqMaxEntries * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_ew, n * kPqMaxEntries * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_edmin, n * kPqMaxEntries * sizeof(uint64_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_result, n * kPqResultWords * sizeof(uint32_t)));
+        return IFHIP_OK;
+    });
+}
+}  // namespace
+
+extern "C" {
+
+int ifhip_gif_enc_stage_create(ifhip_gif_enc_stage** stage, uint32_t width, uint32_t height, uint32_t max_images) {
+    if (!stage) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null stage out-pointer");
+    *stage = nullptr;
+    if (width == 0 || height == 0) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Bitmap dimensions cannot be zero");
+    // size_16() (codecs/gif/mod.rs:385-592): the logical screen's sides are 16 bits wide
+    if (width > 65535u || height > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: GIF dimensions must be at most 65535 (%ux%u)", width, height);
+    if (max_images == 0 || max_images > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: 1..65535 images per stage");
+    const uint64_t pixels = static_cast<uint64_t>(width) * height;
+    if (pixels > kPqMaxPixels) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: %llu pixels (the quantiser's error sums hold 2^28)", static_cast<unsigned long long>(pixels));
+    std::unique_ptr<ifhip_gif_enc_stage> s(new ifhip_gif_enc_stage);
+    s->width = width; s->height = height; s->max_images = max_images;
+    s->n_seg = gifenc_segments(static_cast<uint32_t>(pixels));
+    s->stream_words = static_cast<uint32_t>((gifenc_max_data_bytes(pixels) + 3u) / 4u);
+    s->index_pitch = (static_cast<size_t>(pixels) + 15u) & ~static_cast<size_t>(15u);
+    *stage = s.release();
+    return IFHIP_OK;
+}
+
+void ifhip_gif_enc_stage_destroy(ifhip_gif_enc_stage* stage) { delete stage; }
+
+size_t ifhip_gif_enc_stage_max_file_bytes(const ifhip_gif_enc_stage* stage) {
+    return stage ? static_cast<size_t>(gifenc_max_file_bytes(static_cast<uint64_t>(stage->width) * stage->height)) : 0u;
+}
+
+int ifhip_gif_encode_batch_device(ifhip_gif_enc_stage* stage, const uint8_t* d_images, size_t image_bytes, uint32_t stride, int alpha_meaningful,
+                                  uint32_t n_images, int repeat, uint32_t delay, int needs_user_input, uint8_t* d_files, size_t file_pitch,
+                                  uint32_t* d_lengths, uint32_t* d_status, uint8_t* d_palettes, uint8_t* d_indices, void* hip_stream) {
+    if (!stage) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null stage");
+    if (n_images == 0) return IFHIP_OK;
+    if (n_images > stage->max_images) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: %u images exceed the stage capacity %u", n_images, stage->max_images);
+    if (int rc = check_frames(d_images, image_bytes, stage->width, stage->height, stride, "image")) return rc;
+    if (!d_files || !d_lengths) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
+    if (repeat < -1 || repeat > 65535) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: repeat is -1 (none) or 0..65535");
+    if (delay > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: delay is 0..65535 hundredths of a second");
+    if (file_pitch < kGifEncHeadMax + 8u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: file_pitch below %u bytes", kGifEncHeadMax + 8u);
+    if (int rc = gif_enc_stage_allocate(stage)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    QuantArgs q;
+    std::memset(&q, 0, sizeof q);
+    q.images = d_images; q.image_bytes = image_bytes; q.stride = stride; q.w = stage->width; q.h = stage->height; q.n_images = n_images;
+    q.alpha = alpha_meaningful ? 1u : 0u; q.max_colors = kPqMaxColors; q.key_rule = kPqKeyGif;
+    // the pngquant preset's defaults (codecs/pngquant.rs:50-57): target 100, minimum 0, speed 4
+    q.iterations = pq_speed_iterations(4u); q.max_entries = pq_speed_max_entries(4u);
+    q.bound_target = pq_quality_bound(100u); q.bound_min = pq_quality_bound(0u);
+    q.tables = stage->d_tables; q.state = stage->d_tables + quant_table_words(stage->max_images);
+    q.ekey = stage->d_ekey; q.ew = stage->d_ew; q.edmin = stage->d_edmin; q.result = stage->d_result;
+    q.palettes = d_palettes; q.indices = d_indices;
+    q.files = d_files; q.file_pitch = file_pitch; q.lengths = d_lengths; q.status_out = d_status;
+    GifEncArgs g;
+    std::memset(&g, 0, sizeof g);
+    g.n_seg = stage->n_seg; g.slot_words = gifenc_slot_words(); g.stream_words = stage->stream_words; g.index_pitch = stage->index_pitch;
+    g.indices = stage->d_indices; g.slots = stage->d_slots; g.seg_bits = stage->d_seg_bits; g.stream = stage->d_stream;
+    g.repeat = repeat; g.delay = delay; g.user_input = needs_user_input ? 1u : 0u;
+    if (int rc = pq_launch_palette(q, st)) return rc;
+    const uint32_t npix = stage->width * stage->height;
+    const uint32_t pixel_blocks = std::min(1024u, (npix + kGifEncThreads - 1u) / kGifEncThreads);
+    const uint32_t word_blocks = std::min(1024u, (stage->stream_words + kGifEncThreads - 1u) / kGifEncThreads);
+    hipLaunchKernelGGL(gif_remap_kernel, dim3(pixel_blocks, n_images), dim3(kGifEncThreads), 0, st, q, g);
+    hipLaunchKernelGGL(gif_lzw_kernel, dim3(stage->n_seg, n_images), dim3(64), 0, st, q, g);
+    hipLaunchKernelGGL(gif_enc_scan_kernel, dim3(n_images), dim3(kGifEncThreads), 0, st, g);
+    hipLaunchKernelGGL(gif_gather_kernel, dim3(word_blocks, n_images), dim3(kGifEncThreads), 0, st, g);
+    hipLaunchKernelGGL(gif_finish_kernel, dim3(word_blocks, n_images), dim3(kGifEncThreads), 0, st, q, g);
+    HIP_TRY(hipGetLastError());
+    return IFHIP_OK;
+}
+
+int ifhip_gif_encode(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int alpha_meaningful, int repeat, uint32_t delay,
+                     int needs_user_input, uint8_t* out, size_t capacity, size_t* len) {
+    if (!len) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null length out-pointer");
+    *len = 0;
+    ifhip_gif_enc_stage* stage = nullptr;
+    if (int rc = ifhip_gif_enc_stage_create(&stage, width, height, 1)) return rc;
+    std::unique_ptr<ifhip_gif_enc_stage, void (*)(ifhip_gif_enc_stage*)> guard(stage, [](ifhip_gif_enc_stage* s) { (void)hipStreamSynchronize(nullptr); ifhip_gif_enc_stage_destroy(s); });
+    const size_t pitch = (ifhip_gif_enc_stage_max_file_bytes(stage) + 15u) & ~static_cast<size_t>(15u);
+    HostFrame f;
+    if (int rc = f.up(bgra, width, height, stride, pitch + 16u)) return rc;
+    uint32_t* d_len = reinterpret_cast<uint32_t*>(f.side_output() + pitch);
+    if (int rc = ifhip_gif_encode_batch_device(stage, f.d, f.image_bytes, stride, alpha_meaningful, 1, repeat, delay, needs_user_input, f.side_output(), pitch,
+                                               d_len, d_len + 1, nullptr, nullptr, nullptr)) return rc;
+    uint32_t word = 0;
+    if (int rc = f.down_file(pitch, out, capacity, len, &word)) return rc;
+    if (word || !*len) return fail(IFHIP_INVALID_STATE, "InvalidState: the file did not fit its worst-case size (status %u)", word);
+    return IFHIP_OK;
+}
+
+}  // extern "C"

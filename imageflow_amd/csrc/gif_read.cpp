@@ -4,7 +4,8 @@
 //     the global table's entry at the background index with alpha 255, (0,0,0,0) without a table or beyond it;
 //   * a graphic control extension (0x21 0xF9, four bytes) belongs to the next image: disposal (values above 3 are Keep, the
 //     frame's default), the transparent index where its flag is set, delay, user input;
-//   * every other extension is skipped, whatever its label (allow_unknown_blocks(true), mod.rs:47);
+//   * every other extension is skipped, whatever its label (allow_unknown_blocks(true), mod.rs:47); of a NETSCAPE2.0
+//     application extension the loop count is noted on the way (the GIF coder of a job writes it again);
 //   * an image: descriptor, local colour table, minimum code size, and the data sub-blocks gathered into ONE contiguous LZW
 //     stream; sub-blocks cut short by the end of the file give what they hold, and the LZW stage decides whether that is enough;
 //   * the end of the file in front of or inside the next frame's header is the end of the stream, trailer or not
@@ -68,6 +69,9 @@ int parse_gif(const uint8_t* d, size_t len, uint32_t target, GifParsed* out) {
                 pending.user_input = (flags >> 1) & 1u;
                 pending.delay = le16(d + pos + 2u);
             }
+            // the application extension NETSCAPE2.0 with the sub-block 03 01 <loop count>: what the GIF coder hands on
+            if (label == 0xFFu && pos + 16u <= len && d[pos] == 11u && std::memcmp(d + pos + 1u, "NETSCAPE2.0", 11) == 0 && d[pos + 12u] == 3u && d[pos + 13u] == 1u)
+                P.repeat = static_cast<int32_t>(le16(d + pos + 14u));
             bool ended = false;
             for (;;) {                                               // the extension's sub-blocks
                 if (pos >= len) { ended = true; break; }

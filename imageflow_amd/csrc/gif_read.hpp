@@ -29,6 +29,7 @@ struct GifParsed {
     std::vector<uint8_t> streams;
     std::vector<GifFrameInfo> frames;    // frames 0 .. target, fewer where the file ends first
     uint32_t status = 0;                 // the IFHIP_GIF_DEC_* word of the walk; non-zero: nothing runs for the file
+    int32_t repeat = -1;                 // the loop count of a NETSCAPE2.0 block in front of the walk's end (0: for ever), -1: none seen
 };
 // The header alone (signature, screen descriptor).  IFHIP_OK, or IFHIP_INVALID_ARGUMENT with an "ImageMalformed: GIF
 // decoding error ..." message.

@@ -22,35 +22,13 @@
 
 #include "hip_entry.hpp"
 #include "png_frame_device.hpp"      // (with png_deflate.hpp)
-#include "png_quantize_core.hpp"
+#include "png_quantize.hpp"           // (with png_quantize_core.hpp)
 
 namespace ifhip {
 
 constexpr uint32_t kPqLanes = 1024;          // the remap's rows in flight: a workgroup's most
 constexpr uint32_t kPqLastRowCols = 16384;   // the widest frame of more than kPqLanes rows: the last lane's error row lies in LDS
-constexpr uint32_t kPqStateWords = 16;       // per image: overflow[kPqLevels], entries[kPqLevels]
-constexpr uint32_t kPqResultWords = 8 + kPqMaxColors;   // count, transparent entries, too low, level, entries, -, error (2 words), keys in file order
 constexpr uint32_t kPqCopyBlocks = 16;
-
-struct QuantArgs {
-    const uint8_t* images;
-    size_t image_bytes;
-    uint32_t stride, w, h, n_images;
-    uint32_t alpha, max_colors, dither, iterations, max_entries, zlib_header;
-    uint64_t bound_target, bound_min;
-    uint32_t* tables;                   // [n_images][kPqLevels][2][kPqSlots]: slots, counts
-    uint32_t* state;                    // [n_images][kPqStateWords]
-    uint32_t *ekey, *ew;                // [n_images][kPqMaxEntries]: the packed histogram
-    uint64_t* edmin;                    // [n_images][kPqMaxEntries]: distance to the nearest entry so far
-    uint32_t* result;                   // [n_images][kPqResultWords]
-    uint8_t* palettes;                  // taps (nullable)
-    uint8_t* indices;
-    double* mse;
-    uint8_t* files;
-    size_t file_pitch;
-    uint32_t* lengths;
-    uint32_t* status_out;
-};
 
 __device__ __forceinline__ bool pq_level_runs(const uint32_t* state, uint32_t level) {
     for (uint32_t q = 0; q < level; ++q) if (!state[q]) return false;      // an earlier level held all colours
@@ -71,7 +49,7 @@ __global__ __launch_bounds__(256) void pngq_histogram_kernel(const QuantArgs a, 
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < npix; i += gridDim.x * 256u) {
         const uint32_t y = i / a.w, x = i - y * a.w;
         const uint32_t px = *reinterpret_cast<const uint32_t*>(frame + static_cast<size_t>(y) * a.stride + 4u * x);
-        if (!pq_insert(slots, counts, state + kPqLevels + level, a.max_entries, pq_posterize(pq_normalize(px, a.alpha != 0u), level), cas, add)) {
+        if (!pq_insert(slots, counts, state + kPqLevels + level, a.max_entries, pq_posterize(pq_key(px, a.alpha != 0u, a.key_rule), level), cas, add)) {
             state[level] = 1u;                                       // the pass is void: the next level runs
             break;
         }
@@ -284,6 +262,17 @@ __global__ __launch_bounds__(256) void pngq_finish_kernel(const QuantArgs a, con
     }
 }
 
+int pq_launch_palette(const QuantArgs& q, hipStream_t st) {
+    // the tables of the images in use and all state words: one clear (an empty slot is 0)
+    HIP_TRY(hipMemsetAsync(q.tables, 0, quant_table_words(q.n_images) * sizeof(uint32_t), st));
+    HIP_TRY(hipMemsetAsync(q.state, 0, static_cast<size_t>(q.n_images) * kPqStateWords * sizeof(uint32_t), st));
+    const uint32_t npix = q.w * q.h, hist_blocks = std::min(256u, (npix + 1023u) / 1024u);
+    for (uint32_t level = 0; level < kPqLevels; ++level)
+        hipLaunchKernelGGL(pngq_histogram_kernel, dim3(hist_blocks, q.n_images), dim3(256), 0, st, q, level);
+    hipLaunchKernelGGL(pngq_palette_kernel, dim3(q.n_images), dim3(kPqLanes), 0, st, q);
+    return IFHIP_OK;
+}
+
 }  // namespace ifhip
 
 using namespace ifhip;
@@ -299,8 +288,6 @@ struct ifhip_png_quant_stage {
 };
 
 namespace {
-size_t quant_table_words(size_t n) { return n * kPqLevels * 2u * kPqSlots; }
-
 int quant_stage_allocate(ifhip_png_quant_stage* s) {
     if (int rc = s->deflate.allocate(s->max_images)) return rc;
     const size_t n = s->max_images;
@@ -374,13 +361,7 @@ int ifhip_png_quantize_batch_device(ifhip_png_quant_stage* stage, const uint8_t*
     q.files = d_files; q.file_pitch = file_pitch; q.lengths = d_lengths; q.status_out = d_status;
     // the zlib body first lands in the stage, which has room for its worst case; finish copies it into its frame
     const PngDeflateArgs a = stage->deflate.args(n_images, zlib_level, stage->d_body, stage->body_pitch, static_cast<uint32_t>(stage->deflate.max_body_bytes() - 6u));
-    // the tables of the images in use and all state words: one clear (an empty slot is 0)
-    HIP_TRY(hipMemsetAsync(q.tables, 0, quant_table_words(n_images) * sizeof(uint32_t), st));
-    HIP_TRY(hipMemsetAsync(q.state, 0, static_cast<size_t>(n_images) * kPqStateWords * sizeof(uint32_t), st));
-    const uint32_t npix = stage->width * stage->height, hist_blocks = std::min(256u, (npix + 1023u) / 1024u);
-    for (uint32_t level = 0; level < kPqLevels; ++level)
-        hipLaunchKernelGGL(pngq_histogram_kernel, dim3(hist_blocks, n_images), dim3(256), 0, st, q, level);
-    hipLaunchKernelGGL(pngq_palette_kernel, dim3(n_images), dim3(kPqLanes), 0, st, q);
+    if (int rc = pq_launch_palette(q, st)) return rc;
     hipLaunchKernelGGL(pngq_remap_kernel, dim3(n_images), dim3(kPqLanes), 0, st, q, a);
     png_launch_deflate(a, st);
     hipLaunchKernelGGL(pngq_finish_kernel, dim3(kPqCopyBlocks, n_images), dim3(256), 0, st, q, a);

@@ -38,6 +38,13 @@ IFHIP_HD uint32_t pq_normalize(uint32_t bgra, bool alpha_meaningful) {
     if (!alpha_meaningful) return bgra | 0xFF000000u;
     return (bgra >> 24) ? bgra : 0u;
 }
+// The key rule of a coder (QuantArgs::key_rule).  kPqKeyPng: pq_normalize.  kPqKeyGif: what GifEncoder::write_frame prepares
+// (codecs/gif/mod.rs:385-592): a pixel of meaningful alpha below 0x10 is 00 00 00 00, every other pixel is opaque.
+constexpr uint32_t kPqKeyPng = 0, kPqKeyGif = 1;
+IFHIP_HD uint32_t pq_key(uint32_t bgra, bool alpha_meaningful, uint32_t rule) {
+    if (rule == kPqKeyGif) return alpha_meaningful && (bgra >> 24) < 0x10u ? 0u : bgra | 0xFF000000u;
+    return pq_normalize(bgra, alpha_meaningful);
+}
 IFHIP_HD uint32_t pq_posterize_channel(uint32_t c, uint32_t bits) {    // low bits dropped, the high ones repeated into them (255 stays 255)
     const uint32_t hi = c & ~((1u << bits) - 1u) & 255u;
     uint32_t v = hi;

@@ -127,6 +127,10 @@ IMAGEFLOW_SHIM_API int ifhip_shim_context_device(struct imageflow_context *conte
  * cHRM.  Still refused, naming the case: GRAY / CMYK spaces, a Lab PCS, LUT-based profiles.  A malformed profile is a
  * ColorProfileError (ImageMalformed) unless the decoder was told "ignore_color_profile_errors".  Returns true. */
 IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_color_management(struct imageflow_context *context, int on);
+/* EXTENSION: `encode` with the preset "gif" writes a GIF89a file on the device (ifhip_gif_encode_batch_device: GifEncoder::write_frame,
+ * codecs/gif/mod.rs:385-592) and reports image/gif; off by default, where the preset writes the raw BGRA container as ever.  A
+ * GIF input of the job hands its loop count and the selected frame's delay and user-input flag to the file. */
+IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_gif_encoder(struct imageflow_context *context, int on);
 /* EXTENSION.  Device coding of the libjpeg_turbo preset's options, off by default: with on != 0 an encode with
  * "progressive" and / or "optimize_huffman_coding" is entropy-coded on the device (ifhip_jpeg_encode_flags_batch_device:
  * only the file is downloaded, not the coefficient planes) -- first with room for streams half the size of the

@@ -707,7 +707,7 @@ IFHIP_API int ifhip_webp_decode(const uint8_t* webp, size_t len, uint8_t* bgra, 
  * Known differences: the reference's LZW reader (the gif crate) is not on hand -- a stream that yields fewer indices than
  * width x height is refused (TOO_LITTLE) as Pillow refuses it; indices beyond width x height and bytes behind the end code
  * are ignored; a code that names an entry the table does not hold yet is BAD_CODE wherever it stands in the stream.  Not
- * built: multi-frame output, the GIF encoder.
+ * built: multi-frame output.
  *
  * Status word of a file (d_status[i]): 0, or why no frame was written. */
 #define IFHIP_GIF_DEC_TOO_LITTLE 1       /* a frame's stream holds fewer indices than width x height            */
@@ -741,6 +741,43 @@ IFHIP_API int ifhip_gif_decode_batch_device(const uint8_t* const* files, const s
  * requested but GIF only has M frames"). */
 IFHIP_API int ifhip_gif_decode(const uint8_t* gif, size_t len, uint32_t frame_index, uint8_t* bgra, uint32_t stride, size_t capacity,
                                uint32_t* status);
+
+/* Device GIF coder: EncoderPreset::Gif without the host: what GifEncoder::write_frame (imageflow_core/src/codecs/gif/mod.rs:385-592)
+ * has the gif crate do -- one frame as a GIF89a file: the logical screen of the frame's size (size_16(): both sides at most
+ * 65535) without a global colour table, an optional NETSCAPE2.0 block, a graphic control extension, the image with a local
+ * colour table of at most 256 entries (padded with black to a power of two), no dithering -- on BGRA / BGRX frames that
+ * stay in HBM.  A pixel of meaningful alpha below 16 becomes the transparent entry, which is then entry 0; every other
+ * pixel counts as opaque.  The palette is this library's own (the integer quantiser of the palette PNG coder above, at its
+ * defaults: target 100, minimum 0, speed 4): a frame of at most 256 distinct colours after the alpha rule keeps exactly
+ * those; otherwise it is NOT the gif crate's NeuQuant palette.  The LZW stream carries a clear code every
+ * IFHIP_GIF_ENC_SEGMENT_PIXELS pixels, so that a wave codes a segment on its own (csrc/gif_encode.hip); every reader takes
+ * it.  Not built: multi-frame output, dithering.  A stage owns the scratch of a call in flight and is bound to ONE stream
+ * at a time, like ifhip_png_quant_stage. */
+#ifndef IFHIP_GIF_ENC_SEGMENT_PIXELS
+#define IFHIP_GIF_ENC_SEGMENT_PIXELS 16384
+#endif
+#define IFHIP_GIF_FILE_OVERFLOW 1
+typedef struct ifhip_gif_enc_stage ifhip_gif_enc_stage;
+/* refused: zero dimensions, a side above 65535 ("InvalidArgument"), more than 2^28 pixels */
+IFHIP_API int ifhip_gif_enc_stage_create(ifhip_gif_enc_stage** stage, uint32_t width, uint32_t height, uint32_t max_images);
+IFHIP_API void ifhip_gif_enc_stage_destroy(ifhip_gif_enc_stage* stage);
+/* a file_pitch with which no file overflows, by arithmetic alone: every pixel a 12-bit code, the clear codes of full tables
+ * and of the segments, a length byte per 255 data bytes, the head with NETSCAPE2.0 and 256 entries, the tail */
+IFHIP_API size_t ifhip_gif_enc_stage_max_file_bytes(const ifhip_gif_enc_stage* stage);
+/* n_images frames as in ifhip_png_quantize_batch_device.  alpha_meaningful 0: every pixel is opaque (Bgr32).  repeat: the
+ * loop count of the NETSCAPE2.0 block (0: for ever), -1: no block.  delay (hundredths of a second, 0..65535) and
+ * needs_user_input go into the graphic control extension.  Image i's file goes to d_files + i * file_pitch and its length
+ * to d_lengths[i] -- 0 when the file is longer than file_pitch, with IFHIP_GIF_FILE_OVERFLOW in d_status[i] (nullable).
+ * Nullable taps: d_palettes (per image 256 RGBA entries in file order, then the count as a little-endian u32: 1028 bytes),
+ * d_indices (per image width * height palette indices).  A fixed number of launches per batch; nothing is read back.
+ * Asynchronous on hip_stream.  The same pixels give the same bytes on every run and in every batch position. */
+IFHIP_API int ifhip_gif_encode_batch_device(ifhip_gif_enc_stage* stage, const uint8_t* d_images, size_t image_bytes, uint32_t stride,
+                                            int alpha_meaningful, uint32_t n_images, int repeat, uint32_t delay, int needs_user_input,
+                                            uint8_t* d_files, size_t file_pitch, uint32_t* d_lengths, uint32_t* d_status,
+                                            uint8_t* d_palettes, uint8_t* d_indices, void* hip_stream);
+/* The synchronous host-buffer form: one frame.  out == NULL: only *len (the size needed) is written. */
+IFHIP_API int ifhip_gif_encode(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int alpha_meaningful, int repeat,
+                               uint32_t delay, int needs_user_input, uint8_t* out, size_t capacity, size_t* len);
 
 /* Host, for tests: what the device coder works from -- the Annex K Huffman tables in encode form (dc0, ac0, dc1, ac1; 256
  * entries `code | length << 16`) and the marker segments in front of the scan (SOI ... SOS). */
