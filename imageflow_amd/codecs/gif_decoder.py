@@ -5,11 +5,10 @@ GIF io_id and the decoder command {"select_frame": N} (csrc/abi_shim.cpp)."""
 import ctypes as C
 
 import numpy as np
-import torch
 
 from .. import _native
 from ..errors import ErrorKind, FlowError
-from ..graphics.bitmaps import Bitmap, get_stride
+from ._file_decoder import decode_batch, decode_host
 
 # include/imageflow_hip.h IFHIP_GIF_DEC_*
 STATUS = {0: "ok", 1: "too_little", 2: "bad_code", 3: "container", 4: "min_code_size", 5: "no_palette", 6: "frame_too_large", 7: "no_such_frame"}
@@ -49,30 +48,9 @@ def decode_gif_batch(files, frame_index=None, device="cuda:0", frames=None, fill
     where the header did not parse or describes no pixels), status[i] the file's status word.  frames: Bitmaps to decode into
     (their strides are honoured); fill: a byte the new frames are filled with first."""
     L = _bind()
-    device = torch.device(device)
-    n = len(files)
-    bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
-    out = list(frames) if frames is not None else [None] * n
-    for i, b in enumerate(bufs):
-        if out[i] is not None:
-            continue
-        info = GifFileInfo()
-        if L.ifhip_gif_info(b.ctypes.data, b.size, C.byref(info)) != 0 or not info.width or not info.height:
-            continue
-        stride = get_stride(info.width)
-        data = torch.full((1, info.height * stride), 0 if fill is None else fill, dtype=torch.uint8, device=device)
-        out[i] = Bitmap(data, info.width, info.height, stride, alpha_meaningful=True)
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[b.size for b in bufs])
-    want = (C.c_uint32 * n)(*[int(v) for v in frame_index]) if frame_index is not None else None
-    d_frames = (C.c_void_p * n)(*[o.data.data_ptr() if o is not None else None for o in out])
-    frame_bytes = (C.c_size_t * n)(*[o.data.shape[1] if o is not None else 0 for o in out])
-    strides = (C.c_uint32 * n)(*[o.stride if o is not None else 0 for o in out])
-    status = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
-    stream = torch.cuda.current_stream(device).cuda_stream
-    with torch.cuda.device(device):
-        _native.check(L.ifhip_gif_decode_batch_device(ptrs, lens, n, want, d_frames, frame_bytes, strides, status.data_ptr(), C.c_void_p(stream)))
-    return out, [int(s) for s in status.cpu().numpy()[:n]]
+    want = (C.c_uint32 * len(files))(*[int(v) for v in frame_index]) if frame_index is not None else None
+    return decode_batch(L.ifhip_gif_info, L.ifhip_gif_decode_batch_device, GifFileInfo, lambda info: bool(info.width and info.height), lambda info: True,
+                        files, device, frames, fill, lead=(want,))
 
 
 def decode_gif(data, frame_index=0, device="cuda:0"):
@@ -86,12 +64,4 @@ def decode_gif(data, frame_index=0, device="cuda:0"):
 def decode_gif_host(data, frame_index=0, stride=None, out=None):
     """Host-buffer drop-in (numpy): the file -> BGRA rows [h, stride] uint8."""
     L = _bind()
-    buf = np.frombuffer(bytes(data), np.uint8)
-    info = GifFileInfo()
-    _native.check(L.ifhip_gif_info(buf.ctypes.data, buf.size, C.byref(info)))
-    stride = stride or 4 * info.width
-    if out is None:
-        out = np.zeros((info.height, stride), np.uint8)
-    status = C.c_uint32(0)
-    _native.check(L.ifhip_gif_decode(buf.ctypes.data, buf.size, frame_index, out.ctypes.data, stride, out.size, C.byref(status)))
-    return out
+    return decode_host(L.ifhip_gif_info, L.ifhip_gif_decode, GifFileInfo, data, stride, out, lead=(frame_index,))

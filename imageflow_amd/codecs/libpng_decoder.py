@@ -5,11 +5,10 @@ and the Adam7 scatter on the GPU.  For tests and tools; the job path is `decode`
 import ctypes as C
 
 import numpy as np
-import torch
 
 from .. import _native
 from ..errors import ErrorKind, FlowError
-from ..graphics.bitmaps import Bitmap, get_stride
+from ._file_decoder import decode_batch, decode_host
 
 # include/imageflow_hip.h IFHIP_PNG_DEC_*
 STATUS = {0: "ok", 1: "truncated", 2: "block_type", 3: "stored_length", 4: "code_lengths", 5: "bad_code", 6: "distance", 7: "zlib_header",
@@ -50,29 +49,8 @@ def decode_png_batch(files, device="cuda:0", frames=None, fill=None):
     status): frames[i] a Bitmap of one frame (None where the file's chunks did not parse), status[i] the file's status word.
     frames: Bitmaps to decode into (their strides are honoured); fill: a byte the new frames are filled with first."""
     L = _bind()
-    device = torch.device(device)
-    n = len(files)
-    bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
-    out = list(frames) if frames is not None else [None] * n
-    for i, b in enumerate(bufs):
-        if out[i] is not None:
-            continue
-        info = PngFileInfo()
-        if L.ifhip_png_info(b.ctypes.data, b.size, C.byref(info)) != 0:
-            continue
-        stride = get_stride(info.width)
-        data = torch.full((1, info.height * stride), 0 if fill is None else fill, dtype=torch.uint8, device=device)
-        out[i] = Bitmap(data, info.width, info.height, stride, alpha_meaningful=bool(info.alpha_used))
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[b.size for b in bufs])
-    d_frames = (C.c_void_p * n)(*[o.data.data_ptr() if o is not None else None for o in out])
-    frame_bytes = (C.c_size_t * n)(*[o.data.shape[1] if o is not None else 0 for o in out])
-    strides = (C.c_uint32 * n)(*[o.stride if o is not None else 0 for o in out])
-    status = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
-    stream = torch.cuda.current_stream(device).cuda_stream
-    with torch.cuda.device(device):
-        _native.check(L.ifhip_png_decode_batch_device(ptrs, lens, n, d_frames, frame_bytes, strides, status.data_ptr(), C.c_void_p(stream)))
-    return out, [int(s) for s in status.cpu().numpy()[:n]]
+    return decode_batch(L.ifhip_png_info, L.ifhip_png_decode_batch_device, PngFileInfo, lambda info: True, lambda info: bool(info.alpha_used),
+                        files, device, frames, fill)
 
 
 def decode_png(data, device="cuda:0"):
@@ -86,12 +64,4 @@ def decode_png(data, device="cuda:0"):
 def decode_png_host(data, stride=None, out=None):
     """Host-buffer drop-in (numpy): the file -> BGRA rows [h, stride] uint8."""
     L = _bind()
-    buf = np.frombuffer(bytes(data), np.uint8)
-    info = PngFileInfo()
-    _native.check(L.ifhip_png_info(buf.ctypes.data, buf.size, C.byref(info)))
-    stride = stride or 4 * info.width
-    if out is None:
-        out = np.zeros((info.height, stride), np.uint8)
-    status = C.c_uint32(0)
-    _native.check(L.ifhip_png_decode(buf.ctypes.data, buf.size, out.ctypes.data, stride, out.size, C.byref(status)))
-    return out
+    return decode_host(L.ifhip_png_info, L.ifhip_png_decode, PngFileInfo, data, stride, out)

@@ -4,11 +4,10 @@ inverse transforms on the GPU.  For tests and tools; the job path is `decode` wi
 import ctypes as C
 
 import numpy as np
-import torch
 
 from .. import _native
 from ..errors import ErrorKind, FlowError
-from ..graphics.bitmaps import Bitmap, get_stride
+from ._file_decoder import decode_batch, decode_host
 
 # include/imageflow_hip.h IFHIP_WEBP_DEC_*
 STATUS = {0: "ok", 1: "truncated", 2: "code_lengths", 3: "bad_code", 4: "distance", 5: "copy_end", 6: "cache_symbol", 7: "transform",
@@ -51,29 +50,8 @@ def decode_webp_batch(files, device="cuda:0", frames=None, fill=None):
     holds no lossless image), status[i] the file's status word.  frames: Bitmaps to decode into (their strides are
     honoured); fill: a byte the new frames are filled with first."""
     L = _bind()
-    device = torch.device(device)
-    n = len(files)
-    bufs = [np.frombuffer(bytes(f), np.uint8) for f in files]
-    out = list(frames) if frames is not None else [None] * n
-    for i, b in enumerate(bufs):
-        if out[i] is not None:
-            continue
-        info = WebpFileInfo()
-        if L.ifhip_webp_info(b.ctypes.data, b.size, C.byref(info)) != 0 or not info.lossless:
-            continue
-        stride = get_stride(info.width)
-        data = torch.full((1, info.height * stride), 0 if fill is None else fill, dtype=torch.uint8, device=device)
-        out[i] = Bitmap(data, info.width, info.height, stride, alpha_meaningful=bool(info.has_alpha))
-    ptrs = (C.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (C.c_size_t * n)(*[b.size for b in bufs])
-    d_frames = (C.c_void_p * n)(*[o.data.data_ptr() if o is not None else None for o in out])
-    frame_bytes = (C.c_size_t * n)(*[o.data.shape[1] if o is not None else 0 for o in out])
-    strides = (C.c_uint32 * n)(*[o.stride if o is not None else 0 for o in out])
-    status = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
-    stream = torch.cuda.current_stream(device).cuda_stream
-    with torch.cuda.device(device):
-        _native.check(L.ifhip_webp_decode_batch_device(ptrs, lens, n, d_frames, frame_bytes, strides, status.data_ptr(), C.c_void_p(stream)))
-    return out, [int(s) for s in status.cpu().numpy()[:n]]
+    return decode_batch(L.ifhip_webp_info, L.ifhip_webp_decode_batch_device, WebpFileInfo, lambda info: bool(info.lossless), lambda info: bool(info.has_alpha),
+                        files, device, frames, fill)
 
 
 def decode_webp(data, device="cuda:0"):
@@ -87,12 +65,4 @@ def decode_webp(data, device="cuda:0"):
 def decode_webp_host(data, stride=None, out=None):
     """Host-buffer drop-in (numpy): the file -> BGRA rows [h, stride] uint8."""
     L = _bind()
-    buf = np.frombuffer(bytes(data), np.uint8)
-    info = WebpFileInfo()
-    _native.check(L.ifhip_webp_info(buf.ctypes.data, buf.size, C.byref(info)))
-    stride = stride or 4 * info.width
-    if out is None:
-        out = np.zeros((info.height, stride), np.uint8)
-    status = C.c_uint32(0)
-    _native.check(L.ifhip_webp_decode(buf.ctypes.data, buf.size, out.ctypes.data, stride, out.size, C.byref(status)))
-    return out
+    return decode_host(L.ifhip_webp_info, L.ifhip_webp_decode, WebpFileInfo, data, stride, out)

@@ -1011,6 +1011,19 @@ struct Job {
     void convert_to_srgb(const FramePtr& f, const ifhip_color_plan& plan) {
         check(ifhip_color_transform_batch_device(dev(f), f->bytes(), 1, f->w, f->h, f->stride, &plan, t_job_stream));
     }
+    // one file through a decoder's device part on the job's stream: queue(d_status) launches it; -> the file's status word, waited for
+    template <typename Queue>
+    uint32_t decoded_status(const char* label, Queue queue) {
+        uint32_t* d_status = nullptr;
+        hip_check(job_malloc(reinterpret_cast<void**>(&d_status), 16), "hipMalloc(status)");
+        struct Guard { void* p; ~Guard() { job_free(p); } } guard{d_status};
+        poll_cancel();
+        check(queue(d_status));
+        uint32_t status = 0;
+        hip_check(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, t_job_stream), "download(status)");
+        hip_check(static_cast<hipError_t>(ifhip::wait_stream(t_job_stream)), label);
+        return status;
+    }
 
     // LibPngDecoder::read_frame (codecs/libpng_decoder.rs:82-104 -> c_components/lib/codec_png_wrapper.c:131-246) on the device:
     // the host walks the chunks, the IDAT stream is inflated, un-filtered and expanded to BGRA by csrc/png_decode.hip.  The
@@ -1033,16 +1046,9 @@ struct Job {
         }
         if (P.inflated > 0x7FFF0000ull) raise(kImageMalformed, "ImageMalformed: LibPNG error: the image data of io_id %d would inflate beyond 2^31 bytes", io_id);
         FramePtr f = new_frame(P.w, P.h, P.alpha_used, 0, true);                      // (max_frame_size inside)
-        uint32_t* d_status = nullptr;
-        hip_check(job_malloc(reinterpret_cast<void**>(&d_status), 16), "hipMalloc(status)");
-        struct Guard { void* p; ~Guard() { job_free(p); } } guard{d_status};
         const ifhip::PngParsed* parsed = &P;
         const size_t bytes = f->bytes();
-        poll_cancel();
-        check(ifhip::png_decode_parsed_device(&parsed, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream));
-        uint32_t status = 0;
-        hip_check(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, t_job_stream), "download(status)");
-        hip_check(static_cast<hipError_t>(ifhip::wait_stream(t_job_stream)), "decode(png)");
+        const uint32_t status = decoded_status("decode(png)", [&](uint32_t* d_status) { return ifhip::png_decode_parsed_device(&parsed, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream); });
         if (status) raise(kImageMalformed, "ImageMalformed: LibPNG error: %s (io_id %d, status %u)", ifhip::png_status_text(status), io_id, status);
         if (convert) convert_to_srgb(f, color_plan);
         decodes.push_back({io_id, P.w, P.h, "image/png", "png"});
@@ -1067,16 +1073,9 @@ struct Job {
         ifhip::WebpJob J;
         ifhip::webp_prepare_job(P, &J);                                               // on this job's thread, like ifhip_jpeg_entropy_prepare
         if (J.status) raise(kImageMalformed, "ImageMalformed: libwebp decoding error %s (io_id %d, status %u)", ifhip::webp_status_text(J.status), io_id, J.status);
-        uint32_t* d_status = nullptr;
-        hip_check(job_malloc(reinterpret_cast<void**>(&d_status), 16), "hipMalloc(status)");
-        struct Guard { void* p; ~Guard() { job_free(p); } } guard{d_status};
         const ifhip::WebpJob* job = &J;
         const size_t bytes = f->bytes();
-        poll_cancel();
-        check(ifhip::webp_decode_prepared_device(&job, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream));
-        uint32_t status = 0;
-        hip_check(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, t_job_stream), "download(status)");
-        hip_check(static_cast<hipError_t>(ifhip::wait_stream(t_job_stream)), "decode(webp)");
+        const uint32_t status = decoded_status("decode(webp)", [&](uint32_t* d_status) { return ifhip::webp_decode_prepared_device(&job, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream); });
         if (status) raise(kImageMalformed, "ImageMalformed: libwebp decoding error %s (io_id %d, status %u)", ifhip::webp_status_text(status), io_id, status);
         if (convert) convert_to_srgb(f, color_plan);
         decodes.push_back({io_id, P.w, P.h, "image/webp", "webp"});
@@ -1104,16 +1103,9 @@ struct Job {
         };
         if (P.status) refuse(P.status);
         FramePtr f = new_frame(P.w, P.h, true, 0, true);
-        uint32_t* d_status = nullptr;
-        hip_check(job_malloc(reinterpret_cast<void**>(&d_status), 16), "hipMalloc(status)");
-        struct Guard { void* p; ~Guard() { job_free(p); } } guard{d_status};
         const ifhip::GifParsed* parsed = &P;
         const size_t bytes = f->bytes();
-        poll_cancel();
-        check(ifhip::gif_decode_parsed_device(&parsed, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream));
-        uint32_t status = 0;
-        hip_check(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, t_job_stream), "download(status)");
-        hip_check(static_cast<hipError_t>(ifhip::wait_stream(t_job_stream)), "decode(gif)");
+        const uint32_t status = decoded_status("decode(gif)", [&](uint32_t* d_status) { return ifhip::gif_decode_parsed_device(&parsed, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream); });
         if (status) refuse(status);
         if (!gif_source.seen) {                                                  // what GifEncoder::write_frame asks the job's GIF decoder for (mod.rs:436-483)
             const ifhip::GifFrameInfo& last = P.frames.back();

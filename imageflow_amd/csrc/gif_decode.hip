@@ -28,9 +28,9 @@
 #include <vector>
 
 #include "block_scan.hpp"
+#include "decode_handoff.hpp"
 #include "gif_decode_core.hpp"
 #include "gif_read.hpp"
-#include "hip_entry.hpp"
 
 namespace ifhip {
 
@@ -131,21 +131,12 @@ int gif_decode_parsed_device(const GifParsed* const* files, uint32_t n_files, ui
     GifLayout L;
     gif_layout_batch(files, n_files, d_frames, strides, &L);
     if (L.n_frames > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: 65535 frames per batch at the most");
-    if (int rc = require_gfx950(nullptr)) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    uint8_t* block = nullptr;
-    HIP_TRY(DEV_MALLOC(&block, L.total + 16u));
-    struct Release { uint8_t* p; hipStream_t st; ~Release() { (void)cached_free_after(p, st); } } release{block, st};
-    {
-        void* pin = nullptr;
-        const uint8_t* host = L.blob.data();
-        if (cached_host_malloc(&pin, L.blob.size()) == 0) { std::memcpy(pin, L.blob.data(), L.blob.size()); host = static_cast<const uint8_t*>(pin); }
-        hipError_t e = hipMemcpyAsync(block, host, L.blob.size(), hipMemcpyHostToDevice, st);
-        const hipError_t w = static_cast<hipError_t>(wait_stream(st));      // the staging block is free again on return
-        if (pin) (void)cached_host_free(pin);
-        HIP_TRY(e);
-        HIP_TRY(w);
-    }
+    StagedBlock staged(st);
+    if (int rc = staged.alloc(L.total, L.blob.size())) return rc;
+    uint8_t* const block = staged.block;
+    std::memcpy(staged.host, L.blob.data(), L.blob.size());           // (gif_layout_batch fills L.blob for the CPU emulation as well)
+    if (int rc = staged.send()) return rc;
     GifDecArgs a;
     a.block = block; a.files = reinterpret_cast<const GifFileDesc*>(block + L.files_off); a.frames = reinterpret_cast<const GifFrameDesc*>(block + L.frames_off);
     a.state = reinterpret_cast<GifFrameState*>(block + L.state_off); a.status = d_status; a.n_files = n_files; a.n_frames = L.n_frames;
@@ -183,43 +174,28 @@ extern "C" {
 int ifhip_gif_decode_batch_device(const uint8_t* const* files, const size_t* lens, uint32_t n_files, const uint32_t* frame_index, uint8_t* const* d_frames,
                                   const size_t* frame_bytes, const uint32_t* strides, uint32_t* d_status, void* hip_stream) {
     if (n_files == 0) return IFHIP_OK;
-    if (!files || !lens || !d_frames || !frame_bytes || !strides || !d_status) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
-    if (n_files > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: 1..65535 files per batch");
-    std::vector<GifParsed> parsed(n_files);
-    std::vector<const GifParsed*> ok(n_files, nullptr);
-    for (uint32_t i = 0; i < n_files; ++i) {
-        if (!files[i]) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null file pointer (file %u)", i);
-        if (parse_gif(files[i], lens[i], frame_index ? frame_index[i] : 0u, &parsed[i]) == IFHIP_OK && parsed[i].w && parsed[i].h) ok[i] = &parsed[i];
-    }
+    std::vector<GifParsed> parsed;
+    std::vector<const GifParsed*> ok;
+    auto parse = [&](const uint8_t* file, size_t len, uint32_t i, GifParsed* P) { return parse_gif(file, len, frame_index ? frame_index[i] : 0u, P) == IFHIP_OK && P->w && P->h; };
+    if (int rc = walk_decode_batch(files, lens, n_files, d_frames, frame_bytes, strides, d_status, &parsed, &ok, parse)) return rc;
     return gif_decode_parsed_device(ok.data(), n_files, d_frames, frame_bytes, strides, d_status, hip_stream);
 }
 
 int ifhip_gif_decode(const uint8_t* gif, size_t len, uint32_t frame_index, uint8_t* bgra, uint32_t stride, size_t capacity, uint32_t* status) {
-    if (status) *status = 0;
+    uint32_t word = 0;
+    if (!status) status = &word;
+    *status = 0;
     if (!gif) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null file pointer");
     GifParsed P;
     if (int rc = parse_gif(gif, len, frame_index, &P)) return rc;
     if (!P.w || !P.h) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: GIF decoding error (a logical screen without pixels)");
-    if (!bgra) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null bitmap pointer");
-    if (static_cast<uint64_t>(P.w) * 4u > stride || (stride & 3u)) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: stride smaller than a BGRA row or not a multiple of 4");
-    if (static_cast<uint64_t>(P.h - 1u) * stride + 4ull * P.w > capacity)
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: the frame needs %llu bytes, the buffer has %zu", static_cast<unsigned long long>(static_cast<uint64_t>(P.h - 1u) * stride + 4ull * P.w), capacity);
-    if (P.status) {
-        if (status) *status = P.status;
-        return refuse(P.status, frame_index, P.frames.size());
-    }
-    HostFrame f;
-    if (int rc = f.up(bgra, P.w, P.h, stride, 16u)) return rc;
-    uint8_t* frames[1] = {f.d};
-    const size_t bytes[1] = {f.image_bytes};
-    const uint32_t strides[1] = {stride};
-    const GifParsed* files[1] = {&P};
-    uint32_t* d_status = reinterpret_cast<uint32_t*>(f.side_output());
-    if (int rc = gif_decode_parsed_device(files, 1, frames, bytes, strides, d_status, nullptr)) return rc;
-    uint32_t side[4] = {0, 0, 0, 0};
-    if (int rc = f.down(bgra, side)) return rc;
-    if (status) *status = side[0];
-    if (side[0]) return refuse(side[0], frame_index, P.frames.size());
+    if (int rc = check_decode_destination(bgra, P.w, P.h, stride, capacity)) return rc;
+    const GifParsed* parsed = &P;
+    auto device = [&](uint8_t* frame, size_t bytes, uint32_t at_stride, uint32_t* d_status) { return gif_decode_parsed_device(&parsed, 1, &frame, &bytes, &at_stride, d_status, nullptr); };
+    *status = P.status;                                           // what the host walk finds needs no device
+    if (!*status)
+        if (int rc = decode_to_host_frame(P.w, P.h, bgra, stride, device, status)) return rc;
+    if (*status) return refuse(*status, frame_index, P.frames.size());
     return IFHIP_OK;
 }
 

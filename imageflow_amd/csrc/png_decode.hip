@@ -30,7 +30,7 @@
 #include <memory>
 #include <vector>
 
-#include "hip_entry.hpp"
+#include "decode_handoff.hpp"
 #include "png_decode_core.hpp"
 #include "png_read.hpp"
 
@@ -194,38 +194,27 @@ int png_decode_parsed_device(const PngParsed* const* parsed, uint32_t n_files, u
     }
     if (max_pixels > 256ull * 0x7FFFFFFFull) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: a frame of %llu pixels exceeds the launch grid", static_cast<unsigned long long>(max_pixels));
     // the block: descriptors, palette tables, the streams (what is uploaded), then the inflated images
-    const size_t desc_bytes = (sizeof(PngFile) * n_files + 15u) & ~static_cast<size_t>(15), pal_bytes = static_cast<size_t>(n_palettes) * 1024u;
+    const size_t desc_bytes = pad16(sizeof(PngFile) * n_files), pal_bytes = static_cast<size_t>(n_palettes) * 1024u;
     blob = desc_bytes + pal_bytes;
-    for (uint32_t i = 0; i < n_files; ++i) if (!desc[i].preset_status) { desc[i].stream_off = blob; blob += (parsed[i]->idat_len + 15u) & ~static_cast<size_t>(15); }
+    for (uint32_t i = 0; i < n_files; ++i) if (!desc[i].preset_status) { desc[i].stream_off = blob; blob += pad16(parsed[i]->idat_len); }
     for (uint32_t i = 0; i < n_files; ++i)
-        if (!desc[i].preset_status) { desc[i].inflated_off = blob + inflated_total; inflated_total += (static_cast<size_t>(desc[i].inflated) + 15u) & ~static_cast<size_t>(15); }
-    if (int rc = require_gfx950(nullptr)) return rc;
+        if (!desc[i].preset_status) { desc[i].inflated_off = blob + inflated_total; inflated_total += pad16(desc[i].inflated); }
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    uint8_t* block = nullptr;
-    HIP_TRY(DEV_MALLOC(&block, blob + inflated_total + 16u));
-    struct Release { uint8_t* p; hipStream_t st; ~Release() { (void)cached_free_after(p, st); } } release{block, st};
-    {
-        void* pin = nullptr;
-        std::vector<uint8_t> pageable;
-        uint8_t* host = nullptr;
-        if (cached_host_malloc(&pin, blob) == 0) host = static_cast<uint8_t*>(pin);
-        else { pageable.resize(blob); host = pageable.data(); }
-        std::memset(host, 0, desc_bytes + pal_bytes);
-        std::memcpy(host, desc.data(), sizeof(PngFile) * n_files);
-        uint32_t* pal = reinterpret_cast<uint32_t*>(host + desc_bytes);
-        for (uint32_t i = 0; i < n_files; ++i) {
-            if (desc[i].preset_status) continue;
-            if (desc[i].palette) std::memcpy(pal + static_cast<size_t>(desc[i].palette) * 256u, parsed[i]->palette, 1024);
-            uint8_t* at = host + desc[i].stream_off;                 // the IDAT payloads become one stream here, padded with zeros to 16 bytes
-            for (const auto& c : parsed[i]->idat) { std::memcpy(at, c.first, c.second); at += c.second; }
-            std::memset(at, 0, (0u - parsed[i]->idat_len) & 15u);
-        }
-        hipError_t e = hipMemcpyAsync(block, host, blob, hipMemcpyHostToDevice, st);
-        const hipError_t w = static_cast<hipError_t>(wait_stream(st));      // the staging block is free again on return
-        if (pin) (void)cached_host_free(pin);
-        HIP_TRY(e);
-        HIP_TRY(w);
+    StagedBlock staged(st);
+    if (int rc = staged.alloc(blob + inflated_total, blob)) return rc;
+    uint8_t* const block = staged.block;
+    uint8_t* const host = staged.host;
+    std::memset(host, 0, desc_bytes + pal_bytes);
+    std::memcpy(host, desc.data(), sizeof(PngFile) * n_files);
+    uint32_t* pal = reinterpret_cast<uint32_t*>(host + desc_bytes);
+    for (uint32_t i = 0; i < n_files; ++i) {
+        if (desc[i].preset_status) continue;
+        if (desc[i].palette) std::memcpy(pal + static_cast<size_t>(desc[i].palette) * 256u, parsed[i]->palette, 1024);
+        uint8_t* at = host + desc[i].stream_off;                     // the IDAT payloads become one stream here, padded with zeros to 16 bytes
+        for (const auto& c : parsed[i]->idat) { std::memcpy(at, c.first, c.second); at += c.second; }
+        std::memset(at, 0, (0u - parsed[i]->idat_len) & 15u);
     }
+    if (int rc = staged.send()) return rc;
     PngDecArgs a;
     a.files = reinterpret_cast<const PngFile*>(block); a.palettes = reinterpret_cast<const uint32_t*>(block + desc_bytes); a.block = block;
     a.status = d_status; a.n_files = n_files;
@@ -249,38 +238,25 @@ extern "C" {
 int ifhip_png_decode_batch_device(const uint8_t* const* files, const size_t* lens, uint32_t n_files, uint8_t* const* d_frames, const size_t* frame_bytes,
                                   const uint32_t* strides, uint32_t* d_status, void* hip_stream) {
     if (n_files == 0) return IFHIP_OK;
-    if (!files || !lens || !d_frames || !frame_bytes || !strides || !d_status) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
-    if (n_files > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: 1..65535 files per batch");
-    std::vector<PngParsed> parsed(n_files);
-    std::vector<const PngParsed*> ok(n_files, nullptr);
-    for (uint32_t i = 0; i < n_files; ++i) {
-        if (!files[i]) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null file pointer (file %u)", i);
-        if (parse_png(files[i], lens[i], &parsed[i], true) == IFHIP_OK) ok[i] = &parsed[i];
-    }
+    std::vector<PngParsed> parsed;
+    std::vector<const PngParsed*> ok;
+    auto parse = [](const uint8_t* file, size_t len, uint32_t, PngParsed* P) { return parse_png(file, len, P, true) == IFHIP_OK; };
+    if (int rc = walk_decode_batch(files, lens, n_files, d_frames, frame_bytes, strides, d_status, &parsed, &ok, parse)) return rc;
     return png_decode_parsed_device(ok.data(), n_files, d_frames, frame_bytes, strides, d_status, hip_stream);
 }
 
 int ifhip_png_decode(const uint8_t* png, size_t len, uint8_t* bgra, uint32_t stride, size_t capacity, uint32_t* status) {
-    if (status) *status = 0;
+    uint32_t word = 0;
+    if (!status) status = &word;
+    *status = 0;
     if (!png) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null file pointer");
     PngParsed P;
     if (int rc = parse_png(png, len, &P, true)) return rc;          // the one walk over the chunks
-    if (!bgra) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null bitmap pointer");
-    if (static_cast<uint64_t>(P.w) * 4u > stride || (stride & 3u)) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: stride smaller than a BGRA row or not a multiple of 4");
-    if (static_cast<uint64_t>(P.h - 1u) * stride + 4ull * P.w > capacity)
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: the frame needs %llu bytes, the buffer has %zu", static_cast<unsigned long long>(static_cast<uint64_t>(P.h - 1u) * stride + 4ull * P.w), capacity);
-    HostFrame f;
-    if (int rc = f.up(bgra, P.w, P.h, stride, 16u)) return rc;
-    uint8_t* frames[1] = {f.d};
-    const size_t bytes[1] = {f.image_bytes};
-    const uint32_t strides[1] = {stride};
-    const PngParsed* parsed[1] = {&P};
-    uint32_t* d_status = reinterpret_cast<uint32_t*>(f.side_output());
-    if (int rc = png_decode_parsed_device(parsed, 1, frames, bytes, strides, d_status, nullptr)) return rc;
-    uint32_t side[4] = {0, 0, 0, 0};
-    if (int rc = f.down(bgra, side)) return rc;
-    if (status) *status = side[0];
-    if (side[0]) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: LibPNG error: %s", png_status_text(side[0]));
+    if (int rc = check_decode_destination(bgra, P.w, P.h, stride, capacity)) return rc;
+    const PngParsed* parsed = &P;
+    auto device = [&](uint8_t* frame, size_t bytes, uint32_t at_stride, uint32_t* d_status) { return png_decode_parsed_device(&parsed, 1, &frame, &bytes, &at_stride, d_status, nullptr); };
+    if (int rc = decode_to_host_frame(P.w, P.h, bgra, stride, device, status)) return rc;
+    if (*status) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: LibPNG error: %s", png_status_text(*status));
     return IFHIP_OK;
 }
 

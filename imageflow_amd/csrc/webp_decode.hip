@@ -29,7 +29,7 @@
 #include <cstring>
 #include <vector>
 
-#include "hip_entry.hpp"
+#include "decode_handoff.hpp"
 #include "webp_decode_core.hpp"
 #include "webp_read.hpp"
 
@@ -159,9 +159,9 @@ int webp_decode_prepared_device(const WebpJob* const* jobs, uint32_t n_files, ui
     std::vector<WebpFile> desc(n_files);
     uint64_t max_pixels = 1;
     uint32_t max_steps = 1;
-    const size_t desc_bytes = (sizeof(WebpFile) * n_files + 15u) & ~static_cast<size_t>(15);
+    const size_t desc_bytes = pad16(sizeof(WebpFile) * n_files);
     size_t blob = desc_bytes;
-    auto take = [&](size_t bytes) { const size_t at = blob; blob += (bytes + 15u) & ~static_cast<size_t>(15); return at; };
+    auto take = [&](size_t bytes) { const size_t at = blob; blob += pad16(bytes); return at; };
     for (uint32_t i = 0; i < n_files; ++i) {
         WebpFile& f = desc[i];
         std::memset(&f, 0, sizeof f);
@@ -189,36 +189,25 @@ int webp_decode_prepared_device(const WebpJob* const* jobs, uint32_t n_files, ui
     size_t total = blob;
     for (uint32_t i = 0; i < n_files; ++i)
         if (!desc[i].preset_status)
-            for (int p = 0; p < 2; ++p) { desc[i].plane_off[p] = total; total += (static_cast<size_t>(desc[i].w) * desc[i].h * 4u + 15u) & ~static_cast<size_t>(15); }
-    if (int rc = require_gfx950(nullptr)) return rc;
+            for (int p = 0; p < 2; ++p) { desc[i].plane_off[p] = total; total += pad16(static_cast<size_t>(desc[i].w) * desc[i].h * 4u); }
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    uint8_t* block = nullptr;
-    HIP_TRY(DEV_MALLOC(&block, total + 16u));
-    struct Release { uint8_t* p; hipStream_t st; ~Release() { (void)cached_free_after(p, st); } } release{block, st};
-    {
-        void* pin = nullptr;
-        std::vector<uint8_t> pageable;
-        uint8_t* host = nullptr;
-        if (cached_host_malloc(&pin, blob) == 0) host = static_cast<uint8_t*>(pin);
-        else { pageable.resize(blob); host = pageable.data(); }
-        std::memset(host, 0, desc_bytes);
-        std::memcpy(host, desc.data(), sizeof(WebpFile) * n_files);
-        auto put = [&](size_t at, const void* p, size_t bytes) { if (bytes) std::memcpy(host + at, p, bytes); std::memset(host + at + bytes, 0, (0u - bytes) & 15u); };
-        for (uint32_t i = 0; i < n_files; ++i) {
-            if (desc[i].preset_status) continue;
-            const WebpPrepared& P = *jobs[i]->prepared;
-            put(desc[i].stream_off, P.payload.data(), jobs[i]->parsed.payload_len);
-            put(desc[i].entropy_off, P.entropy.data(), P.entropy.size() * 4u);
-            put(desc[i].group_off, P.group_off.data(), P.group_off.size() * 4u);
-            put(desc[i].tables_off, P.tables.data(), P.tables.size() * 4u);
-            for (uint32_t k = 0; k < P.n_transforms; ++k) { const WebpTransform& T = P.t[P.n_transforms - 1u - k]; put(desc[i].step[k].data_off, T.data.data(), T.data.size() * 4u); }
-        }
-        hipError_t e = hipMemcpyAsync(block, host, blob, hipMemcpyHostToDevice, st);
-        const hipError_t w = static_cast<hipError_t>(wait_stream(st));      // the staging block is free again on return
-        if (pin) (void)cached_host_free(pin);
-        HIP_TRY(e);
-        HIP_TRY(w);
+    StagedBlock staged(st);
+    if (int rc = staged.alloc(total, blob)) return rc;
+    uint8_t* const block = staged.block;
+    uint8_t* const host = staged.host;
+    std::memset(host, 0, desc_bytes);
+    std::memcpy(host, desc.data(), sizeof(WebpFile) * n_files);
+    auto put = [&](size_t at, const void* p, size_t bytes) { if (bytes) std::memcpy(host + at, p, bytes); std::memset(host + at + bytes, 0, (0u - bytes) & 15u); };
+    for (uint32_t i = 0; i < n_files; ++i) {
+        if (desc[i].preset_status) continue;
+        const WebpPrepared& P = *jobs[i]->prepared;
+        put(desc[i].stream_off, P.payload.data(), jobs[i]->parsed.payload_len);
+        put(desc[i].entropy_off, P.entropy.data(), P.entropy.size() * 4u);
+        put(desc[i].group_off, P.group_off.data(), P.group_off.size() * 4u);
+        put(desc[i].tables_off, P.tables.data(), P.tables.size() * 4u);
+        for (uint32_t k = 0; k < P.n_transforms; ++k) { const WebpTransform& T = P.t[P.n_transforms - 1u - k]; put(desc[i].step[k].data_off, T.data.data(), T.data.size() * 4u); }
     }
+    if (int rc = staged.send()) return rc;
     WebpDecArgs a;
     a.files = reinterpret_cast<const WebpFile*>(block); a.block = block; a.status = d_status; a.n_files = n_files;
     const char* stop = debug_switch("webp_decode_stop_after");    // tools/bench_webp_decode.py: the stages' times by difference
@@ -239,45 +228,34 @@ extern "C" {
 int ifhip_webp_decode_batch_device(const uint8_t* const* files, const size_t* lens, uint32_t n_files, uint8_t* const* d_frames, const size_t* frame_bytes,
                                    const uint32_t* strides, uint32_t* d_status, void* hip_stream) {
     if (n_files == 0) return IFHIP_OK;
-    if (!files || !lens || !d_frames || !frame_bytes || !strides || !d_status) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
-    if (n_files > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: 1..65535 files per batch");
-    std::vector<WebpJob> jobs(n_files);
-    std::vector<const WebpJob*> ok(n_files, nullptr);
-    for (uint32_t i = 0; i < n_files; ++i) {
-        if (!files[i]) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null file pointer (file %u)", i);
+    std::vector<WebpJob> jobs;
+    std::vector<const WebpJob*> ok;
+    auto parse = [](const uint8_t* file, size_t len, uint32_t, WebpJob* J) {
         WebpParsed P;
-        if (parse_webp_for_decode(files[i], lens[i], &P) == IFHIP_OK) { webp_prepare_job(P, &jobs[i]); ok[i] = &jobs[i]; }
-    }
+        if (parse_webp_for_decode(file, len, &P) != IFHIP_OK) return false;
+        webp_prepare_job(P, J);
+        return true;
+    };
+    if (int rc = walk_decode_batch(files, lens, n_files, d_frames, frame_bytes, strides, d_status, &jobs, &ok, parse)) return rc;
     return webp_decode_prepared_device(ok.data(), n_files, d_frames, frame_bytes, strides, d_status, hip_stream);
 }
 
 int ifhip_webp_decode(const uint8_t* webp, size_t len, uint8_t* bgra, uint32_t stride, size_t capacity, uint32_t* status) {
-    if (status) *status = 0;
+    uint32_t word = 0;
+    if (!status) status = &word;
+    *status = 0;
     if (!webp) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null file pointer");
     WebpJob J;
     if (int rc = parse_webp_for_decode(webp, len, &J.parsed)) return rc;
     const WebpParsed P = J.parsed;
-    if (!bgra) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null bitmap pointer");
-    if (static_cast<uint64_t>(P.w) * 4u > stride || (stride & 3u)) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: stride smaller than a BGRA row or not a multiple of 4");
-    if (static_cast<uint64_t>(P.h - 1u) * stride + 4ull * P.w > capacity)
-        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: the frame needs %llu bytes, the buffer has %zu", static_cast<unsigned long long>(static_cast<uint64_t>(P.h - 1u) * stride + 4ull * P.w), capacity);
+    if (int rc = check_decode_destination(bgra, P.w, P.h, stride, capacity)) return rc;
     webp_prepare_job(P, &J);
-    if (J.status) {
-        if (status) *status = J.status;
-        return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: libwebp decoding error %s", webp_status_text(J.status));
-    }
-    HostFrame f;
-    if (int rc = f.up(bgra, P.w, P.h, stride, 16u)) return rc;
-    uint8_t* frames[1] = {f.d};
-    const size_t bytes[1] = {f.image_bytes};
-    const uint32_t strides[1] = {stride};
-    const WebpJob* jobs[1] = {&J};
-    uint32_t* d_status = reinterpret_cast<uint32_t*>(f.side_output());
-    if (int rc = webp_decode_prepared_device(jobs, 1, frames, bytes, strides, d_status, nullptr)) return rc;
-    uint32_t side[4] = {0, 0, 0, 0};
-    if (int rc = f.down(bgra, side)) return rc;
-    if (status) *status = side[0];
-    if (side[0]) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: libwebp decoding error %s", webp_status_text(side[0]));
+    const WebpJob* job = &J;
+    auto device = [&](uint8_t* frame, size_t bytes, uint32_t at_stride, uint32_t* d_status) { return webp_decode_prepared_device(&job, 1, &frame, &bytes, &at_stride, d_status, nullptr); };
+    *status = J.status;                                           // what the host prepare finds needs no device
+    if (!*status)
+        if (int rc = decode_to_host_frame(P.w, P.h, bgra, stride, device, status)) return rc;
+    if (*status) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: libwebp decoding error %s", webp_status_text(*status));
     return IFHIP_OK;
 }
 
