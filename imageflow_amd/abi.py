@@ -74,6 +74,8 @@ def _bind():
     L.ifhip_shim_context_set_color_management.restype = C.c_bool
     L.ifhip_shim_context_set_gif_encoder.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_gif_encoder.restype = C.c_bool
+    L.ifhip_shim_context_set_gif_animation.argtypes = [vp, C.c_int]
+    L.ifhip_shim_context_set_gif_animation.restype = C.c_bool
     L.ifhip_shim_context_set_device_jpeg_options.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_device_jpeg_options.restype = C.c_bool
     L.imageflow_context_memory_allocate.argtypes = [vp, C.c_size_t, C.c_char_p, C.c_int32]
@@ -168,6 +170,12 @@ class Context:
         """EXTENSION, off by default: `encode` with the preset "gif" writes a GIF89a file on the device (image/gif) instead of
         the raw BGRA container; a GIF input of the job hands on its loop count, delay and user-input flag."""
         return self.L.ifhip_shim_context_set_gif_encoder(self.p, 1 if on else 0)
+
+    def set_gif_animation(self, on):
+        """EXTENSION, off by default: with the GIF encoder on as well, a job whose `decode` reads a GIF of more than one frame
+        (no select_frame told) and whose "gif" `encode` lies downstream runs once per frame and writes ONE animated GIF;
+        every other encoder of the job takes frame 0.  Every other job is what it is with the switch off."""
+        return self.L.ifhip_shim_context_set_gif_animation(self.p, 1 if on else 0)
 
     def set_device_jpeg_options(self, on):
         """EXTENSION, off by default: entropy-code the libjpeg_turbo preset's progressive / optimize_huffman_coding files on the

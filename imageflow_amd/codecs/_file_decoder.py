@@ -38,6 +38,32 @@ def decode_batch(info_fn, batch_fn, Info, gets_frame, alpha, files, device, fram
     return out, [int(s) for s in status.cpu().numpy()[:n]]
 
 
+def decode_frames(info_fn, count_fn, frames_fn, Info, data, device, stride, fill):
+    """One file, every screen: count_fn is the host walk (frames, delays, user-input flags), frames_fn the device call that
+    writes screen k at k * screen_pitch.  -> (Bitmap of n screens or None, file status word, delays, user-input flags)"""
+    device = torch.device(device)
+    buf = np.frombuffer(bytes(data), np.uint8)
+    info = Info()
+    _native.check(info_fn(buf.ctypes.data, buf.size, C.byref(info)))
+    n = C.c_uint32(0)
+    _native.check(count_fn(buf.ctypes.data, buf.size, C.byref(n), None, None, 0))
+    delays, flags = (C.c_uint32 * max(n.value, 1))(), (C.c_uint32 * max(n.value, 1))()
+    _native.check(count_fn(buf.ctypes.data, buf.size, C.byref(n), delays, flags, n.value))
+    stride = stride or get_stride(info.width)
+    screens = torch.full((max(n.value, 1), info.height * stride), 0 if fill is None else fill, dtype=torch.uint8, device=device)
+    status = torch.zeros(1, dtype=torch.int32, device=device)
+    written = C.c_uint32(0)
+    stream = torch.cuda.current_stream(device).cuda_stream
+    with torch.cuda.device(device):
+        _native.check(frames_fn(buf.ctypes.data, buf.size, screens.data_ptr(), screens.stride(0), stride, screens.shape[0], status.data_ptr(), C.byref(written),
+                                C.c_void_p(stream)))
+    word = int(status.cpu()[0])
+    if word:
+        return Bitmap(screens, info.width, info.height, stride, alpha_meaningful=True), word, [], []
+    assert written.value == n.value
+    return Bitmap(screens[:n.value], info.width, info.height, stride, alpha_meaningful=True), 0, list(delays)[:n.value], [bool(f) for f in list(flags)[:n.value]]
+
+
 def decode_host(info_fn, host_fn, Info, data, stride, out, lead=()):
     """lead: the arguments of host_fn between the file and the bitmap.  -> BGRA rows [h, stride] uint8"""
     buf = np.frombuffer(bytes(data), np.uint8)

@@ -8,7 +8,7 @@ import numpy as np
 
 from .. import _native
 from ..errors import ErrorKind, FlowError
-from ._file_decoder import decode_batch, decode_host
+from ._file_decoder import decode_batch, decode_frames, decode_host
 
 # include/imageflow_hip.h IFHIP_GIF_DEC_*
 STATUS = {0: "ok", 1: "too_little", 2: "bad_code", 3: "container", 4: "min_code_size", 5: "no_palette", 6: "frame_too_large", 7: "no_such_frame"}
@@ -25,6 +25,8 @@ def _bind():
     L.ifhip_gif_info.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(GifFileInfo)]
     L.ifhip_gif_decode_batch_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifhip_gif_decode.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_void_p, C.c_uint32, C.c_size_t, C.POINTER(C.c_uint32)]
+    L.ifhip_gif_frame_count.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.c_void_p, C.c_void_p, C.c_uint32]
+    L.ifhip_gif_decode_frames_device.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint32), C.c_void_p]
     L._gif_dec_bound = True
     return L
 
@@ -59,6 +61,31 @@ def decode_gif(data, frame_index=0, device="cuda:0"):
     if status[0]:
         raise FlowError(ErrorKind.InvalidArgument, f"ImageMalformed: GIF decoding error: {STATUS.get(status[0], status[0])}")
     return frames[0]
+
+
+def gif_frame_count(data):
+    """GifDecoder::has_more_frames until it says no: (frames, delays in hundredths of a second, user-input flags).  Host only;
+    a file the walk refuses raises."""
+    L = _bind()
+    buf = np.frombuffer(bytes(data), np.uint8)
+    n = C.c_uint32(0)
+    _native.check(L.ifhip_gif_frame_count(buf.ctypes.data, buf.size, C.byref(n), None, None, 0))
+    delays, flags = (C.c_uint32 * max(n.value, 1))(), (C.c_uint32 * max(n.value, 1))()
+    _native.check(L.ifhip_gif_frame_count(buf.ctypes.data, buf.size, C.byref(n), delays, flags, n.value))
+    return n.value, list(delays)[:n.value], [bool(f) for f in list(flags)[:n.value]]
+
+
+def decode_gif_frames(data, device="cuda:0", stride=None, fill=None, with_status=False):
+    """Every composed screen of one file in one pass (ifhip_gif_decode_frames_device): -> (screens, delays): screens a Bitmap
+    whose frame k is the logical screen behind frame k's blit -- what decode_gif(data, k) gives --, delays in hundredths of a
+    second.  A damaged frame anywhere raises (with_status: -> (screens, delays, status word) instead, the block untouched)."""
+    L = _bind()
+    screens, status, delays, _ = decode_frames(L.ifhip_gif_info, L.ifhip_gif_frame_count, L.ifhip_gif_decode_frames_device, GifFileInfo, data, device, stride, fill)
+    if with_status:
+        return screens, delays, status
+    if status:
+        raise FlowError(ErrorKind.InvalidArgument, f"ImageMalformed: GIF decoding error: {STATUS.get(status, status)}")
+    return screens, delays
 
 
 def decode_gif_host(data, frame_index=0, stride=None, out=None):

@@ -29,6 +29,9 @@ def _bind():
                                                 C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.ifhip_gif_encode.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_size_t,
                                    C.POINTER(C.c_size_t)]
+    L.ifhip_gif_enc_stage_max_animation_bytes.argtypes = [C.c_void_p, C.c_uint32, C.POINTER(C.c_size_t)]
+    L.ifhip_gif_encode_animation_device.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]
     L._gif_enc_bound = True
     return L
 
@@ -76,6 +79,40 @@ class GifEncodeStage:
         pal, idx = palettes.cpu().numpy(), indices.cpu().numpy()
         pals = [pal[i, :1024].reshape(256, 4)[:int(pal[i, 1024:].view(np.uint32)[0])].copy() for i in range(frames.n)]
         return out, [int(s) for s in status], pals, [idx[i] for i in range(frames.n)]
+
+    def max_animation_bytes(self, n_frames):
+        n = C.c_size_t(0)
+        _native.check(_bind().ifhip_gif_enc_stage_max_animation_bytes(self._h, n_frames, C.byref(n)))
+        return int(n.value)
+
+    def encode_animation_device(self, frames: Bitmap, delays, user_input, repeat=-1, capacity=None):
+        """frames: n BGRA frames of the stage's geometry, n beyond max_images runs the stage in chunks.  Returns (file
+        [capacity] uint8, length [1] int32, status [1] int32), cuda tensors; nothing is synchronised."""
+        L = _bind()
+        n = frames.n
+        if capacity is None:
+            capacity = self.max_animation_bytes(n)
+        file = torch.empty((capacity + 3) // 4 * 4, dtype=torch.uint8, device=self.device)
+        length = torch.zeros(1, dtype=torch.int32, device=self.device)
+        status = torch.zeros(1, dtype=torch.int32, device=self.device)
+        d = (C.c_uint32 * n)(*[int(v) for v in delays])
+        u = (C.c_uint8 * n)(*[1 if v else 0 for v in user_input])
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        with torch.cuda.device(self.device):
+            _native.check(L.ifhip_gif_encode_animation_device(self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride, 1 if frames.alpha_meaningful else 0,
+                                                              n, repeat, d, u, file.data_ptr(), capacity, length.data_ptr(), status.data_ptr(), C.c_void_p(stream)))
+        return file, length, status
+
+    def encode_animation(self, bitmap_batch: Bitmap, delays, user_input, repeat=-1, capacity=None, with_status=False):
+        """The n frames as ONE animated GIF89a file: bytes (with_status: (bytes or None, status word))."""
+        file, length, status = self.encode_animation_device(bitmap_batch, delays, user_input, repeat, capacity)
+        k, word = int(length.cpu()[0]), int(status.cpu()[0])
+        data = file[:k].cpu().numpy().tobytes() if k else None
+        if with_status:
+            return data, word
+        if word or data is None:
+            raise RuntimeError(f"device GIF coder dropped the animation: status {word}")
+        return data
 
     def __del__(self):
         try:

@@ -19,7 +19,9 @@
 //     a lossless WebP for the webplossless preset (the device coder, webp_encode.hip),
 //     and that container for every other preset (preferred_extension "ifbgra", mime "application/x-imageflow-bgra"):
 //     the lodepng / lossy WebP coders are out of scope, the caller's encoder takes the frame;
-//     "gif" is that container too unless ifhip_shim_context_set_gif_encoder switched the device GIF coder on (gif_encode.hip).
+//     "gif" is that container too unless ifhip_shim_context_set_gif_encoder switched the device GIF coder on (gif_encode.hip);
+//   * with ifhip_shim_context_set_gif_animation on as well, an animated GIF source runs the job once per frame and the "gif"
+//     encode nodes write one animated file (Job::run_job).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -464,6 +466,10 @@ struct SizeLimit { uint32_t w, h; float megapixels; };
 struct Security {
     SizeLimit max_decode_size{12000, 12000, 100.f};
     SizeLimit max_frame_size{10000, 10000, 100.f};
+    // Option<u64>, sane_defaults() 400 megapixels (lib.rs:1212-1235): frame count x width x height of an animation
+    // (GifDecoder::check_total_pixels, codecs/gif/mod.rs:103-118).  Read by the animation path alone.
+    bool has_max_total_file_pixels = true;
+    uint64_t max_total_file_pixels = 400000000ull;
 };
 // Engine::validate_frame_size (flow/execution_engine.rs:286-325); ErrorKind::SizeLimitExceeded -> ArgumentInvalid
 void check_size(const SizeLimit& lim, const char* what, uint64_t w, uint64_t h) {
@@ -543,6 +549,7 @@ struct imageflow_context {
     std::atomic<int64_t> coalesced_decodes{0};           // decodes of this context that shared their device call with another thread's job
     std::atomic<int> device{-1};                         // device ordinal its jobs run on; -1: the calling thread's current device
     std::atomic<bool> device_jpeg_options{false};        // EXTENSION ifhip_shim_context_set_device_jpeg_options: progressive / optimised tables coded on the device
+    std::atomic<bool> gif_animation{false};              // EXTENSION ifhip_shim_context_set_gif_animation: animated GIFs run once per frame into one file
     std::atomic<bool> gif_encoder{false};                // EXTENSION ifhip_shim_context_set_gif_encoder: the "gif" preset writes a GIF on the device
     std::atomic<bool> color_management{false};           // EXTENSION ifhip_shim_context_set_color_management: every input is converted to sRGB
     bool cancellation_requested() {
@@ -1089,6 +1096,7 @@ struct Job {
     // colour profile; the JPEG and WebP hints are accepted and ignored.
     struct GifSource { bool seen; int repeat; uint32_t delay; bool user_input; } gif_source{false, -1, 0u, false};   // of the first GIF the job decoded
     FramePtr decode_gif(int32_t io_id, Io& in) {
+        if (anim.active && anim.in_decode_node && anim.sources.count(io_id)) return animated_screen(io_id);
         ifhip::GifParsed P;
         check(ifhip::parse_gif_header(in.in, in.in_len, &P));
         check_size(sec.max_decode_size, "max_decode_size", P.w, P.h);
@@ -1599,6 +1607,10 @@ struct Job {
         Io& o = output(io_id);
         if (o.out_state == OutState::Taken) raise(kArgumentInvalid, "InvalidArgument: Output buffer for io_id %d has already been taken", io_id);
         poll_cancel();
+        if (anim.active) {                                                           // every frame to the "gif" nodes, frame 0 to every other encoder
+            if (preset && preset->t == JVal::Str && preset->s == "gif") { collect_frame(f, io_id); return; }
+            if (anim.k > 0) return;
+        }
         const int coder = encode_coder(preset);
         // EncoderPreset::Mozjpeg {quality, progressive, matte} -> MozjpegEncoder::create (codecs/mozjpeg.rs:37-59): mozjpeg's own
         // defaults.  Of those the trellis quantisation is built (csrc/jpeg_trellis.hip, this project's restatement of
@@ -2016,7 +2028,10 @@ struct Job {
                     }
                 }
             }
-            return decode_oriented(static_cast<int32_t>(want_int(p, "io_id", "decode")), hw, hh, spatial, gamma);
+            anim.in_decode_node = true;                                              // (a watermark's or a command_string's own decode does not animate)
+            FramePtr f = decode_oriented(static_cast<int32_t>(want_int(p, "io_id", "decode")), hw, hh, spatial, gamma);
+            anim.in_decode_node = false;
+            return f;
         }
         if (name == "create_canvas") {
             Timed t(this, "create_canvas");
@@ -2195,6 +2210,208 @@ struct Job {
         if (n.t != JVal::Obj || n.o.size() != 1 || n.o[0].first != "encode") return;
         const JVal* preset = n.o[0].second.get("preset");
         if (encode_coder(preset) == IFHIP_ENCODE_CODER_MOZJPEG) check_mozjpeg_preset(preset);
+    }
+
+
+    // ---- animated GIFs (EXTENSION ifhip_shim_context_set_gif_animation) ---------------------------------------------------------------
+    // The reference re-runs the job for every frame of an animated source (GifDecoder::has_more_frames -> ctx.set_more_frames,
+    // codecs/gif/mod.rs:207-305, flow/nodes/codecs_and_pointer.rs:168) and GifEncoder::write_frame appends frame frame_ix to one
+    // file (:429-521).  Here: the source's screens are decoded ONCE (ifhip::gif_decode_all_parsed_device: one replay for all of
+    // them), run_framewise runs once per frame with the animated decode node yielding screen k, every "gif" encode node
+    // collects its frame k into one device block, and behind the last frame the block is coded in ONE call
+    // (ifhip_gif_encode_animation_device) -- an animation's frames are a ready-made batch.  Every other encoder takes frame 0.
+    struct AnimSource {
+        uint8_t* d = nullptr;                    // n screens, h * stride bytes each
+        uint32_t w = 0, h = 0, stride = 0;
+        ~AnimSource() { job_free(d); }
+    };
+    struct AnimCollect {
+        uint8_t* d = nullptr;                    // n frames, h * stride bytes each
+        ifhip_gif_enc_stage* stage = nullptr;
+        uint32_t w = 0, h = 0, stride = 0;
+        bool alpha = false;
+        ~AnimCollect() { job_free(d); if (stage) { quiesce(); ifhip_gif_enc_stage_destroy(stage); } }
+    };
+    struct Anim {
+        bool active = false, in_decode_node = false;
+        uint32_t n = 0, k = 0;
+        int repeat = 0;
+        uint64_t pixels = 0;                     // decoded screens + collected frames so far (check_total_pixels)
+        std::vector<uint32_t> delays;
+        std::vector<uint8_t> user_input;
+        std::map<int32_t, std::unique_ptr<AnimSource>> sources;
+        std::map<int32_t, std::unique_ptr<AnimCollect>> collects;
+    } anim;
+
+    void add_animation_pixels(uint64_t pixels_per_frame) {
+        anim.pixels += pixels_per_frame * anim.n;
+        if (sec.has_max_total_file_pixels && anim.pixels > sec.max_total_file_pixels)
+            raise(kArgumentInvalid, "SizeLimitExceeded: GIF total decoded pixels (%u frames x %llu pixels, %llu in the job) exceeds max_total_file_pixels %llu", anim.n,
+                  static_cast<unsigned long long>(pixels_per_frame), static_cast<unsigned long long>(anim.pixels), static_cast<unsigned long long>(sec.max_total_file_pixels));
+    }
+    // a `decode` node whose input animates: a GIF of more than one frame that no select_frame was told to (-> its frame count)
+    uint32_t animated_frames_of(const JVal& params) {
+        const JVal* id = params.get("io_id");
+        if (!id || id->t != JVal::Num) return 0;
+        auto it = c->io.find(static_cast<int32_t>(id->n));
+        if (it == c->io.end() || it->second.is_output || !is_gif(it->second) || it->second.told_frame) return 0;
+        if (const JVal* cmds = params.get("commands"))
+            if (cmds->t == JVal::Arr)
+                for (const JVal& cmd : cmds->a) if (cmd.t == JVal::Obj && cmd.get("select_frame")) return 0;
+        uint32_t n = 0;
+        if (ifhip_gif_frame_count(it->second.in, it->second.in_len, &n, nullptr, nullptr, 0) != IFHIP_OK) return 0;   // (a file the walk refuses is the one-frame path's to report)
+        return n > 1u ? n : 0u;
+    }
+    // The animated decodes of a job that have a "gif" encode node downstream: io_id -> frame count; empty: the job does not animate.
+    std::vector<std::pair<int32_t, uint32_t>> animation_plan(const JVal& fw) {
+        std::vector<std::pair<int32_t, uint32_t>> found;
+        auto is_gif_encode = [](const std::string& name, const JVal& p) {
+            const JVal* preset = p.get("preset");
+            return name == "encode" && preset && preset->t == JVal::Str && preset->s == "gif";
+        };
+        auto add = [&](const JVal& p, uint32_t n) {
+            const int32_t id = static_cast<int32_t>(p.get("io_id")->n);
+            for (const auto& f : found) if (f.first == id) return;
+            found.push_back({id, n});
+        };
+        std::string name;
+        const JVal* params;
+        if (const JVal* steps = fw.get("steps")) {
+            if (steps->t != JVal::Arr) return found;
+            for (size_t i = 0; i < steps->a.size(); ++i) {
+                node_of(steps->a[i], &name, &params);
+                if (name != "decode") continue;
+                const uint32_t n = animated_frames_of(*params);
+                if (!n) continue;
+                const JVal* source = params;
+                for (size_t j = i + 1; j < steps->a.size(); ++j) {                       // downstream: up to the next node that starts a frame of its own
+                    node_of(steps->a[j], &name, &params);
+                    if (name == "decode" || name == "create_canvas") break;
+                    if (is_gif_encode(name, *params)) { add(*source, n); break; }
+                }
+            }
+            return found;
+        }
+        const JVal* graph = fw.get("graph");
+        const JVal *nodes = graph ? graph->get("nodes") : nullptr, *edges = graph ? graph->get("edges") : nullptr;
+        if (!nodes || nodes->t != JVal::Obj || !edges || edges->t != JVal::Arr) return found;
+        std::map<int64_t, const JVal*> by_id;
+        std::multimap<int64_t, int64_t> parents;
+        for (const auto& kv : nodes->o) by_id[std::atoll(kv.first.c_str())] = &kv.second;
+        for (const JVal& e : edges->a) {
+            const JVal *from = e.get("from"), *to = e.get("to");
+            if (from && to && from->t == JVal::Num && to->t == JVal::Num) parents.insert({static_cast<int64_t>(to->n), static_cast<int64_t>(from->n)});
+        }
+        for (const auto& kv : by_id) {
+            node_of(*kv.second, &name, &params);
+            if (!is_gif_encode(name, *params)) continue;
+            std::vector<int64_t> todo{kv.first};
+            std::map<int64_t, bool> seen;
+            while (!todo.empty()) {                                                      // every ancestor, over input and canvas edges
+                const int64_t id = todo.back();
+                todo.pop_back();
+                if (seen[id] || !by_id.count(id)) continue;
+                seen[id] = true;
+                node_of(*by_id[id], &name, &params);
+                if (name == "decode") if (const uint32_t n = animated_frames_of(*params)) add(*params, n);
+                auto range = parents.equal_range(id);
+                for (auto it = range.first; it != range.second; ++it) todo.push_back(it->second);
+            }
+        }
+        return found;
+    }
+    // every screen of one animated source, decoded and composed once
+    void decode_animation_source(int32_t io_id, bool first) {
+        Timed t(this, "primitive_decoder");
+        Io& in = input(io_id);
+        ifhip::GifParsed P;
+        check(ifhip::parse_gif_header(in.in, in.in_len, &P));
+        check_size(sec.max_decode_size, "max_decode_size", P.w, P.h);
+        check_size(sec.max_frame_size, "max_frame_size", P.w, P.h);
+        check(ifhip::parse_gif_all(in.in, in.in_len, &P));
+        auto refuse = [&](uint32_t status) {
+            if (status == IFHIP_GIF_DEC_FRAME_TOO_LARGE) raise(kArgumentInvalid, "SizeLimitExceeded: %s (io_id %d)", ifhip::gif_status_text(status), io_id);
+            raise(kImageMalformed, "ImageMalformed: GIF decoding error: %s (io_id %d, status %u)", ifhip::gif_status_text(status), io_id, status);
+        };
+        if (P.status) refuse(P.status);
+        add_animation_pixels(static_cast<uint64_t>(P.w) * P.h);                        // before anything is allocated
+        auto src = std::make_unique<AnimSource>();
+        src->w = P.w; src->h = P.h; src->stride = ifhip_stride_for_width(P.w);
+        const size_t pitch = static_cast<size_t>(P.h) * src->stride;
+        hip_check(job_malloc(reinterpret_cast<void**>(&src->d), pitch * anim.n + 64), "hipMalloc(screens)");
+        hip_check(hipMemsetAsync(src->d, 0, pitch * anim.n + 64, t_job_stream), "hipMemset(screens)");
+        const uint32_t status = decoded_status("decode(gif)", [&](uint32_t* d_status) { return ifhip::gif_decode_all_parsed_device(P, src->d, pitch, src->stride, d_status, t_job_stream); });
+        if (status) refuse(status);
+        if (first) {                                                                    // frame k's delay and user-input flag are the source frame's
+            anim.repeat = P.repeat < 0 ? 0 : P.repeat;                                  // (no NETSCAPE2.0 block: get_repeat's Infinite, mod.rs:167-170)
+            for (const ifhip::GifFrameInfo& f : P.frames) { anim.delays.push_back(f.delay); anim.user_input.push_back(f.user_input ? 1u : 0u); }
+        }
+        anim.sources[io_id] = std::move(src);
+    }
+    // what the animated decode node hands on in run k: a frame of its own (nodes may write into it) holding screen k
+    FramePtr animated_screen(int32_t io_id) {
+        const AnimSource& src = *anim.sources[io_id];
+        FramePtr f = new_frame(src.w, src.h, true, 0, false);
+        hip_check(hipMemcpyAsync(f->d, src.d + static_cast<size_t>(anim.k) * f->bytes(), f->bytes(), hipMemcpyDeviceToDevice, t_job_stream), "copy(screen)");
+        decodes.push_back({io_id, src.w, src.h, "image/gif", "gif"});
+        return f;
+    }
+    // a "gif" encode node in run k: its input joins the node's block
+    void collect_frame(const FramePtr& f, int32_t io_id) {
+        std::unique_ptr<AnimCollect>& slot = anim.collects[io_id];
+        if (anim.k == 0) {
+            if (slot) raise(kArgumentInvalid, "InvalidArgument: io_id %d is written by two encode nodes", io_id);
+            slot = std::make_unique<AnimCollect>();
+            check(ifhip_gif_enc_stage_create(&slot->stage, f->w, f->h, std::min(anim.n, 32u)));   // (size_16(): a side above 65535 is refused here)
+            add_animation_pixels(static_cast<uint64_t>(f->w) * f->h);                  // before the block is allocated
+            slot->w = f->w; slot->h = f->h; slot->stride = f->stride; slot->alpha = f->alpha;
+            hip_check(job_malloc(reinterpret_cast<void**>(&slot->d), f->bytes() * anim.n + 64), "hipMalloc(collected frames)");
+            encodes.push_back({io_id, f->w, f->h, "image/gif", "gif"});
+        }
+        if (!slot || slot->w != f->w || slot->h != f->h || slot->stride != f->stride || slot->alpha != f->alpha)
+            raise(kArgumentInvalid, "InvalidArgument: frame %u reaches the GIF encoder of io_id %d as %ux%u, frame 0 was %ux%u", anim.k, io_id, f->w, f->h, slot ? slot->w : 0u,
+                  slot ? slot->h : 0u);
+        hip_check(hipMemcpyAsync(slot->d + static_cast<size_t>(anim.k) * f->bytes(), dev(f), f->bytes(), hipMemcpyDeviceToDevice, t_job_stream), "copy(collected frame)");
+    }
+    void write_animations() {
+        for (auto& kv : anim.collects) {
+            Timed t(this, "primitive_encoder");
+            AnimCollect& a = *kv.second;
+            Io& o = output(kv.first);
+            size_t capacity = 0;
+            check(ifhip_gif_enc_stage_max_animation_bytes(a.stage, anim.n, &capacity));
+            const size_t pitch = (capacity + 15u) & ~static_cast<size_t>(15u);
+            CodedFile file;
+            hip_check(file.alloc(pitch, pitch), "hipMalloc(gif file)");
+            const size_t image_bytes = static_cast<size_t>(a.h) * a.stride;
+            check(ifhip_gif_encode_animation_device(a.stage, a.d, image_bytes, a.stride, a.alpha ? 1 : 0, anim.n, anim.repeat, anim.delays.data(), anim.user_input.data(), file.d,
+                                                    capacity, file.d_len, file.d_len + 1, t_job_stream));
+            poll_cancel();
+            file.fetch(o);
+            if (file.status != 0 || file.len == 0) raise(kInternalError, "InternalError: the GIF coder dropped a file sized for its worst case (status %u)", file.status);
+            o.written = true;
+        }
+    }
+    // a job: once, or -- where the animation path applies -- once per frame of the animated sources
+    void run_job(const JVal& fw) {
+        if (!c->gif_animation.load(std::memory_order_relaxed) || !c->gif_encoder.load(std::memory_order_relaxed)) return run_framewise(fw);
+        const std::vector<std::pair<int32_t, uint32_t>> plan = animation_plan(fw);
+        if (plan.empty()) return run_framewise(fw);
+        for (const auto& p : plan)                                                       // (mod.rs:253-258: a decoder that has run out of frames while the job goes on)
+            if (p.second != plan[0].second)
+                raise(kInternalError, "InvalidOperation: read_frame was called without a frame available (io_id %d has %u frames, io_id %d has %u)", p.first, p.second,
+                      plan[0].first, plan[0].second);
+        anim.active = true;
+        anim.n = plan[0].second;
+        for (size_t i = 0; i < plan.size(); ++i) decode_animation_source(plan[i].first, i == 0);
+        size_t decoded = 0;
+        for (anim.k = 0; anim.k < anim.n; ++anim.k) {
+            poll_cancel();                                                               // between frames
+            run_framewise(fw);
+            if (anim.k == 0) decoded = decodes.size();
+            else decodes.erase(decodes.begin() + static_cast<std::ptrdiff_t>(decoded), decodes.end());   // one record per decode node, as a one-frame job has
+        }
+        write_animations();
     }
 
     void run_framewise(const JVal& fw) {
@@ -2383,6 +2600,8 @@ void parse_security(const JVal* sec, Security* out) {
     };
     limit("max_decode_size", &out->max_decode_size);
     limit("max_frame_size", &out->max_frame_size);
+    if (const JVal* v = sec->get("max_total_file_pixels"))                 // (context.rs:659-661: a value given replaces the context's, null keeps it)
+        if (v->t == JVal::Num && v->n >= 0 && v->n < 18446744073709551616.0) { out->has_max_total_file_pixels = true; out->max_total_file_pixels = static_cast<uint64_t>(v->n); }
 }
 
 [[noreturn]] void abort_null_context() {                          // imageflow_abi/src/lib.rs:309-325
@@ -2501,6 +2720,12 @@ bool ifhip_shim_context_set_device(struct imageflow_context* c, int ordinal) {
 bool ifhip_shim_context_set_gif_encoder(struct imageflow_context* c, int on) {
     CTX_OR_ABORT(c);
     c->gif_encoder.store(on != 0, std::memory_order_relaxed);
+    return true;
+}
+// EXTENSION: animated GIFs pass through jobs (see Job::run_job); off by default, and without the GIF encoder's switch it changes nothing
+bool ifhip_shim_context_set_gif_animation(struct imageflow_context* c, int on) {
+    CTX_OR_ABORT(c);
+    c->gif_animation.store(on != 0, std::memory_order_relaxed);
     return true;
 }
 bool ifhip_shim_context_set_color_management(struct imageflow_context* c, int on) {
@@ -2708,7 +2933,7 @@ const struct imageflow_json_response* imageflow_context_send_json(struct imagefl
         if (build) if (const JVal* ios = root.get("io")) add_io_from_json(c, *ios);
         const JVal* fw = root.get("framewise");
         if (!fw || fw->t != JVal::Obj) raise(kInvalidJson, "InvalidJson: missing framewise");
-        job.run_framewise(*fw);
+        job.run_job(*fw);
         job.settle_perf(true);
         return respond(c, 200, job_result_json(job, build ? "build_result" : "job_result"));
     } catch (const FlowErr& e) {

@@ -16,6 +16,9 @@
 //                        writing its string from the end along the prefix chain in LDS.  A deferred clear's tail stays in
 //                        its segment's own workgroup, 1024 codes a chunk against the first chunk's arrays.
 //   gif_compose_kernel   one lane per SCREEN PIXEL replays dispose and blit over the frame list; BGRA rows at the caller's stride.
+//   gif_compose_all_kernel   in its place where EVERY screen of a file is wanted (ifhip_gif_decode_frames_device): the same
+//                        replay, once, the pixel stored into screen k behind frame k's blit -- consecutive dwords across
+//                        the lanes for every k.  N screens cost one pass over the frame list, not N.
 //
 // Bounds: a record store is below gif_max_segments (arithmetic from the stream's length); a code read is below the
 // stream's length (the scan counted only whole codes) and the staged stream carries 16 zero bytes behind it; an index store
@@ -121,13 +124,23 @@ __global__ __launch_bounds__(kGifThreads) void gif_compose_kernel(const GifDecAr
     }
 }
 
+__global__ __launch_bounds__(kGifThreads) void gif_compose_all_kernel(const GifDecArgs a, const size_t screen_pitch) {
+    const GifFileDesc& f = a.files[blockIdx.y];
+    const uint32_t status = gif_file_status(f, a.state);
+    if (blockIdx.x == 0u && threadIdx.x == 0u) a.status[blockIdx.y] = status;
+    if (status) return;                                              // (uniform: a damaged frame anywhere, and no screen is written)
+    const uint64_t n = static_cast<uint64_t>(f.w) * f.h;
+    for (uint64_t i = static_cast<uint64_t>(blockIdx.x) * kGifThreads + threadIdx.x; i < n; i += static_cast<uint64_t>(gridDim.x) * kGifThreads) {
+        const uint32_t y = static_cast<uint32_t>(i / f.w), px = static_cast<uint32_t>(i - static_cast<uint64_t>(y) * f.w);
+        gif_compose_all_pixel(f, a.frames, a.block, px, y, screen_pitch);
+    }
+}
+
 // The device part of a batch whose files the host has walked: files[i] == nullptr is a file whose header did not parse.  What
 // depends on the FILE is that file's status word; what depends on the CALLER's arguments -- the frames -- fails the call.
-int gif_decode_parsed_device(const GifParsed* const* files, uint32_t n_files, uint8_t* const* d_frames, const size_t* frame_bytes,
-                             const uint32_t* strides, uint32_t* d_status, void* hip_stream) {
-    for (uint32_t i = 0; i < n_files; ++i)
-        if (files[i])
-            if (int rc = check_frames(d_frames[i], frame_bytes[i], files[i]->w, files[i]->h, strides[i], "frame")) return rc;
+// all_screens_pitch != 0: d_frames[i] holds every screen of file i, that far apart (the caller has checked the block).
+static int gif_decode_launch(const GifParsed* const* files, uint32_t n_files, uint8_t* const* d_frames, const uint32_t* strides, uint32_t* d_status,
+                             void* hip_stream, size_t all_screens_pitch) {
     GifLayout L;
     gif_layout_batch(files, n_files, d_frames, strides, &L);
     if (L.n_frames > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: 65535 frames per batch at the most");
@@ -151,10 +164,28 @@ int gif_decode_parsed_device(const GifParsed* const* files, uint32_t n_files, ui
             hipLaunchKernelGGL(gif_resolve_kernel, dim3(seg_blocks, L.n_frames), dim3(kGifThreads), 0, st, a);
         }
     }
-    if ((!after_scan && !after_resolve) || !L.n_frames)
-        hipLaunchKernelGGL(gif_compose_kernel, dim3(std::min<uint32_t>((L.max_pixels + kGifThreads - 1u) / kGifThreads, 4096u), n_files), dim3(kGifThreads), 0, st, a);
+    if ((!after_scan && !after_resolve) || !L.n_frames) {
+        const dim3 grid(std::min<uint32_t>((L.max_pixels + kGifThreads - 1u) / kGifThreads, 4096u), n_files);
+        if (all_screens_pitch) hipLaunchKernelGGL(gif_compose_all_kernel, grid, dim3(kGifThreads), 0, st, a, all_screens_pitch);
+        else hipLaunchKernelGGL(gif_compose_kernel, grid, dim3(kGifThreads), 0, st, a);
+    }
     HIP_TRY(hipGetLastError());
     return IFHIP_OK;
+}
+
+int gif_decode_parsed_device(const GifParsed* const* files, uint32_t n_files, uint8_t* const* d_frames, const size_t* frame_bytes,
+                             const uint32_t* strides, uint32_t* d_status, void* hip_stream) {
+    for (uint32_t i = 0; i < n_files; ++i)
+        if (files[i])
+            if (int rc = check_frames(d_frames[i], frame_bytes[i], files[i]->w, files[i]->h, strides[i], "frame")) return rc;
+    return gif_decode_launch(files, n_files, d_frames, strides, d_status, hip_stream, 0);
+}
+
+int gif_decode_all_parsed_device(const GifParsed& file, uint8_t* d_screens, size_t screen_pitch, uint32_t stride, uint32_t* d_status, void* hip_stream) {
+    if (int rc = check_frames(d_screens, screen_pitch, file.w, file.h, stride, "screen")) return rc;
+    if (!d_status) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
+    const GifParsed* parsed = &file;
+    return gif_decode_launch(&parsed, 1, &d_screens, &stride, d_status, hip_stream, screen_pitch);
 }
 
 namespace {
@@ -179,6 +210,25 @@ int ifhip_gif_decode_batch_device(const uint8_t* const* files, const size_t* len
     auto parse = [&](const uint8_t* file, size_t len, uint32_t i, GifParsed* P) { return parse_gif(file, len, frame_index ? frame_index[i] : 0u, P) == IFHIP_OK && P->w && P->h; };
     if (int rc = walk_decode_batch(files, lens, n_files, d_frames, frame_bytes, strides, d_status, &parsed, &ok, parse)) return rc;
     return gif_decode_parsed_device(ok.data(), n_files, d_frames, frame_bytes, strides, d_status, hip_stream);
+}
+
+int ifhip_gif_decode_frames_device(const uint8_t* gif, size_t len, uint8_t* d_screens, size_t screen_pitch, uint32_t stride, uint32_t max_frames,
+                                   uint32_t* d_status, uint32_t* n_frames_out, void* hip_stream) {
+    if (!n_frames_out) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null out-pointer");
+    *n_frames_out = 0;
+    if (!gif) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null file pointer");
+    GifParsed P;
+    if (int rc = parse_gif_all(gif, len, &P)) return rc;
+    if (!P.w || !P.h) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: GIF decoding error (a logical screen without pixels)");
+    if (P.status) return refuse(P.status, 0u, P.frames.size());   // what the host walk finds needs no device
+    if (P.frames.size() > max_frames) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: the file has %zu frames, the block holds %u screens", P.frames.size(), max_frames);
+    if (int rc = gif_decode_all_parsed_device(P, d_screens, screen_pitch, stride, d_status, hip_stream)) return rc;
+    // the count is promised only with the file's status: the one wait and the one word this call reads back
+    uint32_t word = 0;
+    HIP_TRY(hipMemcpyAsync(&word, d_status, sizeof word, hipMemcpyDeviceToHost, static_cast<hipStream_t>(hip_stream)));
+    HIP_TRY(static_cast<hipError_t>(wait_stream(hip_stream)));
+    if (!word) *n_frames_out = static_cast<uint32_t>(P.frames.size());
+    return IFHIP_OK;
 }
 
 int ifhip_gif_decode(const uint8_t* gif, size_t len, uint32_t frame_index, uint8_t* bgra, uint32_t stride, size_t capacity, uint32_t* status) {

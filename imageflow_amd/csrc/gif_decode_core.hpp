@@ -274,8 +274,10 @@ IFHIP_HD uint32_t gif_interlace_source_row(uint32_t y, uint32_t h) {
 }
 // Screen::blit for frames 0 .. n - 1 in the reference's order, as far as screen pixel (x, y) sees it: dispose what the
 // previous frame left (gif/disposal.rs:30-53), note what lies under this one where it asks for Previous (:55-76), blit
-// (gif/screen.rs:59-91).
-IFHIP_HD uint32_t gif_compose_pixel(const GifFileDesc& f, const GifFrameDesc* frames, const uint8_t* block, uint32_t x, uint32_t y) {
+// (gif/screen.rs:59-91).  each(k, value): the pixel of the screen behind frame k's blit -- what a reader that asked for
+// frame k is handed.  The pixel's state (its value, what disposal 3 puts back) lives in registers from frame to frame.
+template <typename E>
+IFHIP_HD uint32_t gif_compose_replay(const GifFileDesc& f, const GifFrameDesc* frames, const uint8_t* block, uint32_t x, uint32_t y, E each) {
     const uint32_t* pal = reinterpret_cast<const uint32_t*>(block + f.pal_off);
     uint32_t cur = f.bg, saved = f.bg, method = 1u, pl = 0, pt = 0, pw = 0, ph = 0;
     for (uint32_t i = 0; i < f.n_frames; ++i) {
@@ -289,13 +291,23 @@ IFHIP_HD uint32_t gif_compose_pixel(const GifFileDesc& f, const GifFrameDesc* fr
         const bool inside = sw && sh && x >= l && y >= t && x - l < sw && y - t < sh;
         if (fr.dispose == 3u && inside) saved = cur;
         method = fr.dispose; pl = l; pt = t; pw = sw; ph = sh;
-        if (!inside) continue;
-        const uint32_t fy = y - t, row = fr.interlace ? gif_interlace_source_row(fy, fr.h) : fy;
-        const uint32_t idx = block[fr.index_off + static_cast<uint64_t>(row) * fr.w + (x - l)];
-        if (idx == fr.transparent) continue;
-        cur = idx < fr.pal_n ? pal[fr.pal_off + idx] : 0u;
+        if (inside) {
+            const uint32_t fy = y - t, row = fr.interlace ? gif_interlace_source_row(fy, fr.h) : fy;
+            const uint32_t idx = block[fr.index_off + static_cast<uint64_t>(row) * fr.w + (x - l)];
+            if (idx != fr.transparent) cur = idx < fr.pal_n ? pal[fr.pal_off + idx] : 0u;
+        }
+        each(i, cur);
     }
     return cur;
+}
+// the screen behind the file's last frame alone: what one selected frame asks for
+IFHIP_HD uint32_t gif_compose_pixel(const GifFileDesc& f, const GifFrameDesc* frames, const uint8_t* block, uint32_t x, uint32_t y) {
+    return gif_compose_replay(f, frames, block, x, y, [](uint32_t, uint32_t) {});
+}
+// every screen of the file in one replay: screen k lies `screen_pitch` bytes behind screen k - 1, rows at the file's stride
+IFHIP_HD void gif_compose_all_pixel(const GifFileDesc& f, const GifFrameDesc* frames, const uint8_t* block, uint32_t x, uint32_t y, size_t screen_pitch) {
+    uint8_t* at = f.frame + static_cast<size_t>(y) * f.stride + 4u * static_cast<size_t>(x);
+    (void)gif_compose_replay(f, frames, block, x, y, [&](uint32_t k, uint32_t value) { *reinterpret_cast<uint32_t*>(at + k * screen_pitch) = value; });
 }
 // the first status among a file's frames
 IFHIP_HD uint32_t gif_file_status(const GifFileDesc& f, const GifFrameState* state) {
@@ -379,7 +391,8 @@ struct GifCpuBlock {
 };
 // The batch as the kernels run it, on a block of exactly L.total bytes; status[i]: the files' status words.  grid_x: the
 // workgroups that share a frame's segments, as the kernels' grid does.
-inline void gif_decode_batch_cpu(const GifLayout& L, uint32_t n_files, uint8_t* block, uint32_t* status, uint32_t grid_x = 3u) {
+// all_screens_pitch != 0: every screen of every file, as gif_compose_all_kernel writes them.
+inline void gif_decode_batch_cpu(const GifLayout& L, uint32_t n_files, uint8_t* block, uint32_t* status, uint32_t grid_x = 3u, size_t all_screens_pitch = 0) {
     std::memcpy(block, L.blob.data(), L.blob.size());
     const GifFileDesc* files = reinterpret_cast<const GifFileDesc*>(block + L.files_off);
     const GifFrameDesc* frames = reinterpret_cast<const GifFrameDesc*>(block + L.frames_off);
@@ -409,6 +422,7 @@ inline void gif_decode_batch_cpu(const GifLayout& L, uint32_t n_files, uint8_t* 
         if (status[i]) continue;
         for (uint32_t y = 0; y < files[i].h; ++y)
             for (uint32_t x = 0; x < files[i].w; ++x) {
+                if (all_screens_pitch) { gif_compose_all_pixel(files[i], frames, block, x, y, all_screens_pitch); continue; }
                 const uint32_t v = gif_compose_pixel(files[i], frames, block, x, y);
                 std::memcpy(files[i].frame + static_cast<size_t>(y) * files[i].stride + 4u * x, &v, 4);
             }

@@ -12,6 +12,14 @@
 //   * gather: every dword of the frame's stream is assembled by the lane that owns it;
 //   * finish: the stream into 255-byte sub-blocks, the head, the terminator and ';'.
 // The palette's size -- and with it the minimum code size and the head's length -- is read on the device.
+//
+// N frames into ONE file (ifhip_gif_encode_animation_device): the launches above up to the gather run per chunk
+// of at most max_images frames, then
+//   * offsets (one workgroup): the chunk's body lengths, their exclusive sum on top of the running byte offset that lives on
+//     the device, every frame's head into the stage;
+//   * layout: every dword of the FILE that ends inside the chunk's bytes is assembled by the lane that owns it; the bytes
+//     in front of the first such dword come from the chunk before through a carry word, so no dword is written twice.
+// Nothing is read back between chunks.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -19,6 +27,7 @@
 #include <memory>
 
 #include "block_scan.hpp"
+#include "decode_handoff.hpp"      // StagedBlock
 #include "gif_encode_core.hpp"
 #include "hip_entry.hpp"
 #include "png_quantize.hpp"
@@ -137,6 +146,67 @@ __global__ __launch_bounds__(kGifEncThreads) void gif_finish_kernel(const QuantA
     if (a.status_out) a.status_out[img] = 0u;
 }
 
+// ---- the animation: offsets and layout ------------------------------------------------------------------------------------------------------
+struct GifAnimArgs {
+    uint32_t* run;                  // [0] the file's bytes so far, [1] an overflow was seen, [2], [3] the carry words of even / odd chunks
+    uint32_t *off, *data_bytes, *head_bytes;     // [max_images + 1], [max_images], [max_images]
+    uint8_t* heads;                 // kGifEncScreenPitch + max_images * kGifEncFrameHeadPitch
+    const uint32_t* meta;           // the chunk's frames: delay | user_input << 16
+    uint8_t* file;
+    uint32_t* length;
+    uint32_t* status;
+    uint32_t capacity, n, chunk, first, last, dispose;
+};
+
+__global__ __launch_bounds__(kGifEncThreads) void gif_anim_offsets_kernel(const QuantArgs a, const GifEncArgs g, const GifAnimArgs m) {
+    __shared__ uint32_t scratch[kGifEncThreads / 64u];
+    const uint32_t tid = threadIdx.x;
+    uint32_t base = m.first ? gifenc_screen_bytes(g.repeat) : m.run[0];      // (read by every lane in front of the first barrier, written behind the last)
+    for (uint32_t i0 = 0; i0 < m.n; i0 += kGifEncThreads) {
+        const uint32_t i = i0 + tid;
+        uint32_t body = 0, count = 0, data = 0;
+        const uint32_t* r = a.result + static_cast<size_t>(i) * kPqResultWords;
+        if (i < m.n) {
+            count = r[0];
+            data = (g.seg_bits[static_cast<size_t>(i) * (g.n_seg + 1u) + g.n_seg] + 7u) / 8u;
+            body = gifenc_body_bytes(count, data);
+        }
+        uint32_t total = 0;
+        const uint32_t before = block_exclusive_scan<kGifEncThreads>(body, scratch, &total);
+        if (i < m.n) {
+            m.off[i] = base + before; m.data_bytes[i] = data; m.head_bytes[i] = gifenc_frame_head_bytes(count);
+            gifenc_write_frame_head(m.heads + kGifEncScreenPitch + static_cast<size_t>(i) * kGifEncFrameHeadPitch, a.w, a.h, r + 8, count, r[1], m.meta[i] & 0xFFFFu,
+                                    m.meta[i] >> 16, m.dispose);
+        }
+        base += total;
+    }
+    if (tid != 0u) return;
+    m.off[m.n] = base;
+    const uint32_t seen = m.first ? 0u : m.run[1];
+    m.run[0] = base;
+    m.run[1] = (seen || static_cast<uint64_t>(base) + m.last > m.capacity) ? 1u : 0u;
+    if (m.first) gifenc_write_screen(m.heads, a.w, a.h, g.repeat);
+}
+
+__global__ __launch_bounds__(kGifEncThreads) void gif_anim_layout_kernel(const GifEncArgs g, const GifAnimArgs m) {
+    const uint32_t overflow = m.run[1];
+    GifAnimChunk c;
+    c.off = m.off; c.heads = m.heads; c.streams = reinterpret_cast<const uint8_t*>(g.stream); c.data_bytes = m.data_bytes; c.head_bytes = m.head_bytes;
+    c.n = m.n; c.stream_pitch = g.stream_words * 4u; c.first = m.first; c.last = m.last;
+    c.lo = m.first ? 0u : m.off[0]; c.hi = m.off[m.n] + m.last;
+    const bool lane0 = blockIdx.x == 0u && threadIdx.x == 0u;
+    if (m.last && lane0) { *m.length = overflow ? 0u : c.hi; if (m.status) *m.status = overflow ? kGifEncFileOverflow : 0u; }
+    if (overflow) return;                                        // (uniform; c.hi <= capacity from here on)
+    const uint32_t carry_in = m.first ? 0u : m.run[2u + ((m.chunk + 1u) & 1u)];
+    const uint32_t j0 = c.lo / 4u, j1 = c.hi / 4u;
+    uint32_t* file = reinterpret_cast<uint32_t*>(m.file);
+    for (uint32_t j = j0 + blockIdx.x * kGifEncThreads + threadIdx.x; j < j1; j += gridDim.x * kGifEncThreads) file[j] = gifenc_animation_word(c, j, carry_in);
+    if (!lane0) return;
+    const uint32_t tail = gifenc_animation_word(c, j1, carry_in);  // the bytes behind the last whole dword
+    if (!m.last) { m.run[2u + (m.chunk & 1u)] = tail; return; }
+    for (uint32_t p = 4u * j1; p < c.hi; ++p) m.file[p] = static_cast<uint8_t>(tail >> (8u * (p - 4u * j1)));
+}
+
 }  // namespace ifhip
 
 using namespace ifhip;
@@ -149,7 +219,9 @@ struct ifhip_gif_enc_stage {
     uint32_t *d_slots = nullptr, *d_seg_bits = nullptr, *d_stream = nullptr;
     uint32_t *d_tables = nullptr, *d_ekey = nullptr, *d_ew = nullptr, *d_result = nullptr;   // the quantiser's (the state words lie behind the tables)
     uint64_t* d_edmin = nullptr;
-    StageScratch blocks{&d_indices, &d_slots, &d_seg_bits, &d_stream, &d_tables, &d_ekey, &d_ew, &d_edmin, &d_result};
+    uint32_t* d_anim = nullptr;                          // the animation's running words, offsets and lengths (GifAnimArgs)
+    uint8_t* d_anim_heads = nullptr;
+    StageScratch blocks{&d_indices, &d_slots, &d_seg_bits, &d_stream, &d_tables, &d_ekey, &d_ew, &d_edmin, &d_result, &d_anim, &d_anim_heads};
 };
 
 namespace {
@@ -165,8 +237,40 @@ int gif_enc_stage_allocate(ifhip_gif_enc_stage* s) {
         HIP_TRY(DEV_MALLOC(&s->d_ew, n * kPqMaxEntries * sizeof(uint32_t)));
         HIP_TRY(DEV_MALLOC(&s->d_edmin, n * kPqMaxEntries * sizeof(uint64_t)));
         HIP_TRY(DEV_MALLOC(&s->d_result, n * kPqResultWords * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_anim, (8u + 3u * n + 1u) * sizeof(uint32_t)));
+        HIP_TRY(DEV_MALLOC(&s->d_anim_heads, kGifEncScreenPitch + n * kGifEncFrameHeadPitch));
         return IFHIP_OK;
     });
+}
+// the arguments of one batch of `n_images` frames through the stage (the caller adds where the files go)
+void gif_enc_args(ifhip_gif_enc_stage* stage, const uint8_t* d_images, size_t image_bytes, uint32_t stride, int alpha_meaningful, uint32_t n_images, int repeat,
+                  QuantArgs* qp, GifEncArgs* gp) {
+    QuantArgs& q = *qp;
+    std::memset(&q, 0, sizeof q);
+    q.images = d_images; q.image_bytes = image_bytes; q.stride = stride; q.w = stage->width; q.h = stage->height; q.n_images = n_images;
+    q.alpha = alpha_meaningful ? 1u : 0u; q.max_colors = kPqMaxColors; q.key_rule = kPqKeyGif;
+    // the pngquant preset's defaults (codecs/pngquant.rs:50-57): target 100, minimum 0, speed 4
+    q.iterations = pq_speed_iterations(4u); q.max_entries = pq_speed_max_entries(4u);
+    q.bound_target = pq_quality_bound(100u); q.bound_min = pq_quality_bound(0u);
+    q.tables = stage->d_tables; q.state = stage->d_tables + quant_table_words(stage->max_images);
+    q.ekey = stage->d_ekey; q.ew = stage->d_ew; q.edmin = stage->d_edmin; q.result = stage->d_result;
+    GifEncArgs& g = *gp;
+    std::memset(&g, 0, sizeof g);
+    g.n_seg = stage->n_seg; g.slot_words = gifenc_slot_words(); g.stream_words = stage->stream_words; g.index_pitch = stage->index_pitch;
+    g.indices = stage->d_indices; g.slots = stage->d_slots; g.seg_bits = stage->d_seg_bits; g.stream = stage->d_stream;
+    g.repeat = repeat;
+}
+// palette, remap, lzw, scan and gather: every frame's LZW stream and its length in the stage
+int gif_enc_launch_streams(ifhip_gif_enc_stage* stage, const QuantArgs& q, const GifEncArgs& g, hipStream_t st) {
+    if (int rc = pq_launch_palette(q, st)) return rc;
+    const uint32_t npix = stage->width * stage->height;
+    const uint32_t pixel_blocks = std::min(1024u, (npix + kGifEncThreads - 1u) / kGifEncThreads);
+    const uint32_t word_blocks = std::min(1024u, (stage->stream_words + kGifEncThreads - 1u) / kGifEncThreads);
+    hipLaunchKernelGGL(gif_remap_kernel, dim3(pixel_blocks, q.n_images), dim3(kGifEncThreads), 0, st, q, g);
+    hipLaunchKernelGGL(gif_lzw_kernel, dim3(stage->n_seg, q.n_images), dim3(64), 0, st, q, g);
+    hipLaunchKernelGGL(gif_enc_scan_kernel, dim3(q.n_images), dim3(kGifEncThreads), 0, st, g);
+    hipLaunchKernelGGL(gif_gather_kernel, dim3(word_blocks, q.n_images), dim3(kGifEncThreads), 0, st, g);
+    return IFHIP_OK;
 }
 }  // namespace
 
@@ -210,30 +314,76 @@ int ifhip_gif_encode_batch_device(ifhip_gif_enc_stage* stage, const uint8_t* d_i
     if (int rc = gif_enc_stage_allocate(stage)) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     QuantArgs q;
-    std::memset(&q, 0, sizeof q);
-    q.images = d_images; q.image_bytes = image_bytes; q.stride = stride; q.w = stage->width; q.h = stage->height; q.n_images = n_images;
-    q.alpha = alpha_meaningful ? 1u : 0u; q.max_colors = kPqMaxColors; q.key_rule = kPqKeyGif;
-    // the pngquant preset's defaults (codecs/pngquant.rs:50-57): target 100, minimum 0, speed 4
-    q.iterations = pq_speed_iterations(4u); q.max_entries = pq_speed_max_entries(4u);
-    q.bound_target = pq_quality_bound(100u); q.bound_min = pq_quality_bound(0u);
-    q.tables = stage->d_tables; q.state = stage->d_tables + quant_table_words(stage->max_images);
-    q.ekey = stage->d_ekey; q.ew = stage->d_ew; q.edmin = stage->d_edmin; q.result = stage->d_result;
+    GifEncArgs g;
+    gif_enc_args(stage, d_images, image_bytes, stride, alpha_meaningful, n_images, repeat, &q, &g);
     q.palettes = d_palettes; q.indices = d_indices;
     q.files = d_files; q.file_pitch = file_pitch; q.lengths = d_lengths; q.status_out = d_status;
-    GifEncArgs g;
-    std::memset(&g, 0, sizeof g);
-    g.n_seg = stage->n_seg; g.slot_words = gifenc_slot_words(); g.stream_words = stage->stream_words; g.index_pitch = stage->index_pitch;
-    g.indices = stage->d_indices; g.slots = stage->d_slots; g.seg_bits = stage->d_seg_bits; g.stream = stage->d_stream;
-    g.repeat = repeat; g.delay = delay; g.user_input = needs_user_input ? 1u : 0u;
-    if (int rc = pq_launch_palette(q, st)) return rc;
-    const uint32_t npix = stage->width * stage->height;
-    const uint32_t pixel_blocks = std::min(1024u, (npix + kGifEncThreads - 1u) / kGifEncThreads);
+    g.delay = delay; g.user_input = needs_user_input ? 1u : 0u;
+    if (int rc = gif_enc_launch_streams(stage, q, g, st)) return rc;
     const uint32_t word_blocks = std::min(1024u, (stage->stream_words + kGifEncThreads - 1u) / kGifEncThreads);
-    hipLaunchKernelGGL(gif_remap_kernel, dim3(pixel_blocks, n_images), dim3(kGifEncThreads), 0, st, q, g);
-    hipLaunchKernelGGL(gif_lzw_kernel, dim3(stage->n_seg, n_images), dim3(64), 0, st, q, g);
-    hipLaunchKernelGGL(gif_enc_scan_kernel, dim3(n_images), dim3(kGifEncThreads), 0, st, g);
-    hipLaunchKernelGGL(gif_gather_kernel, dim3(word_blocks, n_images), dim3(kGifEncThreads), 0, st, g);
     hipLaunchKernelGGL(gif_finish_kernel, dim3(word_blocks, n_images), dim3(kGifEncThreads), 0, st, q, g);
+    HIP_TRY(hipGetLastError());
+    return IFHIP_OK;
+}
+
+int ifhip_gif_enc_stage_max_animation_bytes(const ifhip_gif_enc_stage* stage, uint32_t n_frames, size_t* bytes) {
+    if (!bytes) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null out-pointer");
+    *bytes = 0;
+    if (!stage) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null stage");
+    if (n_frames == 0) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: an animation has one frame at the least");
+    // the head with NETSCAPE2.0, n times the one-frame file's bound (above a body's), ';'
+    const uint64_t bound = gifenc_screen_bytes(0) + static_cast<uint64_t>(n_frames) * gifenc_max_file_bytes(static_cast<uint64_t>(stage->width) * stage->height) + 1u;
+    if (bound >= (1ull << 32))
+        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: %u frames of %ux%u may need %llu bytes (byte offsets in the file are 32 bits wide)", n_frames, stage->width,
+                    stage->height, static_cast<unsigned long long>(bound));
+    *bytes = static_cast<size_t>(bound);
+    return IFHIP_OK;
+}
+
+int ifhip_gif_encode_animation_device(ifhip_gif_enc_stage* stage, const uint8_t* d_images, size_t image_bytes, uint32_t stride, int alpha_meaningful,
+                                      uint32_t n_frames, int repeat, const uint32_t* delays, const uint8_t* user_input, uint8_t* d_file, size_t capacity,
+                                      uint32_t* d_length, uint32_t* d_status, void* hip_stream) {
+    if (!stage) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null stage");
+    if (n_frames == 0) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: an animation has one frame at the least");
+    if (int rc = check_frames(d_images, image_bytes, stage->width, stage->height, stride, "image")) return rc;
+    if (!d_file || !d_length || !delays || !user_input) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
+    if (reinterpret_cast<uintptr_t>(d_file) & 3u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: the file's block must be 4-byte aligned");
+    if (repeat < -1 || repeat > 65535) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: repeat is -1 (none) or 0..65535");
+    for (uint32_t k = 0; k < n_frames; ++k)
+        if (delays[k] > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: delay is 0..65535 hundredths of a second (frame %u)", k);
+    if (capacity < gifenc_screen_bytes(0) + 1u)                  // (not even the screen part and ';': never a file, whatever the frames hold)
+        return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: capacity below %u bytes", gifenc_screen_bytes(0) + 1u);
+    size_t bound = 0;
+    if (int rc = ifhip_gif_enc_stage_max_animation_bytes(stage, n_frames, &bound)) return rc;
+    if (int rc = gif_enc_stage_allocate(stage)) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    StagedBlock meta(st);                                        // delay | user_input << 16 per frame: the one upload
+    if (int rc = meta.alloc(4u * static_cast<size_t>(n_frames), 4u * static_cast<size_t>(n_frames))) return rc;
+    for (uint32_t k = 0; k < n_frames; ++k) {
+        const uint32_t word = delays[k] | (user_input[k] ? 1u << 16 : 0u);
+        std::memcpy(meta.host + 4u * static_cast<size_t>(k), &word, 4);
+    }
+    if (int rc = meta.send()) return rc;
+    const uint32_t n = stage->max_images;
+    GifAnimArgs m;
+    std::memset(&m, 0, sizeof m);
+    m.run = stage->d_anim; m.off = stage->d_anim + 8; m.data_bytes = m.off + n + 1u; m.head_bytes = m.data_bytes + n; m.heads = stage->d_anim_heads;
+    m.file = d_file; m.length = d_length; m.status = d_status;
+    m.capacity = static_cast<uint32_t>(std::min<size_t>(capacity, 0xFFFFFFFFu));
+    m.dispose = gifenc_animation_dispose(n_frames, alpha_meaningful != 0);
+    const uint64_t body_words = (gifenc_max_body_bytes(static_cast<uint64_t>(stage->width) * stage->height) + 3u) / 4u;
+    for (uint32_t base = 0, chunk = 0; base < n_frames; base += n, ++chunk) {
+        const uint32_t count = std::min(n, n_frames - base);
+        QuantArgs q;
+        GifEncArgs g;
+        gif_enc_args(stage, d_images + static_cast<size_t>(base) * image_bytes, image_bytes, stride, alpha_meaningful, count, repeat, &q, &g);
+        if (int rc = gif_enc_launch_streams(stage, q, g, st)) return rc;
+        m.meta = reinterpret_cast<const uint32_t*>(meta.block) + base;
+        m.n = count; m.chunk = chunk; m.first = base == 0u ? 1u : 0u; m.last = base + count == n_frames ? 1u : 0u;
+        const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>(4096u, (body_words * count + 16u + kGifEncThreads - 1u) / kGifEncThreads));
+        hipLaunchKernelGGL(gif_anim_offsets_kernel, dim3(1), dim3(kGifEncThreads), 0, st, q, g, m);
+        hipLaunchKernelGGL(gif_anim_layout_kernel, dim3(blocks), dim3(kGifEncThreads), 0, st, g, m);
+    }
     HIP_TRY(hipGetLastError());
     return IFHIP_OK;
 }

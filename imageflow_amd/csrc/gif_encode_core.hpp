@@ -140,9 +140,9 @@ IFHIP_HD uint32_t gifenc_gather_word(const uint32_t* off, uint32_t n_seg, const 
 IFHIP_HD uint32_t gifenc_head_bytes(uint32_t count, int32_t repeat) { return 6u + 7u + (repeat >= 0 ? 19u : 0u) + 8u + 10u + 3u * (1u << gifenc_palette_bits(count)) + 1u; }
 IFHIP_HD uint64_t gifenc_data_position(uint64_t i) { return i + i / 255u + 1u; }
 IFHIP_HD uint64_t gifenc_file_bytes(uint32_t head, uint64_t data_bytes) { return head + data_bytes + (data_bytes + 254u) / 255u + 2u; }
-// keys: the palette in file order (the transparent entry, if any, is entry 0).  One lane.  Returns the bytes written.
-IFHIP_HD uint32_t gifenc_write_head(uint8_t* o, uint32_t w, uint32_t h, const uint32_t* keys, uint32_t count, uint32_t n_trans, int32_t repeat, uint32_t delay,
-                                    uint32_t user_input) {
+// The file's own part of the head: signature, logical screen, NETSCAPE2.0.  One lane.  Returns the bytes written.
+IFHIP_HD uint32_t gifenc_screen_bytes(int32_t repeat) { return 6u + 7u + (repeat >= 0 ? 19u : 0u); }
+IFHIP_HD uint32_t gifenc_write_screen(uint8_t* o, uint32_t w, uint32_t h, int32_t repeat) {
     uint8_t* c = o;
     const uint8_t sig[6] = {'G', 'I', 'F', '8', '9', 'a'};
     for (int i = 0; i < 6; ++i) *c++ = sig[i];
@@ -153,8 +153,17 @@ IFHIP_HD uint32_t gifenc_write_head(uint8_t* o, uint32_t w, uint32_t h, const ui
         for (int i = 0; i < 14; ++i) *c++ = app[i];
         *c++ = 3; *c++ = 1; *c++ = static_cast<uint8_t>(repeat); *c++ = static_cast<uint8_t>(repeat >> 8); *c++ = 0;
     }
-    *c++ = 0x21; *c++ = 0xF9; *c++ = 4;                          // disposal 1 (keep), as the gif crate's Frame::default
-    *c++ = static_cast<uint8_t>(1u << 2 | (user_input ? 2u : 0u) | (n_trans ? 1u : 0u));
+    return static_cast<uint32_t>(c - o);
+}
+// A frame's part: graphic control extension, image descriptor, local table, minimum code size.  keys: the palette in file
+// order (the transparent entry, if any, is entry 0).  One lane.  Returns the bytes written.
+IFHIP_HD uint32_t gifenc_frame_head_bytes(uint32_t count) { return 8u + 10u + 3u * (1u << gifenc_palette_bits(count)) + 1u; }
+constexpr uint32_t kGifEncFrameHeadMax = 8u + 10u + 768u + 1u;
+IFHIP_HD uint32_t gifenc_write_frame_head(uint8_t* o, uint32_t w, uint32_t h, const uint32_t* keys, uint32_t count, uint32_t n_trans, uint32_t delay, uint32_t user_input,
+                                          uint32_t dispose) {
+    uint8_t* c = o;
+    *c++ = 0x21; *c++ = 0xF9; *c++ = 4;
+    *c++ = static_cast<uint8_t>(dispose << 2 | (user_input ? 2u : 0u) | (n_trans ? 1u : 0u));
     *c++ = static_cast<uint8_t>(delay); *c++ = static_cast<uint8_t>(delay >> 8); *c++ = 0; *c++ = 0;
     const uint32_t bits = gifenc_palette_bits(count);
     *c++ = 0x2C; *c++ = 0; *c++ = 0; *c++ = 0; *c++ = 0;
@@ -166,6 +175,67 @@ IFHIP_HD uint32_t gifenc_write_head(uint8_t* o, uint32_t w, uint32_t h, const ui
     }
     *c++ = static_cast<uint8_t>(gifenc_min_code(count));
     return static_cast<uint32_t>(c - o);
+}
+// the head of a one-frame file: disposal 1 (keep), as the gif crate's Frame::default
+IFHIP_HD uint32_t gifenc_write_head(uint8_t* o, uint32_t w, uint32_t h, const uint32_t* keys, uint32_t count, uint32_t n_trans, int32_t repeat, uint32_t delay,
+                                    uint32_t user_input) {
+    const uint32_t at = gifenc_write_screen(o, w, h, repeat);
+    return at + gifenc_write_frame_head(o + at, w, h, keys, count, n_trans, delay, user_input, 1u);
+}
+
+// ---- the animation: N frames in one file -------------------------------------------------------------------------------------
+// The file is the screen part, then per frame a BODY -- the frame's head, its data in sub-blocks, the terminator -- then ';'.
+// Frames of meaningful alpha carry disposal 2 in a file of more than one frame: with the reference's Keep a transparent
+// pixel of frame k would show frame k - 1 through it.  A one-frame file is the one-frame coder's, byte for byte.
+IFHIP_HD uint32_t gifenc_animation_dispose(uint32_t n_frames, bool alpha_meaningful) { return n_frames > 1u && alpha_meaningful ? 2u : 1u; }
+IFHIP_HD uint32_t gifenc_body_bytes(uint32_t count, uint32_t data_bytes) { return gifenc_frame_head_bytes(count) + data_bytes + (data_bytes + 254u) / 255u + 1u; }
+IFHIP_HD uint64_t gifenc_max_body_bytes(uint64_t n_pix) { const uint64_t d = gifenc_max_data_bytes(n_pix); return kGifEncFrameHeadMax + d + (d + 254u) / 255u + 1u; }
+// Byte q of a body: head: the frame's head (head_bytes of it), data: its LZW stream of data_bytes.
+IFHIP_HD uint32_t gifenc_body_byte(const uint8_t* head, uint32_t head_bytes, const uint8_t* data, uint32_t data_bytes, uint32_t q) {
+    if (q < head_bytes) return head[q];
+    const uint32_t s = q - head_bytes, blk = s >> 8, r = s & 255u;         // a sub-block: its length byte and 255 bytes
+    if (s >= data_bytes + (data_bytes + 254u) / 255u) return 0u;           // the terminator
+    if (r == 0u) return data_bytes - 255u * blk < 255u ? data_bytes - 255u * blk : 255u;
+    return data[255u * blk + r - 1u];
+}
+// What one chunk of frames adds to the file.  off[0 .. n]: the byte offsets of the chunk's bodies in the FILE and its end;
+// [lo, hi) is what the chunk owns: with the screen part in front where it is the first, with ';' behind where it is the last.
+struct GifAnimChunk {
+    const uint32_t* off;             // [n + 1]
+    const uint8_t* heads;            // the screen part (32 bytes), then a frame head every kGifEncFrameHeadPitch bytes
+    const uint8_t* streams;          // a frame's LZW data every stream_pitch bytes
+    const uint32_t* data_bytes;      // [n]
+    const uint32_t* head_bytes;      // [n]
+    uint32_t n, stream_pitch, lo, hi, first, last;
+};
+constexpr uint32_t kGifEncScreenPitch = 32u, kGifEncFrameHeadPitch = 800u;
+IFHIP_HD uint32_t gifenc_animation_byte(const GifAnimChunk& c, uint32_t p, uint32_t* frame) {
+    if (p < c.off[0]) return c.heads[p];                                    // (the first chunk: the screen part)
+    if (p >= c.off[c.n]) return 0x3Bu;                                      // (the last chunk)
+    uint32_t i = *frame;
+    while (p >= c.off[i + 1u]) ++i;
+    *frame = i;
+    return gifenc_body_byte(c.heads + kGifEncScreenPitch + static_cast<size_t>(i) * kGifEncFrameHeadPitch, c.head_bytes[i],
+                            c.streams + static_cast<size_t>(i) * c.stream_pitch, c.data_bytes[i], p - c.off[i]);
+}
+// The rule of the gather, stated over the FILE's dwords: dword j is assembled, all four bytes, by the one lane that owns
+// it, so two frames that share a dword never both write it.  A chunk owns the dwords that END inside [lo, hi): j in
+// [lo / 4, hi / 4).  The bytes of dword lo / 4 in front of lo belong to the chunk before: it left them in `carry_in` (the
+// dword's low bytes).  The bytes behind the chunk's last whole dword go to the next chunk the same way, or -- the last
+// chunk -- are stored one by one.
+IFHIP_HD uint32_t gifenc_animation_first_frame(const GifAnimChunk& c, uint32_t p) {
+    uint32_t lo = 0, hi = c.n;                                   // the last body that starts at or before p
+    while (hi - lo > 1u) { const uint32_t mid = (lo + hi) >> 1; if (c.off[mid] <= p) lo = mid; else hi = mid; }
+    return lo;
+}
+IFHIP_HD uint32_t gifenc_animation_word(const GifAnimChunk& c, uint32_t j, uint32_t carry_in) {
+    uint32_t word = 0, frame = gifenc_animation_first_frame(c, 4u * j < c.lo ? c.lo : 4u * j);
+    for (uint32_t b = 0; b < 4u; ++b) {
+        const uint32_t p = 4u * j + b;
+        const uint32_t v = p < c.lo ? (carry_in >> (8u * b)) & 0xFFu : p < c.hi ? gifenc_animation_byte(c, p, &frame) : 0u;
+        word |= v << (8u * b);
+    }
+    return word;
 }
 
 #ifndef __HIPCC__

@@ -125,6 +125,12 @@ int parse_gif(const uint8_t* d, size_t len, uint32_t target, GifParsed* out) {
     return IFHIP_OK;
 }
 
+int parse_gif_all(const uint8_t* d, size_t len, GifParsed* out) {
+    if (int rc = parse_gif(d, len, 0xFFFFFFFFu, out)) return rc;
+    if (out->status == IFHIP_GIF_DEC_NO_SUCH_FRAME && !out->frames.empty()) out->status = 0;     // (the walk's end, not a frame someone asked for)
+    return IFHIP_OK;
+}
+
 const char* gif_status_text(uint32_t s) {
     switch (s) {
     case IFHIP_GIF_DEC_TOO_LITTLE: return "the image data holds fewer indices than the frame has pixels";
@@ -148,5 +154,21 @@ extern "C" int ifhip_gif_info(const uint8_t* gif, size_t len, ifhip_gif_file_inf
     GifParsed P;
     if (int rc = parse_gif_header(gif, len, &P)) return rc;
     info->width = P.w; info->height = P.h; info->has_global_palette = P.has_global ? 1u : 0u; info->background_index = P.bg_index;
+    return IFHIP_OK;
+}
+
+extern "C" int ifhip_gif_frame_count(const uint8_t* gif, size_t len, uint32_t* n_frames, uint32_t* delays, uint32_t* flags, uint32_t capacity) {
+    if (!n_frames) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null out-pointer");
+    *n_frames = 0;
+    if (!gif) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null file pointer");
+    GifParsed P;
+    if (int rc = parse_gif_all(gif, len, &P)) return rc;
+    *n_frames = static_cast<uint32_t>(P.frames.size());
+    for (uint32_t k = 0; k < *n_frames && k < capacity; ++k) {
+        if (delays) delays[k] = P.frames[k].delay;
+        if (flags) flags[k] = P.frames[k].user_input;
+    }
+    if (P.status && P.status != IFHIP_GIF_DEC_NO_SUCH_FRAME)      // (a file without a frame counts 0)
+        return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: GIF decoding error: %s", gif_status_text(P.status));
     return IFHIP_OK;
 }

@@ -36,9 +36,14 @@ struct GifParsed {
 int parse_gif_header(const uint8_t* d, size_t len, GifParsed* out);
 // The walk up to frame `target`.  Fails like parse_gif_header; everything behind the header is the status word.
 int parse_gif(const uint8_t* d, size_t len, uint32_t target, GifParsed* out);
+// The walk to the file's end: every frame, status 0 where the walk met nothing wrong and saw a frame at the least.
+int parse_gif_all(const uint8_t* d, size_t len, GifParsed* out);
 // The device part of a decode (csrc/gif_decode.hip).  files[i] == nullptr: the file's header did not parse.
 int gif_decode_parsed_device(const GifParsed* const* files, uint32_t n_files, uint8_t* const* d_frames, const size_t* frame_bytes,
                              const uint32_t* strides, uint32_t* d_status, void* hip_stream);
+// As gif_decode_parsed_device for ONE file, every screen: screen k (the logical screen behind frame k's blit) lies at
+// d_screens + k * screen_pitch.  The file's status word goes to d_status[0]; a damaged frame anywhere: no screen is written.
+int gif_decode_all_parsed_device(const GifParsed& file, uint8_t* d_screens, size_t screen_pitch, uint32_t stride, uint32_t* d_status, void* hip_stream);
 const char* gif_status_text(uint32_t status);
 
 }  // namespace ifhip

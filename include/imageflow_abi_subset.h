@@ -131,6 +131,19 @@ IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_color_management(struct imageflow
  * codecs/gif/mod.rs:385-592) and reports image/gif; off by default, where the preset writes the raw BGRA container as ever.  A
  * GIF input of the job hands its loop count and the selected frame's delay and user-input flag to the file. */
 IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_gif_encoder(struct imageflow_context *context, int on);
+/* EXTENSION: animated GIFs pass through jobs, as the reference re-runs a job for every frame (GifDecoder::has_more_frames /
+ * ctx.set_more_frames, codecs/gif/mod.rs:207-305; GifEncoder::write_frame with its frame_ix, :429-521).  Off by default.  The
+ * path applies only where this switch AND the GIF encoder are on, a `decode` node reads a GIF of more than one frame with
+ * no select_frame told to it, and an `encode` node with the "gif" preset lies downstream of it: the source's screens are
+ * decoded once (ifhip_gif_decode_frames_device), the framewise job runs once per frame, every "gif" encode node collects
+ * its frames on the device and codes them in ONE call behind the last (ifhip_gif_encode_animation_device: frame k's delay
+ * and user-input flag are the source frame's).  Every other encoder takes frame 0 and writes once; watermarks and a
+ * command_string's own decode do not animate.  Several animated decodes must agree on the frame count (InvalidOperation);
+ * the decoded screens and the collected frames together may hold security.max_total_file_pixels pixels at the most (the
+ * reference's check_total_pixels, codecs/gif/mod.rs:103-118; default 400 000 000, imageflow_types/src/lib.rs:1212-1235): a job
+ * over it is refused as SizeLimitExceeded before anything is allocated.  Every other job is byte for byte what it is with
+ * the switch off. */
+IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_gif_animation(struct imageflow_context *context, int on);
 /* EXTENSION.  Device coding of the libjpeg_turbo preset's options, off by default: with on != 0 an encode with
  * "progressive" and / or "optimize_huffman_coding" is entropy-coded on the device (ifhip_jpeg_encode_flags_batch_device:
  * only the file is downloaded, not the coefficient planes) -- first with room for streams half the size of the

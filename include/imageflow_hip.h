@@ -706,8 +706,8 @@ IFHIP_API int ifhip_webp_decode(const uint8_t* webp, size_t len, uint8_t* bgra, 
  * clear codes.
  * Known differences: the reference's LZW reader (the gif crate) is not on hand -- a stream that yields fewer indices than
  * width x height is refused (TOO_LITTLE) as Pillow refuses it; indices beyond width x height and bytes behind the end code
- * are ignored; a code that names an entry the table does not hold yet is BAD_CODE wherever it stands in the stream.  Not
- * built: multi-frame output.
+ * are ignored; a code that names an entry the table does not hold yet is BAD_CODE wherever it stands in the stream.
+ * Every screen of an animation in one pass: ifhip_gif_decode_frames_device; the frames' count and timing: ifhip_gif_frame_count.
  *
  * Status word of a file (d_status[i]): 0, or why no frame was written. */
 #define IFHIP_GIF_DEC_TOO_LITTLE 1       /* a frame's stream holds fewer indices than width x height            */
@@ -741,6 +741,21 @@ IFHIP_API int ifhip_gif_decode_batch_device(const uint8_t* const* files, const s
  * requested but GIF only has M frames"). */
 IFHIP_API int ifhip_gif_decode(const uint8_t* gif, size_t len, uint32_t frame_index, uint8_t* bgra, uint32_t stride, size_t capacity,
                                uint32_t* status);
+/* The walk of the container to its end (GifDecoder::has_more_frames until it says no, mod.rs:300-305): *n_frames, and for
+ * the first `capacity` frames delays[k] (hundredths of a second) and flags[k] (the user-input flag) of their graphic control
+ * extensions (both arrays nullable).  A file without a frame counts 0; a file the walk refuses is IFHIP_INVALID_ARGUMENT
+ * with an "ImageMalformed: GIF decoding error" message, *n_frames the frames seen up to there.  Host only, no device needed. */
+IFHIP_API int ifhip_gif_frame_count(const uint8_t* gif, size_t len, uint32_t* n_frames, uint32_t* delays, uint32_t* flags, uint32_t capacity);
+/* Every composed screen of ONE file in one pass: screen k -- the logical screen behind Screen::blit of frame k, exactly what
+ * ifhip_gif_decode(..., frame_index = k) gives -- lands at d_screens + k * screen_pitch as BGRA rows of `stride` bytes; only
+ * 4 * width bytes of a row are written.  The block holds max_frames screens; a file of more frames is refused.  The LZW
+ * launches are the batch's; the replay runs ONCE over the frame list and stores the pixel into screen k behind each blit.
+ * A damaged frame anywhere fails the file: no screen is written, d_status[0] (device) holds the status word and
+ * *n_frames_out is 0; otherwise *n_frames_out is the number of screens.  What the host walk finds is refused as
+ * ifhip_gif_decode refuses it.  The call waits for hip_stream once, for the status word.  Argument and frame checks come
+ * before the device check. */
+IFHIP_API int ifhip_gif_decode_frames_device(const uint8_t* gif, size_t len, uint8_t* d_screens, size_t screen_pitch, uint32_t stride,
+                                             uint32_t max_frames, uint32_t* d_status, uint32_t* n_frames_out, void* hip_stream);
 
 /* Device GIF coder: EncoderPreset::Gif without the host: what GifEncoder::write_frame (imageflow_core/src/codecs/gif/mod.rs:385-592)
  * has the gif crate do -- one frame as a GIF89a file: the logical screen of the frame's size (size_16(): both sides at most
@@ -751,7 +766,8 @@ IFHIP_API int ifhip_gif_decode(const uint8_t* gif, size_t len, uint32_t frame_in
  * defaults: target 100, minimum 0, speed 4): a frame of at most 256 distinct colours after the alpha rule keeps exactly
  * those; otherwise it is NOT the gif crate's NeuQuant palette.  The LZW stream carries a clear code every
  * IFHIP_GIF_ENC_SEGMENT_PIXELS pixels, so that a wave codes a segment on its own (csrc/gif_encode.hip); every reader takes
- * it.  Not built: multi-frame output, dithering.  A stage owns the scratch of a call in flight and is bound to ONE stream
+ * it.  N frames into one file: ifhip_gif_encode_animation_device.  Not built: dithering, frame differencing, a shared
+ * palette.  A stage owns the scratch of a call in flight and is bound to ONE stream
  * at a time, like ifhip_png_quant_stage. */
 #ifndef IFHIP_GIF_ENC_SEGMENT_PIXELS
 #define IFHIP_GIF_ENC_SEGMENT_PIXELS 16384
@@ -775,6 +791,24 @@ IFHIP_API int ifhip_gif_encode_batch_device(ifhip_gif_enc_stage* stage, const ui
                                             int alpha_meaningful, uint32_t n_images, int repeat, uint32_t delay, int needs_user_input,
                                             uint8_t* d_files, size_t file_pitch, uint32_t* d_lengths, uint32_t* d_status,
                                             uint8_t* d_palettes, uint8_t* d_indices, void* hip_stream);
+/* A `capacity` with which no animation of n_frames frames overflows, by arithmetic alone: the head with NETSCAPE2.0, n_frames
+ * times ifhip_gif_enc_stage_max_file_bytes, the trailer.  2^32 bytes or more: IFHIP_INVALID_ARGUMENT (byte offsets are 32 bits). */
+IFHIP_API int ifhip_gif_enc_stage_max_animation_bytes(const ifhip_gif_enc_stage* stage, uint32_t n_frames, size_t* bytes);
+/* n_frames frames (as the batch's images) into ONE GIF89a file at d_file (4-byte aligned, `capacity` bytes): the logical screen
+ * of the frame size, no global table, NETSCAPE2.0 when repeat >= 0, then per frame a graphic control extension (delays[k],
+ * user_input[k] -- both arrays in HOST memory, read before the call returns -- and the transparent entry if any), an image
+ * descriptor at (0, 0) of the full size with a local colour table, and the frame's LZW data: exactly the bytes the one-frame
+ * coder writes for that frame; then ';'.  A one-frame file is ifhip_gif_encode_batch_device's, byte for byte.  In a file of
+ * more than one frame, frames of meaningful alpha carry disposal 2 (restore to background) -- the reference writes the gif
+ * crate's Keep there (mod.rs:500-504), which lets frame k - 1 show through the transparent pixels of frame k; frames without
+ * alpha carry Keep as the one-frame file does.  n_frames may exceed the stage's max_images: the stage then runs in chunks of
+ * max_images frames with a running byte offset on the device, nothing is read back in between.  d_length[0]: the file's
+ * length, 0 with IFHIP_GIF_FILE_OVERFLOW in d_status[0] (nullable) where it exceeds `capacity`.  Asynchronous on hip_stream
+ * behind the upload of the two arrays. */
+IFHIP_API int ifhip_gif_encode_animation_device(ifhip_gif_enc_stage* stage, const uint8_t* d_images, size_t image_bytes, uint32_t stride,
+                                                int alpha_meaningful, uint32_t n_frames, int repeat, const uint32_t* delays,
+                                                const uint8_t* user_input, uint8_t* d_file, size_t capacity, uint32_t* d_length,
+                                                uint32_t* d_status, void* hip_stream);
 /* The synchronous host-buffer form: one frame.  out == NULL: only *len (the size needed) is written. */
 IFHIP_API int ifhip_gif_encode(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int alpha_meaningful, int repeat,
                                uint32_t delay, int needs_user_input, uint8_t* out, size_t capacity, size_t* len);
