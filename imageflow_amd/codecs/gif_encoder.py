@@ -4,11 +4,11 @@ files in HBM.  For tests and tools; the job path is the `"gif"` preset of `encod
 switched on (Context.set_gif_encoder, csrc/abi_shim.cpp)."""
 import ctypes as C
 
-import numpy as np
 import torch
 
 from .. import _native
 from ..graphics.bitmaps import Bitmap
+from ._file_encoder import FileEncodeStage, encode_host, files_as_bytes, palettes_from_taps
 
 GIF_FILE_OVERFLOW = 1                   # include/imageflow_hip.h IFHIP_GIF_FILE_OVERFLOW
 SEGMENT_PIXELS = 16384                  # IFHIP_GIF_ENC_SEGMENT_PIXELS
@@ -36,49 +36,34 @@ def _bind():
     return L
 
 
-class GifEncodeStage:
+class GifEncodeStage(FileEncodeStage):
     """ifhip_gif_enc_stage: one geometry, the scratch of a batch in flight (one stream at a time)."""
 
     def __init__(self, width, height, max_images=1, device="cuda:0"):
-        L = _bind()
         self.width, self.height, self.max_images = width, height, max_images
-        self.device = torch.device(device)
-        self._h = C.c_void_p()
-        _native.check(L.ifhip_gif_enc_stage_create(C.byref(self._h), width, height, max_images))
-        self.max_file_bytes = int(L.ifhip_gif_enc_stage_max_file_bytes(self._h))
+        self._create(_bind(), "ifhip_gif_enc_stage", device, width, height, max_images)
 
     def encode_device(self, frames: Bitmap, repeat=-1, delay=0, needs_user_input=False, file_pitch=None, taps=False):
         """frames: n BGRA frames of the stage's geometry.  Returns (files [n, file_pitch] uint8, lengths [n] int32, status [n]
         int32, palettes [n, 1028] uint8 or None, indices [n, h, w] uint8 or None), all cuda tensors; nothing is synchronised."""
-        L = _bind()
         n = frames.n
-        if file_pitch is None:
-            file_pitch = (self.max_file_bytes + 15) // 16 * 16
-        files = torch.empty((n, file_pitch), dtype=torch.uint8, device=self.device)
-        lengths = torch.zeros(n, dtype=torch.int32, device=self.device)
-        status = torch.zeros(n, dtype=torch.int32, device=self.device)
         palettes = torch.zeros((n, PALETTE_TAP), dtype=torch.uint8, device=self.device) if taps else None
         indices = torch.zeros((n, self.height, self.width), dtype=torch.uint8, device=self.device) if taps else None
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            _native.check(L.ifhip_gif_encode_batch_device(self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride, 1 if frames.alpha_meaningful else 0,
-                                                          n, repeat, delay, 1 if needs_user_input else 0, files.data_ptr(), file_pitch, lengths.data_ptr(),
-                                                          status.data_ptr(), palettes.data_ptr() if taps else None, indices.data_ptr() if taps else None,
-                                                          C.c_void_p(stream)))
+        files, lengths, status = self._batch(n, lambda d_files, pitch, d_lengths, d_status: (
+            _bind().ifhip_gif_encode_batch_device, self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride, 1 if frames.alpha_meaningful else 0, n,
+            repeat, delay, 1 if needs_user_input else 0, d_files, pitch, d_lengths, d_status, palettes.data_ptr() if taps else None,
+            indices.data_ptr() if taps else None), file_pitch)
         return files, lengths, status, palettes, indices
 
     def encode(self, frames: Bitmap, repeat=-1, delay=0, needs_user_input=False, file_pitch=None, taps=False):
         """The n files as bytes (None for a file that did not fit file_pitch), the status words and, with taps, per image the
         palette [count, 4] RGBA in file order and the indices [h, w]."""
         files, lengths, status, palettes, indices = self.encode_device(frames, repeat, delay, needs_user_input, file_pitch, taps)
-        lengths, status = lengths.cpu().numpy(), status.cpu().numpy()
-        host = files[:, :max(int(lengths.max()), 1)].cpu().numpy()
-        out = [host[i, :int(k)].tobytes() if k else None for i, k in enumerate(lengths)]
+        out, words = files_as_bytes(files, lengths, status)
         if not taps:
-            return out, [int(s) for s in status]
-        pal, idx = palettes.cpu().numpy(), indices.cpu().numpy()
-        pals = [pal[i, :1024].reshape(256, 4)[:int(pal[i, 1024:].view(np.uint32)[0])].copy() for i in range(frames.n)]
-        return out, [int(s) for s in status], pals, [idx[i] for i in range(frames.n)]
+            return out, words
+        idx = indices.cpu().numpy()
+        return out, words, palettes_from_taps(palettes), [idx[i] for i in range(frames.n)]
 
     def max_animation_bytes(self, n_frames):
         n = C.c_size_t(0)
@@ -88,7 +73,6 @@ class GifEncodeStage:
     def encode_animation_device(self, frames: Bitmap, delays, user_input, repeat=-1, capacity=None):
         """frames: n BGRA frames of the stage's geometry, n beyond max_images runs the stage in chunks.  Returns (file
         [capacity] uint8, length [1] int32, status [1] int32), cuda tensors; nothing is synchronised."""
-        L = _bind()
         n = frames.n
         if capacity is None:
             capacity = self.max_animation_bytes(n)
@@ -97,10 +81,8 @@ class GifEncodeStage:
         status = torch.zeros(1, dtype=torch.int32, device=self.device)
         d = (C.c_uint32 * n)(*[int(v) for v in delays])
         u = (C.c_uint8 * n)(*[1 if v else 0 for v in user_input])
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            _native.check(L.ifhip_gif_encode_animation_device(self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride, 1 if frames.alpha_meaningful else 0,
-                                                              n, repeat, d, u, file.data_ptr(), capacity, length.data_ptr(), status.data_ptr(), C.c_void_p(stream)))
+        self._on_stream(_bind().ifhip_gif_encode_animation_device, self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride,
+                        1 if frames.alpha_meaningful else 0, n, repeat, d, u, file.data_ptr(), capacity, length.data_ptr(), status.data_ptr())
         return file, length, status
 
     def encode_animation(self, bitmap_batch: Bitmap, delays, user_input, repeat=-1, capacity=None, with_status=False):
@@ -113,15 +95,6 @@ class GifEncodeStage:
         if word or data is None:
             raise RuntimeError(f"device GIF coder dropped the animation: status {word}")
         return data
-
-    def __del__(self):
-        try:
-            if self._h:
-                torch.cuda.synchronize(self.device)
-                _bind().ifhip_gif_enc_stage_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
 
 
 def encode_gif(bitmap: Bitmap, repeat=-1, delay=0, needs_user_input=False):
@@ -136,12 +109,5 @@ def encode_gif(bitmap: Bitmap, repeat=-1, delay=0, needs_user_input=False):
 def encode_gif_host(bgra, width, height, stride, alpha_meaningful=True, repeat=-1, delay=0, needs_user_input=False):
     """Host-buffer drop-in (numpy): BGRA rows -> the file's bytes."""
     L = _bind()
-    src = np.ascontiguousarray(bgra, np.uint8)
-    n = C.c_size_t(0)
-    h = C.c_void_p()
-    _native.check(L.ifhip_gif_enc_stage_create(C.byref(h), width, height, 1))   # (geometry only: for the bound)
-    out = np.empty(L.ifhip_gif_enc_stage_max_file_bytes(h), np.uint8)
-    L.ifhip_gif_enc_stage_destroy(h)
-    _native.check(L.ifhip_gif_encode(src.ctypes.data, width, height, stride, 1 if alpha_meaningful else 0, repeat, delay, 1 if needs_user_input else 0,
-                                     out.ctypes.data, out.size, C.byref(n)))
-    return out[:n.value].tobytes()
+    return encode_host(L, "ifhip_gif_enc_stage", (width, height, 1), L.ifhip_gif_encode, bgra, width, height, stride,
+                       (1 if alpha_meaningful else 0, repeat, delay, 1 if needs_user_input else 0))

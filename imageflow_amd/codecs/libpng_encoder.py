@@ -4,11 +4,9 @@ BGRX frames that stay in HBM -> complete PNG files in HBM -- row filters with li
 and their CRCs.  For tests and tools; the job path is the `libpng` preset of `encode` (csrc/abi_shim.cpp)."""
 import ctypes as C
 
-import numpy as np
-import torch
-
 from .. import _native
 from ..graphics.bitmaps import Bitmap
+from ._file_encoder import FileEncodeStage, encode_host, files_as_bytes
 
 PNG_RGB, PNG_RGBA = 2, 6                # include/imageflow_hip.h IFHIP_PNG_*
 PNG_FILE_OVERFLOW = 1
@@ -31,51 +29,23 @@ def _bind():
     return L
 
 
-class PngEncodeStage:
+class PngEncodeStage(FileEncodeStage):
     """ifhip_png_enc_stage: one geometry and colour type, the scratch of a batch in flight (one stream at a time)."""
 
     def __init__(self, width, height, color_type=PNG_RGBA, max_images=1, device="cuda:0"):
-        L = _bind()
         self.width, self.height, self.color_type, self.max_images = width, height, color_type, max_images
-        self.device = torch.device(device)
-        self._h = C.c_void_p()
-        _native.check(L.ifhip_png_enc_stage_create(C.byref(self._h), width, height, color_type, max_images))
-        self.max_file_bytes = int(L.ifhip_png_enc_stage_max_file_bytes(self._h))
+        self._create(_bind(), "ifhip_png_enc_stage", device, width, height, color_type, max_images)
 
     def encode_device(self, frames: Bitmap, zlib_level=DEFAULT_ZLIB_LEVEL, file_pitch=None, files=None, lengths=None, status=None):
         """frames: n BGRA frames of the stage's geometry.  Returns (files [n, file_pitch] uint8, lengths [n] int32, status [n]
         int32), all cuda tensors; nothing is synchronised."""
-        L = _bind()
-        n = frames.n
-        if file_pitch is None:
-            file_pitch = files.shape[1] if files is not None else (self.max_file_bytes + 15) // 16 * 16
-        if files is None:
-            files = torch.empty((n, file_pitch), dtype=torch.uint8, device=self.device)
-        if lengths is None:
-            lengths = torch.zeros(n, dtype=torch.int32, device=self.device)
-        if status is None:
-            status = torch.zeros(n, dtype=torch.int32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            _native.check(L.ifhip_png_encode_batch_device(self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride, n, int(zlib_level),
-                                                          files.data_ptr(), file_pitch, lengths.data_ptr(), status.data_ptr(), C.c_void_p(stream)))
-        return files, lengths, status
+        return self._batch(frames.n, lambda d_files, pitch, d_lengths, d_status: (
+            _bind().ifhip_png_encode_batch_device, self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride, frames.n, int(zlib_level), d_files, pitch,
+            d_lengths, d_status), file_pitch, files, lengths, status)
 
     def encode(self, frames: Bitmap, zlib_level=DEFAULT_ZLIB_LEVEL, file_pitch=None):
         """The n files as bytes (None for a file that did not fit file_pitch) and the status words."""
-        files, lengths, status = self.encode_device(frames, zlib_level, file_pitch)
-        lengths, status = lengths.cpu().numpy(), status.cpu().numpy()
-        host = files[:, :max(int(lengths.max()), 1)].cpu().numpy()
-        return [host[i, :int(k)].tobytes() if k else None for i, k in enumerate(lengths)], [int(s) for s in status]
-
-    def __del__(self):
-        try:
-            if self._h:
-                torch.cuda.synchronize(self.device)
-                _bind().ifhip_png_enc_stage_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
+        return files_as_bytes(*self.encode_device(frames, zlib_level, file_pitch))
 
 
 def color_type_for(alpha_meaningful, depth=None):
@@ -107,8 +77,4 @@ def encode_png(bitmap: Bitmap, depth=None, zlib_compression=None, matte=None):
 def encode_png_host(bgra, width, height, stride, color_type=PNG_RGBA, zlib_level=DEFAULT_ZLIB_LEVEL):
     """Host-buffer drop-in (numpy): BGRA rows -> the file's bytes."""
     L = _bind()
-    src = np.ascontiguousarray(bgra, np.uint8)
-    n = C.c_size_t(0)
-    out = np.empty(height * (1 + 4 * width) + 5 * (height * (1 + 4 * width) // 32768 + 1) + 256, np.uint8)
-    _native.check(L.ifhip_png_encode(src.ctypes.data, width, height, stride, color_type, int(zlib_level), out.ctypes.data, out.size, C.byref(n)))
-    return out[:n.value].tobytes()
+    return encode_host(L, "ifhip_png_enc_stage", (width, height, color_type, 1), L.ifhip_png_encode, bgra, width, height, stride, (color_type, int(zlib_level)))

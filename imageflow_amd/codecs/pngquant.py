@@ -6,12 +6,12 @@ chunks and their CRCs.  A frame whose quantisation misses minimum_quality is wri
 `encode` (csrc/abi_shim.cpp)."""
 import ctypes as C
 
-import numpy as np
 import torch
 
 from .. import _native
 from ..graphics.bitmaps import Bitmap
 from . import libpng_encoder
+from ._file_encoder import FileEncodeStage, encode_host, files_as_bytes, palettes_from_taps
 
 PNG_FILE_OVERFLOW, PNG_QUALITY_TOO_LOW = 1, 2   # include/imageflow_hip.h IFHIP_PNG_*
 MAX_COLORS = 256
@@ -42,68 +42,43 @@ def _opt(v):
     return -1 if v is None else int(v)
 
 
-class PngQuantStage:
+class PngQuantStage(FileEncodeStage):
     """ifhip_png_quant_stage: one geometry, the scratch of a batch in flight (one stream at a time)."""
 
     def __init__(self, width, height, max_images=1, device="cuda:0"):
-        L = _bind()
         self.width, self.height, self.max_images = width, height, max_images
-        self.device = torch.device(device)
-        self._h = C.c_void_p()
-        _native.check(L.ifhip_png_quant_stage_create(C.byref(self._h), width, height, max_images))
-        self.max_file_bytes = int(L.ifhip_png_quant_stage_max_file_bytes(self._h))
+        self._create(_bind(), "ifhip_png_quant_stage", device, width, height, max_images)
 
     def quantize_device(self, frames: Bitmap, quality=None, minimum_quality=None, speed=None, max_colors=MAX_COLORS, dither=True,
                         zlib_level=DEFAULT_ZLIB_LEVEL, alpha_meaningful=None, file_pitch=None, taps=False):
         """frames: n BGRA frames of the stage's geometry.  Returns a dict of cuda tensors: files [n, file_pitch] uint8, lengths
         [n] int32, status [n] int32, and with taps palettes [n, 1028] uint8, indices [n, h, w] uint8, mse [n] float64.
         Nothing is synchronised."""
-        L = _bind()
         n = frames.n
         if alpha_meaningful is None:
             alpha_meaningful = frames.alpha_meaningful
-        if file_pitch is None:
-            file_pitch = (self.max_file_bytes + 15) // 16 * 16
-        out = {"files": torch.empty((n, file_pitch), dtype=torch.uint8, device=self.device),
-               "lengths": torch.zeros(n, dtype=torch.int32, device=self.device),
-               "status": torch.zeros(n, dtype=torch.int32, device=self.device)}
+        out = {}
         if taps:
             out["palettes"] = torch.zeros((n, PALETTE_TAP), dtype=torch.uint8, device=self.device)
             out["indices"] = torch.zeros((n, self.height, self.width), dtype=torch.uint8, device=self.device)
             out["mse"] = torch.zeros(n, dtype=torch.float64, device=self.device)
         ptr = lambda k: out[k].data_ptr() if k in out else None  # noqa: E731
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            _native.check(L.ifhip_png_quantize_batch_device(self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride, 1 if alpha_meaningful else 0,
-                                                            n, _opt(quality), _opt(minimum_quality), _opt(speed), int(max_colors), 1 if dither else 0,
-                                                            int(zlib_level), out["files"].data_ptr(), file_pitch, out["lengths"].data_ptr(),
-                                                            out["status"].data_ptr(), ptr("palettes"), ptr("indices"), ptr("mse"), C.c_void_p(stream)))
+        out["files"], out["lengths"], out["status"] = self._batch(n, lambda d_files, pitch, d_lengths, d_status: (
+            _bind().ifhip_png_quantize_batch_device, self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride, 1 if alpha_meaningful else 0, n,
+            _opt(quality), _opt(minimum_quality), _opt(speed), int(max_colors), 1 if dither else 0, int(zlib_level), d_files, pitch, d_lengths, d_status,
+            ptr("palettes"), ptr("indices"), ptr("mse")), file_pitch)
         return out
 
     def quantize(self, frames: Bitmap, **kw):
         """The n files as bytes (None for an image without one), the status words, and with taps=True a list of
         (palette [count, 4] RGBA, indices [h, w], mse) per image."""
         out = self.quantize_device(frames, **kw)
-        lengths, status = out["lengths"].cpu().numpy(), out["status"].cpu().numpy()
-        host = out["files"][:, :max(int(lengths.max()), 1)].cpu().numpy()
-        files = [host[i, :int(k)].tobytes() if k else None for i, k in enumerate(lengths)]
+        files, status = files_as_bytes(out["files"], out["lengths"], out["status"])
         taps = None
         if "palettes" in out:
-            pal, idx, mse = out["palettes"].cpu().numpy(), out["indices"].cpu().numpy(), out["mse"].cpu().numpy()
-            taps = []
-            for i in range(frames.n):
-                count = int(pal[i, 4 * MAX_COLORS:].view(np.uint32)[0])
-                taps.append((pal[i, :4 * MAX_COLORS].reshape(MAX_COLORS, 4)[:count].copy(), idx[i], float(mse[i])))
-        return files, [int(s) for s in status], taps
-
-    def __del__(self):
-        try:
-            if self._h:
-                torch.cuda.synchronize(self.device)
-                _bind().ifhip_png_quant_stage_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
+            idx, mse = out["indices"].cpu().numpy(), out["mse"].cpu().numpy()
+            taps = [(pal, idx[i], float(mse[i])) for i, pal in enumerate(palettes_from_taps(out["palettes"]))]
+        return files, status, taps
 
 
 def encode_pngquant(bitmap: Bitmap, quality=None, minimum_quality=None, speed=None, maximum_deflate=None):
@@ -127,9 +102,7 @@ def encode_pngquant(bitmap: Bitmap, quality=None, minimum_quality=None, speed=No
 def quantize_png_host(bgra, width, height, stride, alpha_meaningful=True, quality=None, minimum_quality=None, speed=None):
     """Host-buffer form (numpy): BGRA rows -> (the file's bytes or None, the status word)."""
     L = _bind()
-    src = np.ascontiguousarray(bgra, np.uint8)
-    n, status = C.c_size_t(0), C.c_uint32(0)
-    out = np.empty(height * (1 + width) + 5 * (height * (1 + width) // 32768 + 1) + 2048, np.uint8)
-    _native.check(L.ifhip_png_quantize(src.ctypes.data, width, height, stride, 1 if alpha_meaningful else 0, _opt(quality), _opt(minimum_quality),
-                                       _opt(speed), out.ctypes.data, out.size, C.byref(n), C.byref(status)))
-    return (out[:n.value].tobytes() if n.value else None), int(status.value)
+    status = C.c_uint32(0)
+    data = encode_host(L, "ifhip_png_quant_stage", (width, height, 1), L.ifhip_png_quantize, bgra, width, height, stride,
+                       (1 if alpha_meaningful else 0, _opt(quality), _opt(minimum_quality), _opt(speed)), (C.byref(status),))
+    return (data or None), int(status.value)

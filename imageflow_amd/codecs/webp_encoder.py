@@ -4,11 +4,9 @@ libimageflow_hip.so (csrc/webp_encode.hip): BGRA / BGRX frames that stay in HBM 
 HBM.  For tests and tools; the job path is the `webplossless` preset of `encode` (csrc/abi_shim.cpp)."""
 import ctypes as C
 
-import numpy as np
-import torch
-
 from .. import _native
 from ..graphics.bitmaps import Bitmap
+from ._file_encoder import FileEncodeStage, encode_host, files_as_bytes
 
 WEBP_FILE_OVERFLOW = 1                  # include/imageflow_hip.h IFHIP_WEBP_FILE_OVERFLOW
 MAX_DIMENSION = 16384                   # 14 bits of width - 1 and height - 1
@@ -30,51 +28,23 @@ def _bind():
     return L
 
 
-class WebpEncodeStage:
+class WebpEncodeStage(FileEncodeStage):
     """ifhip_webp_enc_stage: one geometry and alpha mode, the scratch of a batch in flight (one stream at a time)."""
 
     def __init__(self, width, height, alpha_meaningful=True, max_images=1, device="cuda:0"):
-        L = _bind()
         self.width, self.height, self.alpha_meaningful, self.max_images = width, height, bool(alpha_meaningful), max_images
-        self.device = torch.device(device)
-        self._h = C.c_void_p()
-        _native.check(L.ifhip_webp_enc_stage_create(C.byref(self._h), width, height, 1 if alpha_meaningful else 0, max_images))
-        self.max_file_bytes = int(L.ifhip_webp_enc_stage_max_file_bytes(self._h))
+        self._create(_bind(), "ifhip_webp_enc_stage", device, width, height, 1 if alpha_meaningful else 0, max_images)
 
     def encode_device(self, frames: Bitmap, file_pitch=None, files=None, lengths=None, status=None):
         """frames: n BGRA frames of the stage's geometry.  Returns (files [n, file_pitch] uint8, lengths [n] int32, status [n]
         int32), all cuda tensors; nothing is synchronised."""
-        L = _bind()
-        n = frames.n
-        if file_pitch is None:
-            file_pitch = files.shape[1] if files is not None else (self.max_file_bytes + 15) // 16 * 16
-        if files is None:
-            files = torch.empty((n, file_pitch), dtype=torch.uint8, device=self.device)
-        if lengths is None:
-            lengths = torch.zeros(n, dtype=torch.int32, device=self.device)
-        if status is None:
-            status = torch.zeros(n, dtype=torch.int32, device=self.device)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        with torch.cuda.device(self.device):
-            _native.check(L.ifhip_webp_encode_batch_device(self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride, n,
-                                                           files.data_ptr(), file_pitch, lengths.data_ptr(), status.data_ptr(), C.c_void_p(stream)))
-        return files, lengths, status
+        return self._batch(frames.n, lambda d_files, pitch, d_lengths, d_status: (
+            _bind().ifhip_webp_encode_batch_device, self._h, frames.data.data_ptr(), frames.image_bytes, frames.stride, frames.n, d_files, pitch, d_lengths,
+            d_status), file_pitch, files, lengths, status)
 
     def encode(self, frames: Bitmap, file_pitch=None):
         """The n files as bytes (None for a file that did not fit file_pitch) and the status words."""
-        files, lengths, status = self.encode_device(frames, file_pitch)
-        lengths, status = lengths.cpu().numpy(), status.cpu().numpy()
-        host = files[:, :max(int(lengths.max()), 1)].cpu().numpy()
-        return [host[i, :int(k)].tobytes() if k else None for i, k in enumerate(lengths)], [int(s) for s in status]
-
-    def __del__(self):
-        try:
-            if self._h:
-                torch.cuda.synchronize(self.device)
-                _bind().ifhip_webp_enc_stage_destroy(self._h)
-                self._h = C.c_void_p()
-        except Exception:
-            pass
+        return files_as_bytes(*self.encode_device(frames, file_pitch))
 
 
 def encode_webp_lossless(bitmap: Bitmap):
@@ -90,11 +60,5 @@ def encode_webp_lossless(bitmap: Bitmap):
 def encode_webp_host(bgra, width, height, stride, alpha_meaningful=True):
     """Host-buffer drop-in (numpy): BGRA rows -> the file's bytes."""
     L = _bind()
-    src = np.ascontiguousarray(bgra, np.uint8)
-    n = C.c_size_t(0)
-    h = C.c_void_p()
-    _native.check(L.ifhip_webp_enc_stage_create(C.byref(h), width, height, 1 if alpha_meaningful else 0, 1))   # (geometry only: for the bound)
-    out = np.empty(L.ifhip_webp_enc_stage_max_file_bytes(h), np.uint8)
-    L.ifhip_webp_enc_stage_destroy(h)
-    _native.check(L.ifhip_webp_encode(src.ctypes.data, width, height, stride, 1 if alpha_meaningful else 0, out.ctypes.data, out.size, C.byref(n)))
-    return out[:n.value].tobytes()
+    alpha = 1 if alpha_meaningful else 0
+    return encode_host(L, "ifhip_webp_enc_stage", (width, height, alpha, 1), L.ifhip_webp_encode, bgra, width, height, stride, (alpha,))

@@ -1575,20 +1575,46 @@ struct Job {
         }
     };
 
-    // a truecolour PNG of the frame by the device coder (csrc/png_encode.hip): only the file's bytes leave the device
-    void write_png(const FramePtr& f, int color_type, int level, Io& o, int32_t io_id) {
-        ifhip_png_enc_stage* ps = nullptr;
-        check(ifhip_png_enc_stage_create(&ps, f->w, f->h, color_type, 1));
-        std::unique_ptr<ifhip_png_enc_stage, void (*)(ifhip_png_enc_stage*)> ps_guard(ps, [](ifhip_png_enc_stage* q) { quiesce(); ifhip_png_enc_stage_destroy(q); });
-        const size_t pitch = (ifhip_png_enc_stage_max_file_bytes(ps) + 15u) & ~static_cast<size_t>(15u);
+    // What a device coder's call in a job is named by: the label of its file's allocation, the coder in "dropped a file", the record.
+    struct CoderNames { const char *label, *coder, *mime, *ext; };
+    static constexpr CoderNames kPngNames{"hipMalloc(png file)", "PNG", "image/png", "png"}, kPalettePngNames{"hipMalloc(png file)", "palette PNG", "image/png", "png"},
+        kWebpNames{"hipMalloc(webp file)", "WebP", "image/webp", "webp"}, kGifNames{"hipMalloc(gif file)", "GIF", "image/gif", "gif"};
+
+    // Behind the stage: a file of `pitch` bytes, call(file) as the coder's one call on t_job_stream, and the file into `o`.
+    // Returns the status word: 0 with the file written, or `lets_through` (not 0), which the caller answers itself.
+    template <typename Call>
+    uint32_t fetch_coded_file(Io& o, size_t pitch, const CoderNames& names, uint32_t lets_through, Call call) {
         CodedFile file;
-        hip_check(file.alloc(pitch, pitch), "hipMalloc(png file)");
-        check(ifhip_png_encode_batch_device(ps, dev(f), f->bytes(), f->stride, 1, level, file.d, pitch, file.d_len, file.d_len + 1, t_job_stream));
+        hip_check(file.alloc(pitch, pitch), names.label);
+        check(call(file));
         poll_cancel();
         file.fetch(o);
-        if (file.status != 0 || file.len == 0) raise(kInternalError, "InternalError: the PNG coder dropped a file sized for its worst case (status %u)", file.status);
+        if (lets_through != 0 && file.status == lets_through) return file.status;
+        if (file.status != 0 || file.len == 0) raise(kInternalError, "InternalError: the %s coder dropped a file sized for its worst case (status %u)", names.coder, file.status);
         o.written = true;
-        encodes.push_back({io_id, f->w, f->h, "image/png", "png"});
+        return 0;
+    }
+    // One frame through a device file coder: create(&stage) for one image, a file of the stage's bound (rounded up to 16),
+    // batch(stage, d_file, pitch, d_len) (d_len + 1: the status word), the file into `o` and its record.
+    template <typename Stage, typename Create, typename Batch>
+    uint32_t write_coded_frame(const FramePtr& f, Io& o, int32_t io_id, const CoderNames& names, uint32_t lets_through, Create create, void (*destroy)(Stage*),
+                               size_t (*max_file_bytes)(const Stage*), Batch batch) {
+        Stage* stage = nullptr;
+        check(create(&stage));
+        struct Guard { Stage* s; void (*destroy)(Stage*); ~Guard() { quiesce(); destroy(s); } } guard{stage, destroy};
+        const size_t pitch = (max_file_bytes(stage) + 15u) & ~static_cast<size_t>(15u);
+        const uint32_t status = fetch_coded_file(o, pitch, names, lets_through, [&](CodedFile& file) { return batch(stage, file.d, pitch, file.d_len); });
+        if (status == 0) encodes.push_back({io_id, f->w, f->h, names.mime, names.ext});
+        return status;
+    }
+
+    // a truecolour PNG of the frame by the device coder (csrc/png_encode.hip): only the file's bytes leave the device
+    void write_png(const FramePtr& f, int color_type, int level, Io& o, int32_t io_id) {
+        write_coded_frame(
+            f, o, io_id, kPngNames, 0u, [&](ifhip_png_enc_stage** s) { return ifhip_png_enc_stage_create(s, f->w, f->h, color_type, 1); }, ifhip_png_enc_stage_destroy,
+            ifhip_png_enc_stage_max_file_bytes, [&](ifhip_png_enc_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
+                return ifhip_png_encode_batch_device(s, dev(f), f->bytes(), f->stride, 1, level, d_file, pitch, d_len, d_len + 1, t_job_stream);
+            });
     }
 
     // encode: EncoderPreset::LibjpegTurbo is written as a real JPEG (codecs/mozjpeg.rs:78-160, create_classic :62-77):
@@ -1764,42 +1790,25 @@ struct Job {
                 maximum_deflate = z->b;
             }
             const int level = maximum_deflate ? 9 : 6;                                    // lode.rs:162-195
-            ifhip_png_quant_stage* qs = nullptr;
-            check(ifhip_png_quant_stage_create(&qs, f->w, f->h, 1));
-            std::unique_ptr<ifhip_png_quant_stage, void (*)(ifhip_png_quant_stage*)> qs_guard(qs, [](ifhip_png_quant_stage* q) { quiesce(); ifhip_png_quant_stage_destroy(q); });
-            const size_t pitch = (ifhip_png_quant_stage_max_file_bytes(qs) + 15u) & ~static_cast<size_t>(15u);
-            CodedFile file;
-            hip_check(file.alloc(pitch, pitch), "hipMalloc(png file)");
-            check(ifhip_png_quantize_batch_device(qs, dev(f), f->bytes(), f->stride, f->alpha ? 1 : 0, 1, quality, min_quality, speed, 256, 1, level,
-                                                  file.d, pitch, file.d_len, file.d_len + 1, nullptr, nullptr, nullptr, t_job_stream));
-            poll_cancel();
-            file.fetch(o);
-            if (file.status == IFHIP_PNG_QUALITY_TOO_LOW) {
-                // pngquant.rs:105-139: below minimum_quality the frame is written losslessly, RGBA or RGB by its alpha
-                write_png(f, f->alpha ? IFHIP_PNG_RGBA : IFHIP_PNG_RGB, level, o, io_id);
-                return;
-            }
-            if (file.status != 0 || file.len == 0) raise(kInternalError, "InternalError: the palette PNG coder dropped a file sized for its worst case (status %u)", file.status);
-            o.written = true;
-            encodes.push_back({io_id, f->w, f->h, "image/png", "png"});
+            const uint32_t status = write_coded_frame(
+                f, o, io_id, kPalettePngNames, IFHIP_PNG_QUALITY_TOO_LOW, [&](ifhip_png_quant_stage** s) { return ifhip_png_quant_stage_create(s, f->w, f->h, 1); },
+                ifhip_png_quant_stage_destroy, ifhip_png_quant_stage_max_file_bytes, [&](ifhip_png_quant_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
+                    return ifhip_png_quantize_batch_device(s, dev(f), f->bytes(), f->stride, f->alpha ? 1 : 0, 1, quality, min_quality, speed, 256, 1, level, d_file, pitch,
+                                                           d_len, d_len + 1, nullptr, nullptr, nullptr, t_job_stream);
+                });
+            // pngquant.rs:105-139: below minimum_quality the frame is written losslessly, RGBA or RGB by its alpha
+            if (status == IFHIP_PNG_QUALITY_TOO_LOW) write_png(f, f->alpha ? IFHIP_PNG_RGBA : IFHIP_PNG_RGB, level, o, io_id);
             return;
         }
         if (coder == IFHIP_ENCODE_CODER_WEBP_LOSSLESS) {
             // EncoderPreset::WebPLossless (imageflow_types/src/lib.rs:773, codecs/auto.rs:282-319) -> WebPEncoder::write_frame
             // (codecs/webp.rs:281-345: WebPEncodeLosslessBGRA, or ...BGR when the frame's alpha is not meaningful); no matte
             // (the reference passes None).  The file is coded on the device (csrc/webp_encode.hip), only its bytes leave it.
-            ifhip_webp_enc_stage* ws = nullptr;
-            check(ifhip_webp_enc_stage_create(&ws, f->w, f->h, f->alpha ? 1 : 0, 1));
-            std::unique_ptr<ifhip_webp_enc_stage, void (*)(ifhip_webp_enc_stage*)> ws_guard(ws, [](ifhip_webp_enc_stage* q) { quiesce(); ifhip_webp_enc_stage_destroy(q); });
-            const size_t pitch = (ifhip_webp_enc_stage_max_file_bytes(ws) + 15u) & ~static_cast<size_t>(15u);
-            CodedFile file;
-            hip_check(file.alloc(pitch, pitch), "hipMalloc(webp file)");
-            check(ifhip_webp_encode_batch_device(ws, dev(f), f->bytes(), f->stride, 1, file.d, pitch, file.d_len, file.d_len + 1, t_job_stream));
-            poll_cancel();
-            file.fetch(o);
-            if (file.status != 0 || file.len == 0) raise(kInternalError, "InternalError: the WebP coder dropped a file sized for its worst case (status %u)", file.status);
-            o.written = true;
-            encodes.push_back({io_id, f->w, f->h, "image/webp", "webp"});
+            write_coded_frame(
+                f, o, io_id, kWebpNames, 0u, [&](ifhip_webp_enc_stage** s) { return ifhip_webp_enc_stage_create(s, f->w, f->h, f->alpha ? 1 : 0, 1); },
+                ifhip_webp_enc_stage_destroy, ifhip_webp_enc_stage_max_file_bytes, [&](ifhip_webp_enc_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
+                    return ifhip_webp_encode_batch_device(s, dev(f), f->bytes(), f->stride, 1, d_file, pitch, d_len, d_len + 1, t_job_stream);
+                });
             return;
         }
         if (preset && preset->t == JVal::Str && preset->s == "gif" && c->gif_encoder.load(std::memory_order_relaxed)) {
@@ -1807,19 +1816,12 @@ struct Job {
             // the alpha rule, the palette and the LZW stream on the device (csrc/gif_encode.hip), only the file leaves it.  The
             // frame itself is left as it is (the rule is applied where the pixels are read); a side above 65535 is size_16()'s
             // InvalidArgument.  A GIF decoder of the job hands on its repeat count and its last frame's delay and user-input flag.
-            ifhip_gif_enc_stage* gs = nullptr;
-            check(ifhip_gif_enc_stage_create(&gs, f->w, f->h, 1));
-            std::unique_ptr<ifhip_gif_enc_stage, void (*)(ifhip_gif_enc_stage*)> gs_guard(gs, [](ifhip_gif_enc_stage* q) { quiesce(); ifhip_gif_enc_stage_destroy(q); });
-            const size_t pitch = (ifhip_gif_enc_stage_max_file_bytes(gs) + 15u) & ~static_cast<size_t>(15u);
-            CodedFile file;
-            hip_check(file.alloc(pitch, pitch), "hipMalloc(gif file)");
-            check(ifhip_gif_encode_batch_device(gs, dev(f), f->bytes(), f->stride, f->alpha ? 1 : 0, 1, gif_source.seen ? gif_source.repeat : -1, gif_source.delay,
-                                                gif_source.user_input ? 1 : 0, file.d, pitch, file.d_len, file.d_len + 1, nullptr, nullptr, t_job_stream));
-            poll_cancel();
-            file.fetch(o);
-            if (file.status != 0 || file.len == 0) raise(kInternalError, "InternalError: the GIF coder dropped a file sized for its worst case (status %u)", file.status);
-            o.written = true;
-            encodes.push_back({io_id, f->w, f->h, "image/gif", "gif"});
+            write_coded_frame(
+                f, o, io_id, kGifNames, 0u, [&](ifhip_gif_enc_stage** s) { return ifhip_gif_enc_stage_create(s, f->w, f->h, 1); }, ifhip_gif_enc_stage_destroy,
+                ifhip_gif_enc_stage_max_file_bytes, [&](ifhip_gif_enc_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
+                    return ifhip_gif_encode_batch_device(s, dev(f), f->bytes(), f->stride, f->alpha ? 1 : 0, 1, gif_source.seen ? gif_source.repeat : -1, gif_source.delay,
+                                                         gif_source.user_input ? 1 : 0, d_file, pitch, d_len, d_len + 1, nullptr, nullptr, t_job_stream);
+                });
             return;
         }
         o.owned.assign(kRawHeader + f->bytes(), 0);
@@ -2381,15 +2383,11 @@ struct Job {
             size_t capacity = 0;
             check(ifhip_gif_enc_stage_max_animation_bytes(a.stage, anim.n, &capacity));
             const size_t pitch = (capacity + 15u) & ~static_cast<size_t>(15u);
-            CodedFile file;
-            hip_check(file.alloc(pitch, pitch), "hipMalloc(gif file)");
             const size_t image_bytes = static_cast<size_t>(a.h) * a.stride;
-            check(ifhip_gif_encode_animation_device(a.stage, a.d, image_bytes, a.stride, a.alpha ? 1 : 0, anim.n, anim.repeat, anim.delays.data(), anim.user_input.data(), file.d,
-                                                    capacity, file.d_len, file.d_len + 1, t_job_stream));
-            poll_cancel();
-            file.fetch(o);
-            if (file.status != 0 || file.len == 0) raise(kInternalError, "InternalError: the GIF coder dropped a file sized for its worst case (status %u)", file.status);
-            o.written = true;
+            fetch_coded_file(o, pitch, kGifNames, 0u, [&](CodedFile& file) {
+                return ifhip_gif_encode_animation_device(a.stage, a.d, image_bytes, a.stride, a.alpha ? 1 : 0, anim.n, anim.repeat, anim.delays.data(), anim.user_input.data(), file.d,
+                                                         capacity, file.d_len, file.d_len + 1, t_job_stream);
+            });
         }
     }
     // a job: once, or -- where the animation path applies -- once per frame of the animated sources

@@ -28,8 +28,8 @@
 
 #include "block_scan.hpp"
 #include "decode_handoff.hpp"      // StagedBlock
+#include "encode_handoff.hpp"
 #include "gif_encode_core.hpp"
-#include "hip_entry.hpp"
 #include "png_quantize.hpp"
 #include "stage_scratch.hpp"
 
@@ -217,11 +217,10 @@ struct ifhip_gif_enc_stage {
     size_t index_pitch = 0;
     uint8_t* d_indices = nullptr;
     uint32_t *d_slots = nullptr, *d_seg_bits = nullptr, *d_stream = nullptr;
-    uint32_t *d_tables = nullptr, *d_ekey = nullptr, *d_ew = nullptr, *d_result = nullptr;   // the quantiser's (the state words lie behind the tables)
-    uint64_t* d_edmin = nullptr;
+    QuantScratch quant;
     uint32_t* d_anim = nullptr;                          // the animation's running words, offsets and lengths (GifAnimArgs)
     uint8_t* d_anim_heads = nullptr;
-    StageScratch blocks{&d_indices, &d_slots, &d_seg_bits, &d_stream, &d_tables, &d_ekey, &d_ew, &d_edmin, &d_result, &d_anim, &d_anim_heads};
+    StageScratch blocks{&d_indices, &d_slots, &d_seg_bits, &d_stream, &quant.d_tables, &quant.d_ekey, &quant.d_ew, &quant.d_edmin, &quant.d_result, &d_anim, &d_anim_heads};
 };
 
 namespace {
@@ -232,11 +231,7 @@ int gif_enc_stage_allocate(ifhip_gif_enc_stage* s) {
         HIP_TRY(DEV_MALLOC(&s->d_slots, n * s->n_seg * gifenc_slot_words() * sizeof(uint32_t)));
         HIP_TRY(DEV_MALLOC(&s->d_seg_bits, n * (s->n_seg + 1u) * sizeof(uint32_t)));
         HIP_TRY(DEV_MALLOC(&s->d_stream, n * s->stream_words * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&s->d_tables, (quant_table_words(n) + n * kPqStateWords) * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&s->d_ekey, n * kPqMaxEntries * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&s->d_ew, n * kPqMaxEntries * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&s->d_edmin, n * kPqMaxEntries * sizeof(uint64_t)));
-        HIP_TRY(DEV_MALLOC(&s->d_result, n * kPqResultWords * sizeof(uint32_t)));
+        if (int rc = s->quant.allocate(n)) return rc;
         HIP_TRY(DEV_MALLOC(&s->d_anim, (8u + 3u * n + 1u) * sizeof(uint32_t)));
         HIP_TRY(DEV_MALLOC(&s->d_anim_heads, kGifEncScreenPitch + n * kGifEncFrameHeadPitch));
         return IFHIP_OK;
@@ -245,15 +240,9 @@ int gif_enc_stage_allocate(ifhip_gif_enc_stage* s) {
 // the arguments of one batch of `n_images` frames through the stage (the caller adds where the files go)
 void gif_enc_args(ifhip_gif_enc_stage* stage, const uint8_t* d_images, size_t image_bytes, uint32_t stride, int alpha_meaningful, uint32_t n_images, int repeat,
                   QuantArgs* qp, GifEncArgs* gp) {
-    QuantArgs& q = *qp;
-    std::memset(&q, 0, sizeof q);
-    q.images = d_images; q.image_bytes = image_bytes; q.stride = stride; q.w = stage->width; q.h = stage->height; q.n_images = n_images;
-    q.alpha = alpha_meaningful ? 1u : 0u; q.max_colors = kPqMaxColors; q.key_rule = kPqKeyGif;
-    // the pngquant preset's defaults (codecs/pngquant.rs:50-57): target 100, minimum 0, speed 4
-    q.iterations = pq_speed_iterations(4u); q.max_entries = pq_speed_max_entries(4u);
-    q.bound_target = pq_quality_bound(100u); q.bound_min = pq_quality_bound(0u);
-    q.tables = stage->d_tables; q.state = stage->d_tables + quant_table_words(stage->max_images);
-    q.ekey = stage->d_ekey; q.ew = stage->d_ew; q.edmin = stage->d_edmin; q.result = stage->d_result;
+    // the pngquant preset's defaults (codecs/pngquant.rs:50-57): speed 4, target 100, minimum 0
+    stage->quant.fill(qp, d_images, image_bytes, stride, stage->width, stage->height, n_images, alpha_meaningful, kPqMaxColors, 4u, 100u, 0u);
+    qp->key_rule = kPqKeyGif;
     GifEncArgs& g = *gp;
     std::memset(&g, 0, sizeof g);
     g.n_seg = stage->n_seg; g.slot_words = gifenc_slot_words(); g.stream_words = stage->stream_words; g.index_pitch = stage->index_pitch;
@@ -303,11 +292,8 @@ size_t ifhip_gif_enc_stage_max_file_bytes(const ifhip_gif_enc_stage* stage) {
 int ifhip_gif_encode_batch_device(ifhip_gif_enc_stage* stage, const uint8_t* d_images, size_t image_bytes, uint32_t stride, int alpha_meaningful,
                                   uint32_t n_images, int repeat, uint32_t delay, int needs_user_input, uint8_t* d_files, size_t file_pitch,
                                   uint32_t* d_lengths, uint32_t* d_status, uint8_t* d_palettes, uint8_t* d_indices, void* hip_stream) {
-    if (!stage) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null stage");
-    if (n_images == 0) return IFHIP_OK;
-    if (n_images > stage->max_images) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: %u images exceed the stage capacity %u", n_images, stage->max_images);
-    if (int rc = check_frames(d_images, image_bytes, stage->width, stage->height, stride, "image")) return rc;
-    if (!d_files || !d_lengths) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
+    bool go = false;
+    if (int rc = open_encode_batch(stage, d_images, image_bytes, stride, n_images, d_files, d_lengths, &go); rc || !go) return rc;
     if (repeat < -1 || repeat > 65535) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: repeat is -1 (none) or 0..65535");
     if (delay > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: delay is 0..65535 hundredths of a second");
     if (file_pitch < kGifEncHeadMax + 8u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: file_pitch below %u bytes", kGifEncHeadMax + 8u);
@@ -390,21 +376,14 @@ int ifhip_gif_encode_animation_device(ifhip_gif_enc_stage* stage, const uint8_t*
 
 int ifhip_gif_encode(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int alpha_meaningful, int repeat, uint32_t delay,
                      int needs_user_input, uint8_t* out, size_t capacity, size_t* len) {
-    if (!len) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null length out-pointer");
-    *len = 0;
-    ifhip_gif_enc_stage* stage = nullptr;
-    if (int rc = ifhip_gif_enc_stage_create(&stage, width, height, 1)) return rc;
-    std::unique_ptr<ifhip_gif_enc_stage, void (*)(ifhip_gif_enc_stage*)> guard(stage, [](ifhip_gif_enc_stage* s) { (void)hipStreamSynchronize(nullptr); ifhip_gif_enc_stage_destroy(s); });
-    const size_t pitch = (ifhip_gif_enc_stage_max_file_bytes(stage) + 15u) & ~static_cast<size_t>(15u);
-    HostFrame f;
-    if (int rc = f.up(bgra, width, height, stride, pitch + 16u)) return rc;
-    uint32_t* d_len = reinterpret_cast<uint32_t*>(f.side_output() + pitch);
-    if (int rc = ifhip_gif_encode_batch_device(stage, f.d, f.image_bytes, stride, alpha_meaningful, 1, repeat, delay, needs_user_input, f.side_output(), pitch,
-                                               d_len, d_len + 1, nullptr, nullptr, nullptr)) return rc;
-    uint32_t word = 0;
-    if (int rc = f.down_file(pitch, out, capacity, len, &word)) return rc;
-    if (word || !*len) return fail(IFHIP_INVALID_STATE, "InvalidState: the file did not fit its worst-case size (status %u)", word);
-    return IFHIP_OK;
+    uint32_t status = 0;
+    if (int rc = encode_host_frame(
+            bgra, width, height, stride, out, capacity, len, &status, [&](ifhip_gif_enc_stage** s) { return ifhip_gif_enc_stage_create(s, width, height, 1); },
+            ifhip_gif_enc_stage_destroy, ifhip_gif_enc_stage_max_file_bytes, [&](ifhip_gif_enc_stage* s, const HostFrame& f, size_t pitch, uint32_t* d_len) {
+                return ifhip_gif_encode_batch_device(s, f.d, f.image_bytes, stride, alpha_meaningful, 1, repeat, delay, needs_user_input, f.side_output(), pitch,
+                                                     d_len, d_len + 1, nullptr, nullptr, nullptr);
+            })) return rc;
+    return refuse_unfitted_file(status, *len);
 }
 
 }  // extern "C"

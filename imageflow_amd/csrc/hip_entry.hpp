@@ -1,7 +1,8 @@
 // hip_entry.hpp -- the host code around the kernel launches of the C entry points, for the translation units that include
 // hip_runtime.h (common.hpp stays free of it): the status of a failed HIP call, the check of a batch of BGRA frames, and
 // the device memory of the synchronous host-buffer drop-ins, taken from the devmem.cpp cache like every other block.
-// What the file decoders share on top of this (batch check, staged block, drop-in frame) is in decode_handoff.hpp.
+// What the file decoders share on top of this (batch check, staged block, drop-in frame) is in decode_handoff.hpp, what
+// the file coders share (the opening of a batch, the drop-in that brings a file down) in encode_handoff.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 

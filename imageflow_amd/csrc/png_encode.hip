@@ -12,7 +12,7 @@
 #include <algorithm>
 #include <memory>
 
-#include "hip_entry.hpp"
+#include "encode_handoff.hpp"
 #include "png_frame_device.hpp"      // (with png_deflate.hpp and png_encode_core.hpp)
 
 namespace ifhip {
@@ -108,11 +108,8 @@ size_t ifhip_png_enc_stage_max_file_bytes(const ifhip_png_enc_stage* stage) { re
 
 int ifhip_png_encode_batch_device(ifhip_png_enc_stage* stage, const uint8_t* d_images, size_t image_bytes, uint32_t stride, uint32_t n_images,
                                   int zlib_level, uint8_t* d_files, size_t file_pitch, uint32_t* d_lengths, uint32_t* d_status, void* hip_stream) {
-    if (!stage) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null stage");
-    if (n_images == 0) return IFHIP_OK;
-    if (n_images > stage->max_images) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: %u images exceed the stage capacity %u", n_images, stage->max_images);
-    if (int rc = check_frames(d_images, image_bytes, stage->width, stage->height, stride, "image")) return rc;
-    if (!d_files || !d_lengths) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
+    bool go = false;
+    if (int rc = open_encode_batch(stage, d_images, image_bytes, stride, n_images, d_files, d_lengths, &go); rc || !go) return rc;
     if (zlib_level < -1 || zlib_level > 9) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: zlib_level is -1 or 0..9");
     if (file_pitch < kPngFraming + 6u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: file_pitch below %u bytes", kPngFraming + 6u);
     if (int rc = stage->deflate.allocate(stage->max_images)) return rc;
@@ -132,20 +129,13 @@ int ifhip_png_encode_batch_device(ifhip_png_enc_stage* stage, const uint8_t* d_i
 
 int ifhip_png_encode(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int color_type, int zlib_level, uint8_t* out,
                      size_t capacity, size_t* len) {
-    if (!len) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null length out-pointer");
-    *len = 0;
-    ifhip_png_enc_stage* stage = nullptr;
-    if (int rc = ifhip_png_enc_stage_create(&stage, width, height, color_type, 1)) return rc;
-    std::unique_ptr<ifhip_png_enc_stage, void (*)(ifhip_png_enc_stage*)> guard(stage, [](ifhip_png_enc_stage* s) { (void)hipStreamSynchronize(nullptr); ifhip_png_enc_stage_destroy(s); });
-    const size_t pitch = (ifhip_png_enc_stage_max_file_bytes(stage) + 15u) & ~static_cast<size_t>(15u);
-    HostFrame f;
-    if (int rc = f.up(bgra, width, height, stride, pitch + 16u)) return rc;
-    uint32_t* d_len = reinterpret_cast<uint32_t*>(f.side_output() + pitch);
-    if (int rc = ifhip_png_encode_batch_device(stage, f.d, f.image_bytes, stride, 1, zlib_level, f.side_output(), pitch, d_len, d_len + 1, nullptr)) return rc;
     uint32_t status = 0;
-    if (int rc = f.down_file(pitch, out, capacity, len, &status)) return rc;
-    if (status || !*len) return fail(IFHIP_INVALID_STATE, "InvalidState: the file did not fit its worst-case size (status %u)", status);
-    return IFHIP_OK;
+    if (int rc = encode_host_frame(
+            bgra, width, height, stride, out, capacity, len, &status, [&](ifhip_png_enc_stage** s) { return ifhip_png_enc_stage_create(s, width, height, color_type, 1); },
+            ifhip_png_enc_stage_destroy, ifhip_png_enc_stage_max_file_bytes, [&](ifhip_png_enc_stage* s, const HostFrame& f, size_t pitch, uint32_t* d_len) {
+                return ifhip_png_encode_batch_device(s, f.d, f.image_bytes, stride, 1, zlib_level, f.side_output(), pitch, d_len, d_len + 1, nullptr);
+            })) return rc;
+    return refuse_unfitted_file(status, *len);
 }
 
 }  // extern "C"

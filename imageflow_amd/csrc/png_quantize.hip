@@ -20,7 +20,7 @@
 #include <cstring>
 #include <memory>
 
-#include "hip_entry.hpp"
+#include "encode_handoff.hpp"
 #include "png_frame_device.hpp"      // (with png_deflate.hpp)
 #include "png_quantize.hpp"           // (with png_quantize_core.hpp)
 
@@ -273,6 +273,28 @@ int pq_launch_palette(const QuantArgs& q, hipStream_t st) {
     return IFHIP_OK;
 }
 
+int QuantScratch::allocate(size_t n) {
+    max_images = n;
+    HIP_TRY(DEV_MALLOC(&d_tables, (quant_table_words(n) + n * kPqStateWords) * sizeof(uint32_t)));
+    HIP_TRY(DEV_MALLOC(&d_ekey, n * kPqMaxEntries * sizeof(uint32_t)));
+    HIP_TRY(DEV_MALLOC(&d_ew, n * kPqMaxEntries * sizeof(uint32_t)));
+    HIP_TRY(DEV_MALLOC(&d_edmin, n * kPqMaxEntries * sizeof(uint64_t)));
+    HIP_TRY(DEV_MALLOC(&d_result, n * kPqResultWords * sizeof(uint32_t)));
+    return IFHIP_OK;
+}
+
+void QuantScratch::fill(QuantArgs* qp, const uint8_t* images, size_t image_bytes, uint32_t stride, uint32_t w, uint32_t h, uint32_t n_images,
+                        int alpha_meaningful, uint32_t max_colors, uint32_t speed, uint32_t target, uint32_t minimum) const {
+    QuantArgs& q = *qp;
+    std::memset(&q, 0, sizeof q);
+    q.images = images; q.image_bytes = image_bytes; q.stride = stride; q.w = w; q.h = h; q.n_images = n_images;
+    q.alpha = alpha_meaningful ? 1u : 0u; q.max_colors = max_colors;
+    q.iterations = pq_speed_iterations(speed); q.max_entries = pq_speed_max_entries(speed);
+    q.bound_target = pq_quality_bound(target); q.bound_min = pq_quality_bound(minimum);
+    q.tables = d_tables; q.state = d_tables + quant_table_words(max_images);
+    q.ekey = d_ekey; q.ew = d_ew; q.edmin = d_edmin; q.result = d_result;
+}
+
 }  // namespace ifhip
 
 using namespace ifhip;
@@ -282,9 +304,8 @@ struct ifhip_png_quant_stage {
     PngDeflateScratch deflate;
     size_t body_pitch = 0;
     uint8_t* d_body = nullptr;          // the zlib bodies, until finish knows where in the file they go
-    uint32_t *d_tables = nullptr, *d_ekey = nullptr, *d_ew = nullptr, *d_result = nullptr;   // (the state words lie behind the tables)
-    uint64_t* d_edmin = nullptr;
-    StageScratch blocks{&d_body, &d_tables, &d_ekey, &d_ew, &d_edmin, &d_result};
+    QuantScratch quant;
+    StageScratch blocks{&d_body, &quant.d_tables, &quant.d_ekey, &quant.d_ew, &quant.d_edmin, &quant.d_result};
 };
 
 namespace {
@@ -293,12 +314,7 @@ int quant_stage_allocate(ifhip_png_quant_stage* s) {
     const size_t n = s->max_images;
     return s->blocks.ensure([&]() -> int {                       // the stage's own buffers, on the same device
         HIP_TRY(DEV_MALLOC(&s->d_body, n * s->body_pitch));
-        HIP_TRY(DEV_MALLOC(&s->d_tables, (quant_table_words(n) + n * kPqStateWords) * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&s->d_ekey, n * kPqMaxEntries * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&s->d_ew, n * kPqMaxEntries * sizeof(uint32_t)));
-        HIP_TRY(DEV_MALLOC(&s->d_edmin, n * kPqMaxEntries * sizeof(uint64_t)));
-        HIP_TRY(DEV_MALLOC(&s->d_result, n * kPqResultWords * sizeof(uint32_t)));
-        return IFHIP_OK;
+        return s->quant.allocate(n);
     });
 }
 int clamp_int(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
@@ -333,11 +349,8 @@ int ifhip_png_quantize_batch_device(ifhip_png_quant_stage* stage, const uint8_t*
                                     uint32_t n_images, int quality, int min_quality, int speed, uint32_t max_colors, int dither, int zlib_level,
                                     uint8_t* d_files, size_t file_pitch, uint32_t* d_lengths, uint32_t* d_status, uint8_t* d_palettes, uint8_t* d_indices,
                                     double* d_mse, void* hip_stream) {
-    if (!stage) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null stage");
-    if (n_images == 0) return IFHIP_OK;
-    if (n_images > stage->max_images) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: %u images exceed the stage capacity %u", n_images, stage->max_images);
-    if (int rc = check_frames(d_images, image_bytes, stage->width, stage->height, stride, "image")) return rc;
-    if (!d_files || !d_lengths) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
+    bool go = false;
+    if (int rc = open_encode_batch(stage, d_images, image_bytes, stride, n_images, d_files, d_lengths, &go); rc || !go) return rc;
     if (max_colors < 2u || max_colors > kPqMaxColors) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: max_colors is 2..256");
     if (dither != 0 && dither != 1) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: dither is 0 or 1");
     if (zlib_level < -1 || zlib_level > 9) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: zlib_level is -1 or 0..9");
@@ -350,13 +363,9 @@ int ifhip_png_quantize_batch_device(ifhip_png_quant_stage* stage, const uint8_t*
     const uint32_t sp = static_cast<uint32_t>(clamp_int(speed < 0 ? 4 : speed, 1, 10));
     const int target = clamp_int(quality < 0 ? 100 : quality, 0, 100), minimum = clamp_int(min_quality < 0 ? 0 : min_quality, 0, target);
     QuantArgs q;
-    std::memset(&q, 0, sizeof q);
-    q.images = d_images; q.image_bytes = image_bytes; q.stride = stride; q.w = stage->width; q.h = stage->height; q.n_images = n_images;
-    q.alpha = alpha_meaningful ? 1u : 0u; q.max_colors = max_colors; q.dither = static_cast<uint32_t>(dither);
-    q.iterations = pq_speed_iterations(sp); q.max_entries = pq_speed_max_entries(sp); q.zlib_header = png_zlib_header(zlib_level);
-    q.bound_target = pq_quality_bound(static_cast<uint32_t>(target)); q.bound_min = pq_quality_bound(static_cast<uint32_t>(minimum));
-    q.tables = stage->d_tables; q.state = stage->d_tables + quant_table_words(stage->max_images);
-    q.ekey = stage->d_ekey; q.ew = stage->d_ew; q.edmin = stage->d_edmin; q.result = stage->d_result;
+    stage->quant.fill(&q, d_images, image_bytes, stride, stage->width, stage->height, n_images, alpha_meaningful, max_colors, sp,
+                      static_cast<uint32_t>(target), static_cast<uint32_t>(minimum));
+    q.dither = static_cast<uint32_t>(dither); q.zlib_header = png_zlib_header(zlib_level);
     q.palettes = d_palettes; q.indices = d_indices; q.mse = d_mse;
     q.files = d_files; q.file_pitch = file_pitch; q.lengths = d_lengths; q.status_out = d_status;
     // the zlib body first lands in the stage, which has room for its worst case; finish copies it into its frame
@@ -371,24 +380,17 @@ int ifhip_png_quantize_batch_device(ifhip_png_quant_stage* stage, const uint8_t*
 
 int ifhip_png_quantize(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int alpha_meaningful, int quality, int min_quality, int speed,
                        uint8_t* out, size_t capacity, size_t* len, uint32_t* status) {
-    if (!len) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null length out-pointer");
-    *len = 0;
-    if (status) *status = 0;
-    ifhip_png_quant_stage* stage = nullptr;
-    if (int rc = ifhip_png_quant_stage_create(&stage, width, height, 1)) return rc;
-    std::unique_ptr<ifhip_png_quant_stage, void (*)(ifhip_png_quant_stage*)> guard(stage, [](ifhip_png_quant_stage* s) { (void)hipStreamSynchronize(nullptr); ifhip_png_quant_stage_destroy(s); });
-    const size_t pitch = (ifhip_png_quant_stage_max_file_bytes(stage) + 15u) & ~static_cast<size_t>(15u);
-    HostFrame f;
-    if (int rc = f.up(bgra, width, height, stride, pitch + 16u)) return rc;
-    uint32_t* d_len = reinterpret_cast<uint32_t*>(f.side_output() + pitch);
-    if (int rc = ifhip_png_quantize_batch_device(stage, f.d, f.image_bytes, stride, alpha_meaningful, 1, quality, min_quality, speed, kPqMaxColors, 1, 6,
-                                                 f.side_output(), pitch, d_len, d_len + 1, nullptr, nullptr, nullptr, nullptr)) return rc;
+    if (len && status) *status = 0;                                        // (a null `len` is refused below with nothing written)
     uint32_t word = 0;
-    if (int rc = f.down_file(pitch, out, capacity, len, &word)) return rc;
+    if (int rc = encode_host_frame(
+            bgra, width, height, stride, out, capacity, len, &word, [&](ifhip_png_quant_stage** s) { return ifhip_png_quant_stage_create(s, width, height, 1); },
+            ifhip_png_quant_stage_destroy, ifhip_png_quant_stage_max_file_bytes, [&](ifhip_png_quant_stage* s, const HostFrame& f, size_t pitch, uint32_t* d_len) {
+                return ifhip_png_quantize_batch_device(s, f.d, f.image_bytes, stride, alpha_meaningful, 1, quality, min_quality, speed, kPqMaxColors, 1, 6,
+                                                       f.side_output(), pitch, d_len, d_len + 1, nullptr, nullptr, nullptr, nullptr);
+            })) return rc;
     if (status) *status = word;
     if (word == kPqQualityTooLow) return IFHIP_OK;                         // no file: the caller writes a lossless one (pngquant.rs:105-139)
-    if (word || !*len) return fail(IFHIP_INVALID_STATE, "InvalidState: the file did not fit its worst-case size (status %u)", word);
-    return IFHIP_OK;
+    return refuse_unfitted_file(word, *len);
 }
 
 }  // extern "C"

@@ -33,6 +33,18 @@ struct QuantArgs {
 
 inline size_t quant_table_words(size_t n) { return n * kPqLevels * 2u * kPqSlots; }
 
+// The scratch of the palette stages for a stage of up to max_images images.  The five blocks belong to the one owner of the
+// stage that embeds this (StageScratch: all of a stage's blocks or none), which lists them and calls allocate() in its turn.
+struct QuantScratch {
+    uint32_t *d_tables = nullptr, *d_ekey = nullptr, *d_ew = nullptr, *d_result = nullptr;   // (the state words lie behind the tables)
+    uint64_t* d_edmin = nullptr;
+    size_t max_images = 0;
+    int allocate(size_t n);             // for n images, one checked allocation per block: IFHIP_OK, or the status of the one that failed
+    // A zeroed QuantArgs with the scratch, the batch's geometry and the bounds of speed 1..10, target 0..100 and minimum 0..target.
+    void fill(QuantArgs* q, const uint8_t* images, size_t image_bytes, uint32_t stride, uint32_t w, uint32_t h, uint32_t n_images,
+              int alpha_meaningful, uint32_t max_colors, uint32_t speed, uint32_t target, uint32_t minimum) const;
+};
+
 // The clear of the tables and state words of the images in use, the histogram launches (one per posterise level) and the
 // palette launch: q.result then holds every image's palette.  Asynchronous on st.
 int pq_launch_palette(const QuantArgs& q, hipStream_t st);

@@ -27,7 +27,7 @@
 #include <memory>
 
 #include "block_scan.hpp"
-#include "hip_entry.hpp"
+#include "encode_handoff.hpp"
 #include "stage_scratch.hpp"
 #include "webp_encode_core.hpp"
 
@@ -502,11 +502,8 @@ size_t ifhip_webp_enc_stage_max_file_bytes(const ifhip_webp_enc_stage* stage) { 
 
 int ifhip_webp_encode_batch_device(ifhip_webp_enc_stage* stage, const uint8_t* d_images, size_t image_bytes, uint32_t stride, uint32_t n_images,
                                    uint8_t* d_files, size_t file_pitch, uint32_t* d_lengths, uint32_t* d_status, void* hip_stream) {
-    if (!stage) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null stage");
-    if (n_images == 0) return IFHIP_OK;
-    if (n_images > stage->max_images) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: %u images exceed the stage capacity %u", n_images, stage->max_images);
-    if (int rc = check_frames(d_images, image_bytes, stage->width, stage->height, stride, "image")) return rc;
-    if (!d_files || !d_lengths) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
+    bool go = false;
+    if (int rc = open_encode_batch(stage, d_images, image_bytes, stride, n_images, d_files, d_lengths, &go); rc || !go) return rc;
     if (reinterpret_cast<uintptr_t>(d_files) & 3u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: d_files must be 4-byte aligned");
     if (file_pitch < kWebpRiff + 8u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: file_pitch below %u bytes", kWebpRiff + 8u);
     if (int rc = stage->allocate()) return rc;
@@ -529,20 +526,13 @@ int ifhip_webp_encode_batch_device(ifhip_webp_enc_stage* stage, const uint8_t* d
 }
 
 int ifhip_webp_encode(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int alpha_meaningful, uint8_t* out, size_t capacity, size_t* len) {
-    if (!len) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null length out-pointer");
-    *len = 0;
-    ifhip_webp_enc_stage* stage = nullptr;
-    if (int rc = ifhip_webp_enc_stage_create(&stage, width, height, alpha_meaningful, 1)) return rc;
-    std::unique_ptr<ifhip_webp_enc_stage, void (*)(ifhip_webp_enc_stage*)> guard(stage, [](ifhip_webp_enc_stage* s) { (void)hipStreamSynchronize(nullptr); ifhip_webp_enc_stage_destroy(s); });
-    const size_t pitch = (ifhip_webp_enc_stage_max_file_bytes(stage) + 15u) & ~static_cast<size_t>(15u);
-    HostFrame f;
-    if (int rc = f.up(bgra, width, height, stride, pitch + 16u)) return rc;
-    uint32_t* d_len = reinterpret_cast<uint32_t*>(f.side_output() + pitch);
-    if (int rc = ifhip_webp_encode_batch_device(stage, f.d, f.image_bytes, stride, 1, f.side_output(), pitch, d_len, d_len + 1, nullptr)) return rc;
     uint32_t status = 0;
-    if (int rc = f.down_file(pitch, out, capacity, len, &status)) return rc;
-    if (status || !*len) return fail(IFHIP_INVALID_STATE, "InvalidState: the file did not fit its worst-case size (status %u)", status);
-    return IFHIP_OK;
+    if (int rc = encode_host_frame(
+            bgra, width, height, stride, out, capacity, len, &status, [&](ifhip_webp_enc_stage** s) { return ifhip_webp_enc_stage_create(s, width, height, alpha_meaningful, 1); },
+            ifhip_webp_enc_stage_destroy, ifhip_webp_enc_stage_max_file_bytes, [&](ifhip_webp_enc_stage* s, const HostFrame& f, size_t pitch, uint32_t* d_len) {
+                return ifhip_webp_encode_batch_device(s, f.d, f.image_bytes, stride, 1, f.side_output(), pitch, d_len, d_len + 1, nullptr);
+            })) return rc;
+    return refuse_unfitted_file(status, *len);
 }
 
 }  // extern "C"
