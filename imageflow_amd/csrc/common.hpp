@@ -41,7 +41,7 @@ int require_gfx950(int* device_out);                  // IFHIP_OK and the curren
 #define DEV_MALLOC(pp, n) static_cast<hipError_t>(::ifhip::cached_malloc(reinterpret_cast<void**>(pp), (n)))
 #define DEV_FREE(p) static_cast<hipError_t>(::ifhip::cached_free(p))
 
-// An ICC profile that describes sRGB itself (csrc/jpeg_entropy.hip; the JPEG APP2 and the PNG iCCP readers share it)
+// An ICC profile that describes sRGB itself (csrc/jpeg_parse.cpp; the JPEG APP2 and the PNG iCCP readers share it)
 bool icc_describes_srgb(const uint8_t* profile, size_t profile_bytes);
 // ifhip_jpeg_icc_profile_kind with the profile it judged: the APP2 chunks put together (empty for kind 0)
 int jpeg_icc_profile(const uint8_t* jpeg, size_t len, int* kind, std::vector<uint8_t>* profile);

@@ -5,8 +5,8 @@
 // bit stream is decoded by thousands of lanes at once and lands as the quantised coefficient planes the pixel stage
 // (jpeg_kernels.hip) consumes, so a compressed file is the only thing that crosses PCIe.
 //
-// Host (this file, plain C++): marker parsing (SOF0/SOF1, DHT, DQT, DRI, SOS), byte un-stuffing, splitting the scan at
-// restart markers into *segments* (independent bit streams with a known start state), canonical Huffman tables.
+// Host: jpeg_parse.cpp reads the markers (SOF0/SOF1, DHT, DQT, DRI, SOS), un-stuffs the scan and splits it at restart markers
+// into *segments* (independent bit streams with a known start state); this file derives the decode tables and assembles the batch.
 // Device: the self-synchronising parallel decode (Klein & Wiseman; Weissenberger & Schmidt, ICPP 2018):
 //   * the stream is cut into sub-sequences of 1024 bits, one lane each;
 //   * round 0 decodes every sub-sequence speculatively from state (block 0 of the MCU, coefficient 0); because Huffman
@@ -22,7 +22,6 @@
 // Coefficient-exact against oracle/jpeg_oracle.c jo_jpeg_read_coefficients (itself pinned to libjpeg-turbo).
 #include <hip/hip_runtime.h>
 
-#include <chrono>
 #include <cstdlib>
 #include <cstring>
 #include <memory>
@@ -30,17 +29,15 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
-#include <type_traits>
 #include <cstdio>
 #include <vector>
 
 #include "hip_entry.hpp"
+#include "jpeg_parse.hpp"
 
 namespace ifhip {
 
-constexpr uint32_t kSubBits = 1024;     // bits per sub-sequence (one lane)
-constexpr uint32_t kSubWords = kSubBits / 32;
-constexpr uint32_t kLutBits = 9;
+constexpr uint32_t kLutBits = 9;          // (kSubBits, the bits of a sub-sequence: jpeg_parse.hpp, the un-stuffer pads to it)
 
 // Huffman tables in the form every pass reads.  Everything a pass needs from a symbol sits in one 32-bit entry, found
 // with ONE lookup by the next kLutBits bits of the stream -- or two for the 2 % of the symbols whose code is longer:
@@ -79,7 +76,6 @@ __host__ __device__ inline uint32_t pair_entry(uint32_t first, uint32_t both) { 
 __host__ __device__ inline uint32_t invalid_entry(bool ac) { return (32u << 16) | ((ac ? 64u : 1u) << 8) | 16u; }
 
 
-constexpr uint32_t kMaxBlocksInMcu = 10;        // libjpeg's D_MAX_BLOCKS_IN_MCU: files with more are rejected by the parser
 struct EntropyGeom {
     uint32_t ncomp, blocks_per_mcu, mcus_w, mcus_h;
     uint32_t bw[3], bh[3];
@@ -735,137 +731,9 @@ __global__ void __launch_bounds__(kWriteLanes) entropy_write_kernel(const Entrop
 using namespace ifhip;
 
 // ==================================================================================================================
-// host: parser, un-stuffing, tables
+// host: decode tables (the parser and the un-stuffer: jpeg_parse.cpp)
 // ==================================================================================================================
 namespace {
-
-struct HuffSpec { uint8_t bits[17]; uint8_t vals[256]; bool present = false; };
-
-struct ParsedJpeg {
-    uint32_t width = 0, height = 0;
-    int ncomp = 0;
-    uint8_t comp_id[3] = {0, 0, 0}, hs[3] = {0, 0, 0}, vs[3] = {0, 0, 0}, tq[3] = {0, 0, 0}, td[3] = {0, 0, 0}, ta[3] = {0, 0, 0};
-    uint16_t qt[4][64];
-    bool qt_present[4] = {false, false, false, false};
-    HuffSpec dc[4], ac[4];
-    uint32_t restart_interval = 0;
-    int adobe_transform = -1;                        // APP14 "Adobe" colour transform flag, -1: no such marker
-    size_t scan_begin = 0;
-    uint32_t mcus_w = 0, mcus_h = 0, bw[3] = {0, 0, 0}, bh[3] = {0, 0, 0}, blocks_per_mcu = 0;
-};
-
-const uint8_t kZigzagHost[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48,
-                                 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22,
-                                 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
-int parse_jpeg(const uint8_t* d, size_t len, ParsedJpeg* out) {
-    ParsedJpeg& P = *out;
-    if (!d || len < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: not a JPEG (no SOI)");
-    size_t i = 2;
-    bool have_sof = false;
-    while (i + 4 <= len) {
-        if (d[i] != 0xFF) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: marker expected at byte %zu", i);
-        while (i < len && d[i] == 0xFF) ++i;                                   // fill bytes
-        if (i >= len) break;
-        const uint8_t m = d[i++];
-        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;      // no payload
-        if (m == 0xD9) break;
-        if (i + 2 > len) break;
-        const size_t seg = (static_cast<size_t>(d[i]) << 8) | d[i + 1];
-        if (seg < 2 || i + seg > len) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: truncated marker segment FF%02X", m);
-        const uint8_t* q = d + i + 2;
-        const size_t n = seg - 2;
-        if (m == 0xDB) {                                                       // DQT
-            size_t k = 0;
-            while (k < n) {
-                const int pq = q[k] >> 4, t = q[k] & 15;
-                ++k;
-                if (t > 3 || k + (pq ? 128u : 64u) > n) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad DQT");
-                for (int z = 0; z < 64; ++z) {
-                    const uint16_t v = pq ? static_cast<uint16_t>((q[k] << 8) | q[k + 1]) : q[k];
-                    k += pq ? 2 : 1;
-                    P.qt[t][kZigzagHost[z]] = v;
-                }
-                P.qt_present[t] = true;
-            }
-        } else if (m == 0xC4) {                                                // DHT
-            size_t k = 0;
-            while (k + 17 <= n) {
-                const int tc = q[k] >> 4, th = q[k] & 15;
-                if (tc > 1 || th > 3) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad DHT");
-                HuffSpec& h = tc ? P.ac[th] : P.dc[th];
-                h.bits[0] = 0;
-                size_t total = 0;
-                for (int l = 1; l <= 16; ++l) { h.bits[l] = q[k + l]; total += q[k + l]; }
-                k += 17;
-                if (total > 256 || k + total > n) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad DHT");
-                std::memset(h.vals, 0, sizeof h.vals);
-                std::memcpy(h.vals, q + k, total);
-                k += total;
-                h.present = true;
-            }
-        } else if (m == 0xC0 || m == 0xC1) {                                   // baseline / extended sequential, Huffman
-            if (n < 6 || q[0] != 8) return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: %d-bit JPEG", n ? q[0] : 0);
-            P.height = (q[1] << 8) | q[2];
-            P.width = (q[3] << 8) | q[4];
-            P.ncomp = q[5];
-            if (P.ncomp != 1 && P.ncomp != 3) return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: %d-component JPEG", P.ncomp);
-            if (n < 6u + 3u * P.ncomp) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad SOF");
-            for (int c = 0; c < P.ncomp; ++c) {
-                P.comp_id[c] = q[6 + 3 * c];
-                P.hs[c] = q[7 + 3 * c] >> 4; P.vs[c] = q[7 + 3 * c] & 15; P.tq[c] = q[8 + 3 * c] & 3;
-            }
-            have_sof = true;
-        } else if (m >= 0xC2 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
-            return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: JPEG process SOF%d (only baseline Huffman)", m - 0xC0);
-        } else if (m == 0xDD) {
-            if (n >= 2) P.restart_interval = (q[0] << 8) | q[1];
-        } else if (m == 0xEE && n >= 12 && std::memcmp(q, "Adobe", 5) == 0) {
-            P.adobe_transform = q[11];                                         // 0: RGB / CMYK stored as is, 1: YCbCr, 2: YCCK
-        } else if (m == 0xDA) {                                                // SOS
-            if (!have_sof) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: SOS before SOF");
-            if (n < 1 || q[0] != P.ncomp || n < 4u + 2u * P.ncomp)
-                return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: non-interleaved / multi-scan JPEG");
-            for (int s = 0; s < P.ncomp; ++s) {
-                int c = -1;
-                for (int k = 0; k < P.ncomp; ++k) if (P.comp_id[k] == q[1 + 2 * s]) c = k;
-                if (c != s) return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: scan component order");
-                P.td[c] = q[2 + 2 * s] >> 4; P.ta[c] = q[2 + 2 * s] & 15;
-                if (P.td[c] > 3 || P.ta[c] > 3) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad SOS");
-            }
-            P.scan_begin = i + seg;
-            break;
-        }
-        i += seg;
-    }
-    if (!have_sof || !P.scan_begin || P.width == 0 || P.height == 0) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: no frame / scan found");
-    // libjpeg's colour-space guess (jdapimin.c default_decompress_parms): the pixel stage converts YCbCr only
-    if (P.ncomp == 3 && (P.adobe_transform == 0 ||
-                         (P.adobe_transform < 0 && P.comp_id[0] == 'R' && P.comp_id[1] == 'G' && P.comp_id[2] == 'B')))
-        return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: RGB-coded JPEG (no YCbCr transform)");
-    uint32_t hmax = 1, vmax = 1;
-    for (int c = 0; c < P.ncomp; ++c) {
-        if (P.hs[c] < 1 || P.hs[c] > 2 || P.vs[c] < 1 || P.vs[c] > 2)
-            return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: sampling factor %dx%d", P.hs[c], P.vs[c]);
-        if (!P.qt_present[P.tq[c]] || !P.dc[P.td[c]].present || !P.ac[P.ta[c]].present)
-            return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: missing quantisation or Huffman table");
-        hmax = std::max<uint32_t>(hmax, P.hs[c]); vmax = std::max<uint32_t>(vmax, P.vs[c]);
-    }
-    if (P.ncomp == 1) { P.hs[0] = P.vs[0] = 1; hmax = vmax = 1; }             // a single-component scan is never interleaved
-    P.mcus_w = (P.width + 8 * hmax - 1) / (8 * hmax);
-    P.mcus_h = (P.height + 8 * vmax - 1) / (8 * vmax);
-    P.blocks_per_mcu = 0;
-    for (int c = 0; c < P.ncomp; ++c) { P.bw[c] = P.mcus_w * P.hs[c]; P.bh[c] = P.mcus_h * P.vs[c]; P.blocks_per_mcu += P.hs[c] * P.vs[c]; }
-    // The same whitelist as the pixel stage (make_geom): luma carries the maximum factors, chroma is 1x1 -- 4:4:4, 4:2:2,
-    // 4:4:0, 4:2:0.  That bounds an MCU at 6 blocks; libjpeg itself refuses more than D_MAX_BLOCKS_IN_MCU = 10
-    // (e.g. 2x2 / 2x2 / 2x2), and the per-MCU block tables of the decoder are sized by that constant.
-    if (P.ncomp == 3 && (P.hs[0] != hmax || P.vs[0] != vmax || P.hs[1] != 1 || P.vs[1] != 1 || P.hs[2] != 1 || P.vs[2] != 1))
-        return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: sampling %dx%d,%dx%d,%dx%d (chroma must be 1x1)",
-                    P.hs[0], P.vs[0], P.hs[1], P.vs[1], P.hs[2], P.vs[2]);
-    if (P.blocks_per_mcu > kMaxBlocksInMcu)
-        return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: %u blocks per MCU (limit %u)", P.blocks_per_mcu, kMaxBlocksInMcu);
-    return IFHIP_OK;
-}
 
 void derive_search_table(const HuffSpec& h, SearchTab* t) {
     std::memset(t, 0, sizeof *t);
@@ -976,100 +844,6 @@ void derive_image_tables(const ParsedJpeg& P, FastTabs* F, SearchTab* S6, uint32
     if (pool_used_out) *pool_used_out = pool_used;
 }
 
-// Un-stuffs the scan (runs between 0xFF bytes are copied whole) and cuts it at restart markers into segments.
-// Returns the number of MCUs the segments cover (fewer than the image has: the scan ended early).
-uint32_t unstuff_scan(const uint8_t* d, size_t len, const ParsedJpeg& P, std::vector<std::vector<uint8_t>>* seg_bytes,
-                      std::vector<uint32_t>* seg_mcu0, std::vector<uint32_t>* seg_mcus) {
-    const uint32_t total_mcus = P.mcus_w * P.mcus_h;
-    const uint32_t per_seg = P.restart_interval ? P.restart_interval : total_mcus;
-    uint32_t mcu0 = 0;
-    size_t i = P.scan_begin;
-    bool more = true;
-    while (more && mcu0 < total_mcus) {
-        seg_bytes->emplace_back();
-        std::vector<uint8_t>& bytes = seg_bytes->back();
-        more = false;
-        while (i < len) {
-            const uint8_t* ff = static_cast<const uint8_t*>(std::memchr(d + i, 0xFF, len - i));
-            const size_t run_end = ff ? static_cast<size_t>(ff - d) : len;
-            bytes.insert(bytes.end(), d + i, d + run_end);
-            i = run_end;
-            if (i >= len) break;
-            ++i;                                                           // the 0xFF
-            while (i < len && d[i] == 0xFF) ++i;                           // fill bytes before a marker
-            if (i >= len) break;
-            const uint8_t m = d[i++];
-            if (m == 0x00) { bytes.push_back(0xFF); continue; }
-            if (m >= 0xD0 && m <= 0xD7) { more = true; break; }            // restart: next segment
-            break;                                                         // EOI or any other marker: scan ends
-        }
-        const uint32_t mcus = std::min(per_seg, total_mcus - mcu0);
-        seg_mcu0->push_back(mcu0);
-        seg_mcus->push_back(mcus);
-        mcu0 += mcus;
-    }
-    return mcu0;
-}
-
-// The same walk, straight into the staging buffer the device reads: every restart segment starts on a sub-sequence boundary
-// and is zero-padded to the next one (an empty segment still takes one sub-sequence).  No per-segment vectors: a prepared
-// file used to cost a 400 KB vector grown by doubling, a copy out of it and a free that glibc answered with madvise() -- 40 %
-// of the host CPU of an ABI job (round 5, profiles/r5_abi_jobs_host_cpu_slots32.txt).  `cap` bytes are available at dst
-// (packed_scan_bound); returns the MCUs covered, *n_sub the sub-sequences written.
-size_t packed_scan_bound(size_t len, const ParsedJpeg& P) {
-    const uint32_t total_mcus = P.mcus_w * P.mcus_h;
-    const uint32_t per_seg = P.restart_interval ? P.restart_interval : total_mcus;
-    const size_t max_segs = per_seg ? (static_cast<size_t>(total_mcus) + per_seg - 1) / per_seg : 1;
-    return (len > P.scan_begin ? len - P.scan_begin : 0) + (max_segs + 1) * (kSubBits / 8u);
-}
-uint32_t unstuff_scan_packed(const uint8_t* d, size_t len, const ParsedJpeg& P, uint8_t* dst, size_t cap, std::vector<uint32_t>* seg_mcu0,
-                             std::vector<uint32_t>* seg_mcus, std::vector<uint64_t>* seg_bits, std::vector<uint32_t>* seg_nsub,
-                             std::vector<uint32_t>* seg_first_word, uint64_t* n_sub) {
-    constexpr size_t kSubBytes = kSubBits / 8u;
-    const uint32_t total_mcus = P.mcus_w * P.mcus_h;
-    const uint32_t per_seg = P.restart_interval ? P.restart_interval : total_mcus;
-    uint32_t mcu0 = 0;
-    uint64_t subs = 0;
-    size_t i = P.scan_begin;
-    bool more = true;
-    while (more && mcu0 < total_mcus) {
-        uint8_t* out = dst + subs * kSubBytes;
-        size_t nb = 0;
-        const size_t room = cap - static_cast<size_t>(subs) * kSubBytes;          // (the bound leaves a sub-sequence per segment beyond the scan's bytes)
-        more = false;
-        while (i < len) {
-            const uint8_t* ff = static_cast<const uint8_t*>(std::memchr(d + i, 0xFF, len - i));
-            const size_t run_end = ff ? static_cast<size_t>(ff - d) : len;
-            if (nb + (run_end - i) + 1 + kSubBytes > room) throw std::length_error("scan staging bound exceeded");
-            std::memcpy(out + nb, d + i, run_end - i);
-            nb += run_end - i;
-            i = run_end;
-            if (i >= len) break;
-            ++i;                                                           // the 0xFF
-            while (i < len && d[i] == 0xFF) ++i;                           // fill bytes before a marker
-            if (i >= len) break;
-            const uint8_t m = d[i++];
-            if (m == 0x00) { out[nb++] = 0xFF; continue; }
-            if (m >= 0xD0 && m <= 0xD7) { more = true; break; }            // restart: next segment
-            break;                                                         // EOI or any other marker: scan ends
-        }
-        const uint64_t bits = static_cast<uint64_t>(nb) * 8u;
-        const uint64_t ns = std::max<uint64_t>(1, (bits + kSubBits - 1) / kSubBits);
-        std::memset(out + nb, 0, static_cast<size_t>(ns) * kSubBytes - nb);                   // pad to the 1 024-bit boundary
-        const uint32_t mcus = std::min(per_seg, total_mcus - mcu0);
-        seg_mcu0->push_back(mcu0);
-        seg_mcus->push_back(mcus);
-        seg_bits->push_back(bits);
-        seg_nsub->push_back(static_cast<uint32_t>(ns));
-        seg_first_word->push_back(static_cast<uint32_t>(subs * kSubWords));
-        subs += ns;
-        mcu0 += mcus;
-        if (subs * kSubBits + 4096 >= (1ull << 32)) break;                 // (the caller refuses: more than 512 MB of scan data)
-    }
-    *n_sub = subs;
-    return mcu0;
-}
-
 }  // namespace
 
 struct ifhip_jpeg_entropy {
@@ -1097,206 +871,6 @@ static int dev_alloc(ifhip_jpeg_entropy* e, T** out, size_t count, const T* init
     return IFHIP_OK;
 }
 
-namespace ifhip {
-// Does an ICC profile describe sRGB itself (see ifhip_jpeg_icc_profile_kind in include/imageflow_hip.h: an RGB matrix profile
-// with the sRGB primaries within 0.003 after D50 adaptation and the sRGB tone curve)?  Shared by the JPEG (APP2) and the PNG
-// (iCCP) readers.
-bool icc_describes_srgb(const uint8_t* profile, size_t profile_bytes) {
-    struct View {
-        const uint8_t* p; size_t n;
-        const uint8_t& operator[](size_t i) const { return p[i]; }
-        size_t size() const { return n; }
-    } icc{profile, profile_bytes};
-    // ICC.1 header: size (0..3), colour space (16..19), PCS (20..23); tag table at 128: count, then {sig, offset, size}
-    auto be32 = [&](size_t o) { return (static_cast<uint32_t>(icc[o]) << 24) | (static_cast<uint32_t>(icc[o + 1]) << 16) | (static_cast<uint32_t>(icc[o + 2]) << 8) | icc[o + 3]; };
-    if (icc.size() < 132 || std::memcmp(&icc[16], "RGB ", 4) != 0 || std::memcmp(&icc[20], "XYZ ", 4) != 0) return false;
-    const uint32_t tags = be32(128);
-    if (tags > 200 || 132 + static_cast<size_t>(tags) * 12 > icc.size()) return false;
-    auto find = [&](const char* sig, size_t* off, size_t* size) {
-        for (uint32_t t = 0; t < tags; ++t) {
-            const size_t e = 132 + static_cast<size_t>(t) * 12;
-            if (std::memcmp(&icc[e], sig, 4) != 0) continue;
-            *off = be32(e + 4); *size = be32(e + 8);
-            return *off + *size <= icc.size() && *size >= 8;
-        }
-        return false;
-    };
-    // primaries, D50-adapted (IEC 61966-2-1 through Bradford, as every sRGB profile carries them)
-    static const double want[3][3] = {{0.4360, 0.2225, 0.0139}, {0.3851, 0.7169, 0.0971}, {0.1431, 0.0606, 0.7141}};
-    const char* xyz_sig[3] = {"rXYZ", "gXYZ", "bXYZ"};
-    for (int c = 0; c < 3; ++c) {
-        size_t off = 0, size = 0;
-        if (!find(xyz_sig[c], &off, &size) || size < 20 || std::memcmp(&icc[off], "XYZ ", 4) != 0) return false;
-        for (int k = 0; k < 3; ++k) {
-            const double v = static_cast<int32_t>(be32(off + 8 + 4 * static_cast<size_t>(k))) / 65536.0;
-            if (std::fabs(v - want[c][k]) > 0.003) return false;
-        }
-    }
-    // tone curves: the sRGB parametric form (type 3: g 2.4, a 1/1.055, b 0.055/1.055, c 1/12.92, d 0.04045) or a sampled curve
-    // whose entries follow the sRGB function (checked at every entry; 2 of 65535 is the 16-bit tables' own rounding)
-    const char* trc_sig[3] = {"rTRC", "gTRC", "bTRC"};
-    for (int c = 0; c < 3; ++c) {
-        size_t off = 0, size = 0;
-        if (!find(trc_sig[c], &off, &size) || size < 12) return false;
-        if (std::memcmp(&icc[off], "para", 4) == 0) {
-            if (size < 12 + 20 || ((static_cast<uint32_t>(icc[off + 8]) << 8) | icc[off + 9]) != 3u) return false;
-            static const double p[5] = {2.4, 1.0 / 1.055, 0.055 / 1.055, 1.0 / 12.92, 0.04045};
-            for (int k = 0; k < 5; ++k)
-                if (std::fabs(static_cast<int32_t>(be32(off + 12 + 4 * static_cast<size_t>(k))) / 65536.0 - p[k]) > 0.002) return false;
-        } else if (std::memcmp(&icc[off], "curv", 4) == 0) {
-            const uint32_t n = be32(off + 8);
-            if (n < 256 || 12 + static_cast<size_t>(n) * 2 > size) return false;      // (a single gamma value is not the sRGB curve)
-            for (uint32_t k = 0; k < n; ++k) {
-                const double x = static_cast<double>(k) / (n - 1), y = x <= 0.04045 ? x / 12.92 : std::pow((x + 0.055) / 1.055, 2.4);
-                const double got = ((static_cast<uint32_t>(icc[off + 12 + 2 * static_cast<size_t>(k)]) << 8) | icc[off + 13 + 2 * static_cast<size_t>(k)]) / 65535.0;
-                if (std::fabs(got - y) > 2.0 / 65535.0 + 1e-4) return false;
-            }
-        } else {
-            return false;
-        }
-    }
-    return true;
-}
-}  // namespace ifhip
-
-extern "C" {
-
-int ifhip_jpeg_parse_headers(const uint8_t* jpeg, size_t len, uint32_t* width, uint32_t* height, int* n_components,
-                             uint8_t* h_samp3, uint8_t* v_samp3, uint32_t* blocks_w3, uint32_t* blocks_h3,
-                             uint16_t* qt3x64, uint32_t* restart_interval) {
-    ParsedJpeg P;
-    int rc = parse_jpeg(jpeg, len, &P);
-    if (rc) return rc;
-    if (width) *width = P.width;
-    if (height) *height = P.height;
-    if (n_components) *n_components = P.ncomp;
-    for (int c = 0; c < 3; ++c) {
-        if (h_samp3) h_samp3[c] = c < P.ncomp ? P.hs[c] : 0;
-        if (v_samp3) v_samp3[c] = c < P.ncomp ? P.vs[c] : 0;
-        if (blocks_w3) blocks_w3[c] = c < P.ncomp ? P.bw[c] : 0;
-        if (blocks_h3) blocks_h3[c] = c < P.ncomp ? P.bh[c] : 0;
-        if (qt3x64) {
-            if (c < P.ncomp) std::memcpy(qt3x64 + 64 * c, P.qt[P.tq[c]], 128);
-            else std::memset(qt3x64 + 64 * c, 0, 128);
-        }
-    }
-    if (restart_interval) *restart_interval = P.restart_interval;
-    return IFHIP_OK;
-}
-
-// EXIF orientation of a JPEG as MozJpegDecoder reads it (codecs/mozjpeg_decoder_helpers.rs:107-202; the decoder saves
-// APP1 and APP2 markers up to 0xffff bytes, mozjpeg_decoder.rs:551-558): the FIRST saved marker whose data starts with
-// "Exif\0\0" decides -- shorter than 32 bytes: none; the TIFF header is looked for at offsets 0..15; IFD0's entries are
-// walked for tag 0x0112, rejected only if its type is not SHORT AND its count is not 1 (sic, `&&`), values above 8 are none.
-// Every read behind the data's end is the reference's io error, i.e. none.  *flag: -1 none, else 0..8.
-int ifhip_jpeg_exif_orientation(const uint8_t* d, size_t len, int* flag) {
-    if (!flag) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null out-pointer");
-    *flag = -1;
-    if (!d || len < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: not a JPEG (no SOI)");
-    size_t i = 2;
-    while (i + 4 <= len) {
-        if (d[i] != 0xFF) break;
-        while (i < len && d[i] == 0xFF) ++i;
-        if (i >= len) break;
-        const uint8_t m = d[i++];
-        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
-        if (m == 0xD9 || m == 0xDA || i + 2 > len) break;                       // jpeg_read_header stops at SOS
-        const size_t seg = (static_cast<size_t>(d[i]) << 8) | d[i + 1];
-        if (seg < 2 || i + seg > len) break;
-        const uint8_t* q = d + i + 2;
-        const size_t n = seg - 2;
-        i += seg;
-        if ((m != 0xE1 && m != 0xE2) || n < 6 || std::memcmp(q, "Exif\0\0", 6) != 0) continue;
-        if (n < 32) return IFHIP_OK;                                             // "EXIF too short"
-        size_t tiff = 16;
-        bool little = false;
-        for (size_t t = 0; t < 16 && tiff == 16; ++t) {
-            if (std::memcmp(q + t, "II\x2a\0", 4) == 0) { tiff = t; little = true; }
-            else if (std::memcmp(q + t, "MM\0\x2a", 4) == 0) { tiff = t; little = false; }
-        }
-        if (tiff == 16) return IFHIP_OK;
-        const uint8_t* r = q + tiff + 4;
-        const uint64_t rn = n - tiff - 4;
-        uint64_t pos = 0;
-        bool eof = false;
-        auto rd = [&](uint32_t bytes) -> uint32_t {
-            if (eof || pos + bytes > rn) { eof = true; return 0; }
-            uint32_t v = 0;
-            for (uint32_t k = 0; k < bytes; ++k) v |= static_cast<uint32_t>(r[pos + k]) << (little ? 8u * k : 8u * (bytes - 1u - k));
-            pos += bytes;
-            return v;
-        };
-        const uint32_t offset = rd(4);
-        if (eof) return IFHIP_OK;
-        pos = static_cast<uint64_t>(std::max<uint32_t>(4u, offset)) - 4u;
-        const uint32_t tags = rd(2);
-        for (uint32_t k = 0; k < tags && !eof; ++k) {
-            if (rd(2) == 0x112u && !eof) {
-                const uint32_t type = rd(2), count = rd(4);
-                if (eof || (type != 3u && count != 1u)) return IFHIP_OK;
-                const uint32_t v = rd(2);
-                if (!eof && v <= 8u) *flag = static_cast<int>(v);
-                return IFHIP_OK;
-            }
-            pos += 10;
-        }
-        return IFHIP_OK;
-    }
-    return IFHIP_OK;
-}
-
-// The embedded ICC profile (see include/imageflow_hip.h).  libjpeg's jpeg_read_icc_profile rule: APP2 markers whose data starts
-// with "ICC_PROFILE\0", then a 1-based sequence number and the marker count; every number must occur exactly once with the
-// same count.  A chunk set that breaks the rule -- inconsistent counts, a sequence number out of range or twice, a missing
-// chunk, nothing but empty chunks -- is NO profile to the reference (read_icc_profile returns None,
-// mozjpeg_decoder_helpers.rs:42-83: the frame is decoded without a transform) and kind 0 here; so is a GRAY profile on a
-// colour frame (mozjpeg_decoder.rs:391-395 -> SourceProfile::Srgb).
-int ifhip_jpeg_icc_profile_kind(const uint8_t* d, size_t len, int* kind) {
-    std::vector<uint8_t> icc;
-    return ifhip::jpeg_icc_profile(d, len, kind, &icc);
-}
-
-}  // extern "C"
-
-int ifhip::jpeg_icc_profile(const uint8_t* d, size_t len, int* kind, std::vector<uint8_t>* profile) {
-    if (!kind) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null out-pointer");
-    *kind = 0;
-    std::vector<uint8_t>& icc = *profile;
-    icc.clear();
-    if (!d || len < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: not a JPEG (no SOI)");
-    std::vector<std::pair<const uint8_t*, size_t>> chunk(256, {nullptr, 0});
-    uint32_t count = 0, seen = 0;
-    bool broken = false;
-    int frame_components = 0;
-    size_t i = 2;
-    while (i + 4 <= len) {
-        if (d[i] != 0xFF) break;
-        while (i < len && d[i] == 0xFF) ++i;
-        if (i >= len) break;
-        const uint8_t m = d[i++];
-        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
-        if (m == 0xD9 || m == 0xDA || i + 2 > len) break;
-        const size_t seg = (static_cast<size_t>(d[i]) << 8) | d[i + 1];
-        if (seg < 2 || i + seg > len) break;
-        const uint8_t* q = d + i + 2;
-        const size_t n = seg - 2;
-        i += seg;
-        if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC && n >= 6) frame_components = q[5];     // SOFn: P, Y, X, Nf
-        if (m != 0xE2 || n < 14 || std::memcmp(q, "ICC_PROFILE\0", 12) != 0) continue;
-        const uint32_t seq = q[12], num = q[13];
-        if (seq == 0 || num == 0 || seq > num || (count && num != count) || chunk[seq].first) { broken = true; continue; }
-        count = num;
-        chunk[seq] = {q + 14, n - 14};
-        ++seen;
-    }
-    if (!seen || broken || seen != count) return IFHIP_OK;              // no profile, or a chunk set the reference drops
-    for (uint32_t k = 1; k <= count; ++k) icc.insert(icc.end(), chunk[k].first, chunk[k].first + chunk[k].second);
-    if (icc.empty()) return IFHIP_OK;                                    // only empty markers: None
-    if (icc.size() >= 20 && std::memcmp(&icc[16], "GRAY", 4) == 0 && frame_components != 1) { icc.clear(); return IFHIP_OK; }   // -> SourceProfile::Srgb
-    *kind = icc_describes_srgb(icc.data(), icc.size()) ? 1 : 2;
-    return IFHIP_OK;
-}
-
 // One file, prepared on the host by whoever owns it: parsed, its scan un-stuffed, cut at the restart markers and packed as
 // big-endian words (every segment padded to 1 024 bits) in PINNED memory, its decode tables derived.  A batch is then
 // assembled from n of these with no further pass over the data: n asynchronous uploads.  (A service that runs one job per
@@ -1305,11 +879,9 @@ int ifhip::jpeg_icc_profile(const uint8_t* d, size_t len, int* kind, std::vector
 struct ifhip_jpeg_prepared {
     ParsedJpeg P;
     uint16_t qt[192];
-    std::vector<uint32_t> seg_mcu0, seg_mcus, seg_nsub, seg_first_word;      // per restart segment
-    std::vector<uint64_t> seg_bits;
+    ScanSegments seg;                                // per restart segment, and the sub-sequences of them all
     uint32_t* words = nullptr;                       // pinned (devmem cache)
     size_t n_words = 0;
-    uint32_t n_sub = 0;
     FastTabs ftabs, ptabs, ctabs;
     SearchTab stabs[6];
     uint32_t pool_limit = kPoolEntries;
@@ -1348,8 +920,8 @@ void give_prepared(ifhip_jpeg_prepared* p) {
     if (!p) return;
     p->drop_device_copy();                                               // (before the pinned source goes: the copy reads it)
     if (p->words) { (void)cached_host_free(p->words); p->words = nullptr; }
-    p->n_words = 0; p->n_sub = 0;
-    p->seg_mcu0.clear(); p->seg_mcus.clear(); p->seg_nsub.clear(); p->seg_first_word.clear(); p->seg_bits.clear();
+    p->n_words = 0;
+    p->seg.clear();
     PreparedPool& pool = prepared_pool();
     {
         std::lock_guard<std::mutex> lk(pool.mu);
@@ -1372,10 +944,9 @@ static int prepare_impl(ifhip_jpeg_prepared** out, const uint8_t* file, size_t l
     ParsedJpeg& P = R->P;
     P = ParsedJpeg();
     if (int rc = parse_jpeg(file, len, &P)) return rc;
-    std::memset(R->qt, 0, sizeof R->qt);
+    jpeg::report_quant_tables(P, P, R->qt);
     std::memset(&R->ftabs, 0, sizeof R->ftabs); std::memset(&R->ptabs, 0, sizeof R->ptabs); std::memset(&R->ctabs, 0, sizeof R->ctabs);   // (a recycled handle)
     std::memset(R->stabs, 0, sizeof R->stabs);
-    for (int c = 0; c < P.ncomp; ++c) std::memcpy(&R->qt[c * 64], P.qt[P.tq[c]], 128);
     R->pool_limit = test_hook_u32("ent_test_pool", kPoolEntries, kPoolEntries);
     derive_image_tables(P, &R->ftabs, R->stabs, R->pool_limit);
     derive_pair_tables(R->ftabs, P.ncomp, &R->ptabs);
@@ -1388,13 +959,11 @@ static int prepare_impl(ifhip_jpeg_prepared** out, const uint8_t* file, size_t l
     if (cached_host_malloc(&pinned, pinned_bytes) != 0)
         return fail(IFHIP_ALLOCATION_FAILED, "AllocationFailed: %zu bytes of pinned staging", pinned_bytes);
     R->words = static_cast<uint32_t*>(pinned);                           // (R owns it from here: every return below releases it)
-    uint64_t subs = 0;
-    const uint32_t mcu0 = unstuff_scan_packed(file, len, P, reinterpret_cast<uint8_t*>(pinned), pinned_bytes, &R->seg_mcu0, &R->seg_mcus, &R->seg_bits,
-                                              &R->seg_nsub, &R->seg_first_word, &subs);
+    const uint32_t mcu0 = unstuff_scan_packed(file, len, P, reinterpret_cast<uint8_t*>(pinned), pinned_bytes, &R->seg);
+    const uint64_t subs = R->seg.n_sub;
     if (subs * kSubBits + 4096 >= (1ull << 32)) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: more than 512 MB of scan data");
     if (mcu0 < total_mcus)
         return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: scan of image %u ends after %u of %u MCUs", index_for_messages, mcu0, total_mcus);
-    R->n_sub = static_cast<uint32_t>(subs);
     R->n_words = static_cast<size_t>(subs) * kSubWords;
     for (size_t q = 0; q < R->n_words; ++q) R->words[q] = __builtin_bswap32(R->words[q]);   // stream order bytes -> big-endian words
     *out = R.release();
@@ -1411,7 +980,7 @@ static int create_prepared_impl(ifhip_jpeg_entropy** out, ifhip_jpeg_prepared* c
     // with its own wait for the stream: most of the 1.9 ms a 16-file batch spent here, profiles/r5_abi_jobs_cliff_7_decode_batches.txt).
     size_t n_segs = 0;
     uint64_t subs_in_batch = 0;
-    for (uint32_t img = 0; img < n_images; ++img) { n_segs += prep[img]->seg_nsub.size(); subs_in_batch += prep[img]->n_sub; }
+    for (uint32_t img = 0; img < n_images; ++img) { n_segs += prep[img]->seg.nsub.size(); subs_in_batch += prep[img]->seg.n_sub; }
     if (subs_in_batch * kSubBits + 4096 >= (1ull << 32)) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: batch holds more than 512 MB of scan data");
     auto aligned = [](size_t v) { return (v + 255u) & ~static_cast<size_t>(255u); };
     const size_t o_segs = 0, o_sub = aligned(o_segs + std::max<size_t>(n_segs, 1) * sizeof(Segment)),
@@ -1448,15 +1017,15 @@ static int create_prepared_impl(ifhip_jpeg_entropy** out, ifhip_jpeg_prepared* c
         std::memcpy(&ftabs[img], &R.ftabs, sizeof(FastTabs)); std::memcpy(&ptabs[img], &R.ptabs, sizeof(FastTabs)); std::memcpy(&ctabs[img], &R.ctabs, sizeof(FastTabs));
         std::memcpy(&stabs[static_cast<size_t>(img) * 6u], R.stabs, sizeof R.stabs);
         first_sub_of[img] = static_cast<uint32_t>(total_subs);
-        for (size_t k = 0; k < R.seg_nsub.size(); ++k) {
+        for (size_t k = 0; k < R.seg.nsub.size(); ++k) {
             Segment sg;
             std::memset(&sg, 0, sizeof sg);
             sg.image = img;
-            sg.first_mcu = R.seg_mcu0[k];
-            sg.n_blocks = R.seg_mcus[k] * P.blocks_per_mcu;
+            sg.first_mcu = R.seg.mcu0[k];
+            sg.n_blocks = R.seg.mcus[k] * P.blocks_per_mcu;
             sg.first_sub = static_cast<uint32_t>(total_subs);
-            sg.n_sub = R.seg_nsub[k];
-            sg.bit_end = static_cast<uint32_t>(total_subs * kSubBits + R.seg_bits[k]);
+            sg.n_sub = R.seg.nsub[k];
+            sg.bit_end = static_cast<uint32_t>(total_subs * kSubBits + R.seg.bits[k]);
             for (uint32_t q = 0; q < sg.n_sub; ++q) sub_seg[total_subs + q] = static_cast<uint32_t>(seg_count);
             total_subs += sg.n_sub;
             segs[seg_count++] = sg;
@@ -1471,7 +1040,7 @@ static int create_prepared_impl(ifhip_jpeg_entropy** out, ifhip_jpeg_prepared* c
         for (uint32_t w = 0; w < n_wg; ++w) {
             const uint64_t s0 = static_cast<uint64_t>(w) * kOwnSubs;
             while (img + 1u < n_images && first_sub_of[img + 1u] <= s0) ++img;
-            key[w] = prep[img]->n_sub;
+            key[w] = static_cast<uint32_t>(prep[img]->seg.n_sub);
             wg_order[w] = w;
         }
         std::stable_sort(wg_order, wg_order + n_wg, [&](uint32_t x, uint32_t y) { return key[x] < key[y]; });
@@ -1625,13 +1194,7 @@ int ifhip_jpeg_prepared_upload(ifhip_jpeg_prepared* p, void* hip_stream) {
 }
 int ifhip_jpeg_prepared_info(const ifhip_jpeg_prepared* p, uint32_t* width, uint32_t* height, int* n_components, uint8_t* h_samp3, uint8_t* v_samp3) {
     if (!p) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null handle");
-    if (width) *width = p->P.width;
-    if (height) *height = p->P.height;
-    if (n_components) *n_components = p->P.ncomp;
-    for (int c = 0; c < 3; ++c) {
-        if (h_samp3) h_samp3[c] = c < p->P.ncomp ? p->P.hs[c] : 0;
-        if (v_samp3) v_samp3[c] = c < p->P.ncomp ? p->P.vs[c] : 0;
-    }
+    jpeg::report_frame(p->P, p->P, width, height, n_components, h_samp3, v_samp3);
     return IFHIP_OK;
 }
 int ifhip_jpeg_entropy_create_prepared(ifhip_jpeg_entropy** out, ifhip_jpeg_prepared* const* prepared, uint32_t n_images) {
@@ -1747,27 +1310,24 @@ int ifhip_jpeg_debug_scan_report(const uint8_t* jpeg, size_t len, ifhip_jpeg_sca
         for (int c = 0; c < P.ncomp; ++c)
             for (uint32_t b = 0; b < static_cast<uint32_t>(P.hs[c]) * P.vs[c]; ++b, ++k) g.kcomp_packed |= static_cast<uint32_t>(c) << (2u * k);
         std::vector<std::vector<uint8_t>> seg_bytes;
-        std::vector<uint32_t> seg_mcu0, seg_mcus;
-        const uint32_t covered = unstuff_scan(jpeg, len, P, &seg_bytes, &seg_mcu0, &seg_mcus);
+        ScanSegments seg, packed_seg;
+        const uint32_t covered = unstuff_scan(jpeg, len, P, &seg_bytes, &seg);
         {   // the product's un-stuffer (straight into the staging block) against the walk above: same segments, same bytes, and
             // -- under the sanitizer build, tools/sanitize -- never a byte beyond the bound the staging block is sized by
             const size_t bound = packed_scan_bound(len, P);
             std::unique_ptr<uint8_t[]> packed(new uint8_t[bound]);
-            std::vector<uint32_t> p_mcu0, p_mcus, p_nsub, p_first;
-            std::vector<uint64_t> p_bits;
-            uint64_t p_subs = 0;
-            const uint32_t p_covered = unstuff_scan_packed(jpeg, len, P, packed.get(), bound, &p_mcu0, &p_mcus, &p_bits, &p_nsub, &p_first, &p_subs);
-            bool same = p_covered == covered && p_mcu0 == seg_mcu0 && p_mcus == seg_mcus && p_bits.size() == seg_bytes.size();
+            const uint32_t p_covered = unstuff_scan_packed(jpeg, len, P, packed.get(), bound, &packed_seg);
+            bool same = p_covered == covered && packed_seg.mcu0 == seg.mcu0 && packed_seg.mcus == seg.mcus && packed_seg.bits.size() == seg_bytes.size();
             for (size_t k = 0; same && k < seg_bytes.size(); ++k)
-                same = p_bits[k] == seg_bytes[k].size() * 8u &&
-                       std::memcmp(packed.get() + static_cast<size_t>(p_first[k]) * 4u, seg_bytes[k].data(), seg_bytes[k].size()) == 0;
+                same = packed_seg.bits[k] == seg_bytes[k].size() * 8u &&
+                       std::memcmp(packed.get() + static_cast<size_t>(packed_seg.first_word[k]) * 4u, seg_bytes[k].data(), seg_bytes[k].size()) == 0;
             if (!same) return fail(IFHIP_INVALID_STATE, "InvalidState: the packed un-stuffer disagrees with the per-segment walk");
         }
         out->segments = static_cast<uint32_t>(seg_bytes.size());
         out->scan_complete = covered == P.mcus_w * P.mcus_h ? 1u : 0u;
         for (size_t sgi = 0; sgi < seg_bytes.size(); ++sgi) {
             const HostStream in{seg_bytes[sgi]};
-            const uint64_t bit_end = static_cast<uint64_t>(seg_bytes[sgi].size()) * 8u, want = static_cast<uint64_t>(seg_mcus[sgi]) * P.blocks_per_mcu;
+            const uint64_t bit_end = static_cast<uint64_t>(seg_bytes[sgi].size()) * 8u, want = static_cast<uint64_t>(seg.mcus[sgi]) * P.blocks_per_mcu;
             const uint64_t n_sub = std::max<uint64_t>(1u, (bit_end + kSubBits - 1u) / kSubBits);
             out->sub_sequences += static_cast<uint32_t>(n_sub);
             HostCounts plain, paired, counted;
@@ -1803,16 +1363,7 @@ int ifhip_jpeg_debug_scan_report(const uint8_t* jpeg, size_t len, ifhip_jpeg_sca
 int ifhip_jpeg_entropy_info(const ifhip_jpeg_entropy* e, uint32_t* width, uint32_t* height, int* n_components, uint8_t* h_samp3,
                             uint8_t* v_samp3, uint32_t* blocks_w3, uint32_t* blocks_h3, uint32_t* n_subsequences, uint32_t* n_segments) {
     if (!e) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null handle");
-    const ParsedJpeg& F = e->first;
-    if (width) *width = F.width;
-    if (height) *height = F.height;
-    if (n_components) *n_components = F.ncomp;
-    for (int c = 0; c < 3; ++c) {
-        if (h_samp3) h_samp3[c] = c < F.ncomp ? F.hs[c] : 0;
-        if (v_samp3) v_samp3[c] = c < F.ncomp ? F.vs[c] : 0;
-        if (blocks_w3) blocks_w3[c] = c < F.ncomp ? F.bw[c] : 0;
-        if (blocks_h3) blocks_h3[c] = c < F.ncomp ? F.bh[c] : 0;
-    }
+    jpeg::report_frame(e->first, e->first, width, height, n_components, h_samp3, v_samp3, blocks_w3, blocks_h3);
     if (n_subsequences) *n_subsequences = e->a.n_sub;
     if (n_segments) *n_segments = e->a.n_seg;
     return IFHIP_OK;

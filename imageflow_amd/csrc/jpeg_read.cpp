@@ -16,22 +16,22 @@
 #include <vector>
 
 #include "common.hpp"
+#include "jpeg_markers.hpp"
 
 namespace ifhip {
 namespace {
 
-const uint8_t kZig[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48,
-                          41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22,
-                          15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-
+constexpr auto& kZig = jpeg::kNaturalOrder;
 struct HuffTab {                       // jdhuff.c jpeg_make_d_derived_tbl: canonical codes by length
     bool present = false;
-    uint8_t bits[17] = {0};
-    uint8_t vals[256] = {0};
+    const uint8_t* vals = nullptr;     // the specification's, in the frame
     int32_t maxcode[18];               // largest code of length l, -1 if none
     int32_t valoff[17];                // huffval index of the first code of length l minus that code
     uint8_t look_len[256], look_sym[256];      // 8-bit lookahead: code length (0: longer than 8) and symbol
-    void derive() {
+    void derive(const jpeg::HuffSpec& h) {
+        const uint8_t* bits = h.bits;
+        present = true;
+        vals = h.vals;
         int32_t code = 0;
         int k = 0;
         std::memset(look_len, 0, sizeof look_len);
@@ -50,19 +50,9 @@ struct HuffTab {                       // jdhuff.c jpeg_make_d_derived_tbl: cano
     }
 };
 
-struct Frame {
-    uint32_t width = 0, height = 0;
-    int ncomp = 0;
-    bool progressive = false;
-    uint8_t comp_id[3] = {0, 0, 0}, hs[3] = {1, 1, 1}, vs[3] = {1, 1, 1}, tq[3] = {0, 0, 0};
-    uint32_t hmax = 1, vmax = 1, mcus_w = 0, mcus_h = 0;
-    uint32_t bw[3] = {0, 0, 0}, bh[3] = {0, 0, 0};            // MCU-padded plane sizes in blocks
-    uint32_t wb[3] = {0, 0, 0}, hb[3] = {0, 0, 0};            // jdinput.c width_in_blocks / height_in_blocks (what a non-interleaved scan covers)
-    uint16_t qt[4][64];
-    bool qt_present[4] = {false, false, false, false};
+struct Frame : jpeg::FrameHeader, jpeg::Geometry, jpeg::Tables {
     uint16_t qt_latched[3][64];                               // jdinput.c latch_quant_tables: a component's table as it stood at its FIRST scan
     bool latched[3] = {false, false, false};
-    int adobe_transform = -1;
 };
 
 struct BitReader {                     // jdhuff.c fill_bit_buffer: bytes with FF00 un-stuffed, zeros behind a marker
@@ -111,102 +101,57 @@ struct ScanComp { int ci, td, ta; };
 
 }  // namespace
 
-// width_in_blocks etc. of a frame (jdinput.c initial_setup / per_scan_setup)
+// The frame checks and the geometry of a frame whose header has been read: at the SOF, and again at an Adobe marker behind it
+// (parse_jpeg asks the same questions behind the scan header, RGB-coded first: jpeg_parse.cpp).
 static int finish_frame(Frame& F) {
-    if (F.ncomp != 1 && F.ncomp != 3) return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: %d-component JPEG", F.ncomp);
-    F.hmax = F.vmax = 1;
-    for (int c = 0; c < F.ncomp; ++c) {
-        if (F.hs[c] < 1 || F.hs[c] > 2 || F.vs[c] < 1 || F.vs[c] > 2)
-            return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: sampling factor %dx%d", F.hs[c], F.vs[c]);
-        F.hmax = std::max<uint32_t>(F.hmax, F.hs[c]); F.vmax = std::max<uint32_t>(F.vmax, F.vs[c]);
-    }
-    if (F.ncomp == 1) { F.hs[0] = F.vs[0] = 1; F.hmax = F.vmax = 1; }
-    if (F.ncomp == 3 && (F.hs[0] != F.hmax || F.vs[0] != F.vmax || F.hs[1] != 1 || F.vs[1] != 1 || F.hs[2] != 1 || F.vs[2] != 1))
-        return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: sampling %dx%d,%dx%d,%dx%d (chroma must be 1x1)", F.hs[0], F.vs[0],
-                    F.hs[1], F.vs[1], F.hs[2], F.vs[2]);
-    if (F.ncomp == 3 && (F.adobe_transform == 0 || (F.adobe_transform < 0 && F.comp_id[0] == 'R' && F.comp_id[1] == 'G' && F.comp_id[2] == 'B')))
-        return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: RGB-coded JPEG (no YCbCr transform)");
-    F.mcus_w = (F.width + 8 * F.hmax - 1) / (8 * F.hmax);
-    F.mcus_h = (F.height + 8 * F.vmax - 1) / (8 * F.vmax);
-    for (int c = 0; c < F.ncomp; ++c) {
-        F.bw[c] = F.mcus_w * F.hs[c]; F.bh[c] = F.mcus_h * F.vs[c];
-        F.wb[c] = (static_cast<uint64_t>(F.width) * F.hs[c] + 8ull * F.hmax - 1) / (8ull * F.hmax);
-        F.hb[c] = (static_cast<uint64_t>(F.height) * F.vs[c] + 8ull * F.vmax - 1) / (8ull * F.vmax);
-    }
+    for (int c = 0; c < F.ncomp; ++c)
+        if (!jpeg::factors_in_range(F, c)) return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: sampling factor %dx%d", F.hs[c], F.vs[c]);
+    jpeg::frame_geometry(&F, &F);
+    if (!jpeg::chroma_is_1x1(F, F))
+        return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: sampling %dx%d,%dx%d,%dx%d (chroma must be 1x1)", F.hs[0], F.vs[0], F.hs[1], F.vs[1], F.hs[2], F.vs[2]);
+    if (jpeg::rgb_coded(F, F.adobe_transform)) return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: RGB-coded JPEG (no YCbCr transform)");
     return IFHIP_OK;
 }
 
 // One pass over the markers.  coef == nullptr: stop at the first SOS (frame facts only).
 static int read_jpeg(const uint8_t* d, size_t len, Frame* out, int16_t* const coef[3]) {
     Frame& F = *out;
-    if (!d || len < 4 || d[0] != 0xFF || d[1] != 0xD8) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: not a JPEG (no SOI)");
-    HuffTab dc[4], ac[4];
-    uint32_t restart_interval = 0;
+    if (!jpeg::has_soi(d, len)) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: not a JPEG (no SOI)");
+    HuffTab dc[4], ac[4];                                                 // derived from F.dc / F.ac as they arrive
     bool have_sof = false, any_scan = false;
     // (jdphuff.c's coef_bits bookkeeping only WARNS about scripts that send bits out of order -- JWRN_BOGUS_PROGRESSION -- and
     // decodes them anyway; there is no warning channel here, so such scans are decoded as libjpeg decodes them)
     size_t i = 2;
-    while (i + 4 <= len) {
-        if (d[i] != 0xFF) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: marker expected at byte %zu", i);
-        while (i < len && d[i] == 0xFF) ++i;
-        if (i >= len) break;
-        const uint8_t m = d[i++];
-        if (m == 0xD8 || (m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
-        if (m == 0xD9) break;
-        if (i + 2 > len) break;
-        const size_t seg = (static_cast<size_t>(d[i]) << 8) | d[i + 1];
-        if (seg < 2 || i + seg > len) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: truncated marker segment FF%02X", m);
-        const uint8_t* q = d + i + 2;
-        const size_t n = seg - 2;
-        if (m == 0xDB) {
-            size_t k = 0;
-            while (k < n) {
-                const int pq = q[k] >> 4, t = q[k] & 15;
-                ++k;
-                if (t > 3 || k + (pq ? 128u : 64u) > n) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad DQT");
-                for (int z = 0; z < 64; ++z) {
-                    F.qt[t][kZig[z]] = pq ? static_cast<uint16_t>((q[k] << 8) | q[k + 1]) : q[k];
-                    k += pq ? 2 : 1;
-                }
-                F.qt_present[t] = true;
+    jpeg::Segment seg;
+    for (jpeg::Step step; (step = jpeg::next_segment(d, len, &i, &seg)) != jpeg::Step::End;) {
+        if (step == jpeg::Step::NotAMarker) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: marker expected at byte %zu", i);
+        if (step == jpeg::Step::Truncated) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: truncated marker segment FF%02X", seg.marker);
+        const uint8_t m = seg.marker, *q = seg.data;
+        const size_t n = seg.size;
+        if (m == jpeg::kDQT) {
+            if (!jpeg::read_dqt(seg, F.qt, F.qt_present)) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad DQT");
+        } else if (m == jpeg::kDHT) {
+            uint32_t defined = 0;
+            if (!jpeg::read_dht(seg, F.dc, F.ac, &defined)) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad DHT");
+            for (int t = 0; t < 4; ++t) {
+                if (defined & (1u << t)) dc[t].derive(F.dc[t]);
+                if (defined & (16u << t)) ac[t].derive(F.ac[t]);
             }
-        } else if (m == 0xC4) {
-            size_t k = 0;
-            while (k + 17 <= n) {
-                const int tc = q[k] >> 4, th = q[k] & 15;
-                if (tc > 1 || th > 3) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad DHT");
-                HuffTab& h = tc ? ac[th] : dc[th];
-                size_t total = 0;
-                h.bits[0] = 0;
-                for (int l = 1; l <= 16; ++l) { h.bits[l] = q[k + l]; total += q[k + l]; }
-                k += 17;
-                if (total > 256 || k + total > n) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad DHT");
-                std::memset(h.vals, 0, sizeof h.vals);
-                std::memcpy(h.vals, q + k, total);
-                k += total;
-                h.present = true;
-                h.derive();
-            }
-        } else if (m == 0xC0 || m == 0xC1 || m == 0xC2) {
+        } else if (m == 0xC0 || m == 0xC1 || m == 0xC2) {                 // one frame header, judged where it stands
             if (have_sof) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: two frame headers");
-            if (n < 6 || q[0] != 8) return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: %d-bit JPEG", n ? q[0] : 0);
-            F.progressive = m == 0xC2;
-            F.height = (q[1] << 8) | q[2];
-            F.width = (q[3] << 8) | q[4];
-            F.ncomp = q[5];
-            if (F.ncomp != 1 && F.ncomp != 3) return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: %d-component JPEG", F.ncomp);
-            if (n < 6u + 3u * F.ncomp || F.width == 0 || F.height == 0) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad SOF");
-            for (int c = 0; c < F.ncomp; ++c) { F.comp_id[c] = q[6 + 3 * c]; F.hs[c] = q[7 + 3 * c] >> 4; F.vs[c] = q[7 + 3 * c] & 15; F.tq[c] = q[8 + 3 * c] & 3; }
+            const jpeg::Sof sof = jpeg::read_sof(seg, &F);
+            if (sof == jpeg::Sof::Precision) return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: %d-bit JPEG", F.precision);
+            if (sof == jpeg::Sof::ComponentCount) return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: %d-component JPEG", F.ncomp);
+            if (sof == jpeg::Sof::Short || F.width == 0 || F.height == 0) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad SOF");
             if (int rc = finish_frame(F)) return rc;
             have_sof = true;
-        } else if (m >= 0xC3 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
+        } else if (jpeg::is_sof(m)) {
             return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "MethodNotImplemented: JPEG process SOF%d (Huffman sequential and progressive only)", m - 0xC0);
-        } else if (m == 0xDD) {
-            if (n >= 2) restart_interval = (q[0] << 8) | q[1];
-        } else if (m == 0xEE && n >= 12 && std::memcmp(q, "Adobe", 5) == 0) {
-            F.adobe_transform = q[11];
+        } else if (m == jpeg::kDRI) {
+            jpeg::read_dri(seg, &F.restart_interval);
+        } else if (jpeg::read_adobe(seg, &F.adobe_transform)) {
             if (have_sof) if (int rc = finish_frame(F)) return rc;
-        } else if (m == 0xDA) {
+        } else if (m == jpeg::kSOS) {
             if (!have_sof) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: SOS before SOF");
             if (!coef) return IFHIP_OK;                                   // frame facts only
             if (n < 1) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad SOS");
@@ -221,7 +166,7 @@ static int read_jpeg(const uint8_t* d, size_t len, Frame* out, int16_t* const co
                 if (sc[s].td > 3 || sc[s].ta > 3) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad SOS");
             }
             const int Ss = q[1 + 2 * ns], Se = q[2 + 2 * ns], Ah = q[3 + 2 * ns] >> 4, Al = q[3 + 2 * ns] & 15;
-            if (F.progressive) {                                          // jdphuff.c start_pass_phuff_decoder's checks
+            if (F.progressive()) {                                          // jdphuff.c start_pass_phuff_decoder's checks
                 const bool dc_scan = Ss == 0;
                 if ((dc_scan && Se != 0) || (!dc_scan && (Se < Ss || Se > 63 || ns != 1)) || Al > 13 || (Ah != 0 && Ah - 1 != Al))
                     return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: bad progressive scan parameters Ss=%d Se=%d Ah=%d Al=%d", Ss, Se, Ah, Al);
@@ -236,15 +181,16 @@ static int read_jpeg(const uint8_t* d, size_t len, Frame* out, int16_t* const co
                 F.latched[c] = true;
             }
             for (int s = 0; s < ns; ++s) {
-                const bool need_dc = !F.progressive || (Ss == 0 && Ah == 0), need_ac = !F.progressive || Ss != 0;
+                const bool need_dc = !F.progressive() || (Ss == 0 && Ah == 0), need_ac = !F.progressive() || Ss != 0;
                 if ((need_dc && !dc[sc[s].td].present) || (need_ac && !ac[sc[s].ta].present))
                     return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: missing Huffman table");
             }
             // per-scan geometry (jdinput.c per_scan_setup): one component -> its own block raster; several -> MCUs
             const bool interleaved = ns > 1;
             const uint32_t mcus_w = interleaved ? F.mcus_w : F.wb[sc[0].ci], mcus_h = interleaved ? F.mcus_h : F.hb[sc[0].ci];
-            BitReader br{d, len, i + seg};
+            BitReader br{d, len, i};
             int32_t last_dc[3] = {0, 0, 0};
+            const uint32_t restart_interval = F.restart_interval;
             uint32_t eobrun = 0, restarts_left = restart_interval;
             const uint64_t total_mcus = static_cast<uint64_t>(mcus_w) * mcus_h;
             for (uint64_t mi = 0; mi < total_mcus; ++mi) {
@@ -270,7 +216,7 @@ static int read_jpeg(const uint8_t* d, size_t len, Frame* out, int16_t* const co
                             const uint32_t bx = mx * nh + dx, by = my * nv + dy;
                             int16_t* blk = coef[ci] + (static_cast<size_t>(by) * F.bw[ci] + bx) * 64u;
                             int sym = 0;
-                            if (!F.progressive) {                         // jdhuff.c decode_mcu
+                            if (!F.progressive()) {                         // jdhuff.c decode_mcu
                                 if (decode_symbol(br, dc[sc[s].td], &sym)) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: corrupt entropy-coded data");
                                 int32_t diff = 0;
                                 if (sym) { if (sym > 15) sym = 15; diff = extend(br.get(sym), sym); }
@@ -351,9 +297,7 @@ static int read_jpeg(const uint8_t* d, size_t len, Frame* out, int16_t* const co
             size_t p = br.pos;
             while (p + 1 < len && !(d[p] == 0xFF && d[p + 1] != 0x00 && d[p + 1] != 0xFF && !(d[p + 1] >= 0xD0 && d[p + 1] <= 0xD7))) ++p;
             i = p;
-            continue;
         }
-        i += seg;
     }
     if (!have_sof) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: no frame found");
     if (coef && !any_scan) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: no scan found");
@@ -371,20 +315,9 @@ int ifhip_jpeg_frame_info(const uint8_t* jpeg, size_t len, uint32_t* width, uint
     try {
         Frame F;
         if (int rc = read_jpeg(jpeg, len, &F, nullptr)) return rc;
-        if (width) *width = F.width;
-        if (height) *height = F.height;
-        if (n_components) *n_components = F.ncomp;
-        if (progressive) *progressive = F.progressive ? 1 : 0;
-        for (int c = 0; c < 3; ++c) {
-            if (h_samp3) h_samp3[c] = c < F.ncomp ? F.hs[c] : 0;
-            if (v_samp3) v_samp3[c] = c < F.ncomp ? F.vs[c] : 0;
-            if (blocks_w3) blocks_w3[c] = c < F.ncomp ? F.bw[c] : 0;
-            if (blocks_h3) blocks_h3[c] = c < F.ncomp ? F.bh[c] : 0;
-            if (qt3x64) {
-                if (c < F.ncomp && F.qt_present[F.tq[c]]) std::memcpy(qt3x64 + 64 * c, F.qt[F.tq[c]], 128);
-                else std::memset(qt3x64 + 64 * c, 0, 128);
-            }
-        }
+        jpeg::report_frame(F, F, width, height, n_components, h_samp3, v_samp3, blocks_w3, blocks_h3);
+        jpeg::report_quant_tables(F, F, qt3x64);
+        if (progressive) *progressive = F.progressive() ? 1 : 0;
         return IFHIP_OK;
     } catch (const std::exception& ex) { return fail(IFHIP_INVALID_STATE, "InvalidState: %s", ex.what()); }
 }

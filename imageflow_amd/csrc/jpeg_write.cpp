@@ -17,12 +17,11 @@
 #endif
 
 #include "common.hpp"
+#include "jpeg_markers.hpp"
 
 namespace {
 
-const uint8_t kZigzag[64] = {0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48,
-                             41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22,
-                             15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+constexpr auto& kZigzag = ifhip::jpeg::kNaturalOrder;
 
 // ITU T.81 Annex K.1 / K.2 (natural order) and K.3 (Huffman specifications), as jcparam.c / jstdhuff.c carry them
 const uint8_t kStdLumaQ[64] = {16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,

@@ -10,7 +10,7 @@ with 0..3 fill bytes before each RSTn, pad bits of ones, zeros or noise, blocks 
 of ZRLs, a ZRL directly before an EOB.
 
 `stats` records what a file contains, so that coverage is asserted and not hoped for (tests/test_jpeg_gen.py).  1 024 bits
-is the decoder's sub-sequence (csrc/jpeg_entropy.hip kSubBits); its restart segments start on that grid, and `seg_first_sub`
+is the decoder's sub-sequence (csrc/jpeg_parse.hpp kSubBits); its restart segments start on that grid, and `seg_first_sub`
 follows that rule.
 
     names() / entry(name)   the corpus: fixed seeds, every file rebuilt from its seed, cached per process

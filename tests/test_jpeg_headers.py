@@ -1,6 +1,6 @@
-"""Host-only part of the entropy stage: ifhip_jpeg_parse_headers (csrc/jpeg_entropy.hip) against the oracle's parser on
-every committed file, and the oracle's serial Huffman decoder against libjpeg-turbo (Pillow) on the restart-interval /
-optimised-table fixtures that the GPU decoder is checked with."""
+"""Host-only part of the entropy stage: ifhip_jpeg_parse_headers (csrc/jpeg_parse.cpp, on the marker walk of
+csrc/jpeg_markers.hpp) against the oracle's parser on every committed file, and the oracle's serial Huffman decoder against
+libjpeg-turbo (Pillow) on the restart-interval / optimised-table fixtures that the GPU decoder is checked with."""
 import io
 import os
 
