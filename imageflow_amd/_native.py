@@ -50,6 +50,9 @@ def lib():
     L.ifhip_apply_matte.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int, C.c_uint32]
     L.ifhip_apply_matte_batch_device.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.c_uint32,
                                                  C.c_uint32, C.c_int, C.c_uint32, C.c_void_p]
+    if hasattr(L, "ifhip_set_thread_stream"):
+        L.ifhip_set_thread_stream.argtypes = [C.c_void_p]
+        L.ifhip_set_thread_stream.restype = None
     _lib = L
     if not hasattr(L, "ifhip_debug_set"):          # (a library build of an earlier round, loaded through IFHIP_LIB for an A/B run)
         return L
@@ -73,6 +76,13 @@ def set_cu_budget(compute_units):
     L = lib()
     L.ifhip_set_cu_budget.argtypes = [C.c_uint32]
     check(L.ifhip_set_cu_budget(int(compute_units)))
+
+
+def set_thread_stream(stream):
+    """ifhip_set_thread_stream: the HIP stream on which THIS THREAD's create calls (plans, stages, entropy handles) upload
+    and clear what they need.  stream: a torch.cuda.Stream, a raw hipStream_t as int, or None for the null stream."""
+    handle = getattr(stream, "cuda_stream", stream)
+    lib().ifhip_set_thread_stream(C.c_void_p(None if handle is None else int(handle)))
 
 
 def trim_cache(keep_device_bytes=0, keep_host_bytes=0):

@@ -11,7 +11,15 @@
  *     available from ifhip_last_error_message();
  *   - a bitmap is (pointer, w, h, stride-in-bytes), BGRA8, rows padded as graphics/bitmaps.rs:712-740;
  *   - colours are Color32 0xAARRGGBB whose little-endian bytes are B,G,R,A (imageflow_helpers/src/colors.rs:77-117);
- *   - `*_device` variants take pointers into HBM and a hipStream_t (as void*); they enqueue and return.
+ *   - `*_device` variants take pointers into HBM and a hipStream_t (as void*).  Every read and write of such a call is
+ *     ordered on that stream: the producer of its inputs may be queued in front of it and the consumer of its outputs behind
+ *     it on the same stream, with no host wait in between (tests/test_gpu_stream_order.py holds every entry point to this
+ *     with inputs that arrive late).  Most calls enqueue and return.  These wait on the host for what is already queued on
+ *     hip_stream: the file decoders ifhip_{png,webp,gif}_decode_batch_device and ifhip_gif_decode_frames_device (the files go
+ *     up on hip_stream and the call waits for that copy before its first launch), ifhip_gif_encode_animation_device (its two
+ *     host arrays likewise), ifhip_jpeg_entropy_decode_device (it synchronises the stream) and the first call of a JPEG
+ *     encode stage at a quality it has not coded yet (the marker segments go up from the stage's one pinned copy, which the
+ *     call before may still be sending); DESIGN.md, "Stream contract".
  *     The non-device variants take host memory, are synchronous, and are the drop-in for the Rust callers.
  *   - there is NO CPU fallback: without a usable gfx950 device every compute entry point fails with
  *     IFHIP_GPU_UNAVAILABLE.

@@ -131,7 +131,9 @@ def own_frames(d, files, extra_stride, fill):
 @pytest.mark.parametrize("name", DECODERS)
 def test_one_batch_on_the_default_stream_a_side_stream_and_into_supplied_frames(name):
     """Two good files around one whose container does not parse.  The side-stream run is a smoke test: it shows that the
-    hand-off is ordered on the caller's stream and does not deadlock; it does not prove the absence of a race."""
+    hand-off is ordered on the caller's stream and does not deadlock; it does not prove the absence of a race.
+    tests/test_gpu_stream_order.py does, for every decoder: the 0xA5 pre-fill of the frames arrives late on a stream that is
+    held up on purpose, so a decode that ran ahead of that stream is overwritten."""
     d = decoder(name)
     files = [d.good[0][0], NOT_A_FILE, d.good[1][0]]
     wants = [d.good[0][1], None, d.good[1][1]]

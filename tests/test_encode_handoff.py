@@ -263,7 +263,8 @@ def batch_files(name, w, h, stride):
 @pytest.mark.parametrize("name", CODERS)
 def test_one_batch_on_the_default_stream_a_side_stream_and_into_supplied_buffers(name):
     """The side-stream run is a smoke test: it shows that the hand-off is ordered on the caller's stream and does not deadlock;
-    it does not prove the absence of a race."""
+    it does not prove the absence of a race.  tests/test_gpu_stream_order.py does, for every coder: the frames arrive late on
+    a stream that is held up on purpose, and a launch that left that stream would code the decoy."""
     for w, h, stride in GEOMETRIES[name]:
         rows, files = batch_files(name, w, h, stride)
         assert all(files), (name, w, h)

@@ -221,3 +221,11 @@ def test_frame_checks_come_before_the_device_check():
         assert call() == INVALID, name
     for name, call in _bitmap_calls(p_in, p_out, H * STRIDE, STRIDE).items():
         assert call() in (int(ErrorKind.GpuUnavailable), int(ErrorKind.GpuError)), name
+
+
+def test_set_thread_stream_is_bound_and_accepts_none():
+    """_native.set_thread_stream exists, takes None (the null stream) and a raw handle, and needs no device: it only notes
+    the stream for this thread's later create calls."""
+    assert _native.set_thread_stream(None) is None
+    _native.set_thread_stream(0)
+    _native.set_thread_stream(None)
