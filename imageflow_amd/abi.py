@@ -72,6 +72,8 @@ def _bind():
     L.ifhip_shim_context_device.restype = C.c_int
     L.ifhip_shim_context_set_color_management.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_color_management.restype = C.c_bool
+    L.ifhip_shim_context_set_webp_lossy_decoder.argtypes = [vp, C.c_int]
+    L.ifhip_shim_context_set_webp_lossy_decoder.restype = C.c_bool
     L.ifhip_shim_context_set_gif_encoder.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_gif_encoder.restype = C.c_bool
     L.ifhip_shim_context_set_gif_animation.argtypes = [vp, C.c_int]
@@ -165,6 +167,12 @@ class Context:
         behind its decode, instead of refusing the job (the decoder command "convert_color_profile" does it for one input;
         "discard_color_profile" wins over both)."""
         return self.L.ifhip_shim_context_set_color_management(self.p, 1 if on else 0)
+
+    def set_webp_lossy_decoder(self, on):
+        """EXTENSION, off by default: lossy WebP inputs (`VP8 `, with or without `ALPH`) are decoded on the device to exactly
+        libwebp's pixels -- `decode`, `watermark`, `command_string` and v1/get_image_info take them -- instead of being
+        ImageTypeNotSupported."""
+        return self.L.ifhip_shim_context_set_webp_lossy_decoder(self.p, 1 if on else 0)
 
     def set_gif_encoder(self, on):
         """EXTENSION, off by default: `encode` with the preset "gif" writes a GIF89a file on the device (image/gif) instead of

@@ -50,6 +50,7 @@
 #include "color_profile.hpp"   // a colour profile as a conversion plan (color_profile.cpp; the kernel: color_profile.hip)
 #include "png_read.hpp"         // the PNG chunk walk and the device decode of a walked file (png_read.cpp, png_decode.hip)
 #include "gif_read.hpp"         // the container walk and the device decode of a GIF (gif_read.cpp, gif_decode.hip)
+#include "vp8_read.hpp"         // the host stage and the device decode of a lossy WebP (vp8_read.cpp, vp8_decode.hip)
 #include "webp_read.hpp"        // the RIFF walk, the prepare and the device decode of a lossless WebP (webp_read.cpp, webp_decode.hip)
 #include "layout.hpp"           // imageflow_riapi's constraint layout (constrain / watermark)
 #include "querystring.hpp"      // imageflow_riapi's querystring: Instructions, their expansion into nodes (command_string)
@@ -551,6 +552,7 @@ struct imageflow_context {
     std::atomic<bool> device_jpeg_options{false};        // EXTENSION ifhip_shim_context_set_device_jpeg_options: progressive / optimised tables coded on the device
     std::atomic<bool> gif_animation{false};              // EXTENSION ifhip_shim_context_set_gif_animation: animated GIFs run once per frame into one file
     std::atomic<bool> gif_encoder{false};                // EXTENSION ifhip_shim_context_set_gif_encoder: the "gif" preset writes a GIF on the device
+    std::atomic<bool> webp_lossy_decoder{false};         // EXTENSION ifhip_shim_context_set_webp_lossy_decoder: lossy WebP inputs are decoded on the device
     std::atomic<bool> color_management{false};           // EXTENSION ifhip_shim_context_set_color_management: every input is converted to sRGB
     bool cancellation_requested() {
         if (cancel.load(std::memory_order_relaxed)) return true;
@@ -898,8 +900,10 @@ struct Job {
         return in.in_len >= 13 && (std::memcmp(in.in, "GIF87a", 6) == 0 || std::memcmp(in.in, "GIF89a", 6) == 0) && (in.in[6] | in.in[7]) && (in.in[8] | in.in[9]);
     }
     // the walk of a WebP input for a decode: a lossy file is ImageTypeNotSupported (known difference: the reference decodes it)
-    static void walk_webp(const Io& in, ifhip::WebpParsed* P) {
-        const int rc = ifhip::parse_webp_for_decode(in.in, in.in_len, P);
+    // unless the context's lossy decoder is switched on (ifhip_shim_context_set_webp_lossy_decoder): then P->lossless tells the two apart
+    static void walk_webp(const Io& in, ifhip::WebpParsed* P, bool lossy_decoder) {
+        int rc = ifhip::parse_webp_for_decode(in.in, in.in_len, P);
+        if (rc == IFHIP_METHOD_NOT_IMPLEMENTED && lossy_decoder) rc = ifhip::parse_webp_lossy_for_decode(in.in, in.in_len, P);
         if (rc == IFHIP_METHOD_NOT_IMPLEMENTED) raise(kImageTypeNotSupported, "%s", ifhip_last_error_message());
         check(rc);
     }
@@ -934,7 +938,7 @@ struct Job {
         }
         if (is_webp(in)) {                                               // WebPDecoder: no EXIF orientation (webp.rs:176-179)
             ifhip::WebpParsed P;
-            walk_webp(in, &P);
+            walk_webp(in, &P, c->webp_lossy_decoder.load(std::memory_order_relaxed));
             *w = P.w; *h = P.h;
             return;
         }
@@ -1068,7 +1072,7 @@ struct Job {
     // decode-time rescaler (webp.rs:181-188), which is not built.
     FramePtr decode_webp(int32_t io_id, Io& in) {
         ifhip::WebpParsed P;
-        walk_webp(in, &P);
+        walk_webp(in, &P, c->webp_lossy_decoder.load(std::memory_order_relaxed));
         check_size(sec.max_decode_size, "max_decode_size", P.w, P.h);                 // on the header, before anything is staged
         ifhip_color_plan color_plan;
         const bool convert = !in.told_discard_profile && P.color_kind == 2 &&
@@ -1077,6 +1081,20 @@ struct Job {
             raise(kActionNotSupported, "ActionNotSupported: webp_decoder_hints %ux%u for io_id %d (%ux%u): libwebp's decode-time rescaler is not built "
                   "(the reference shrinks during the decode, codecs/webp.rs:181-188); decode at full size and resample", in.told_webp_w, in.told_webp_h, io_id, P.w, P.h);
         FramePtr f = new_frame(P.w, P.h, P.has_alpha, 0, true);                       // (max_frame_size inside)
+        if (!P.lossless) {
+            // EXTENSION (ifhip_shim_context_set_webp_lossy_decoder): a still `VP8 ` (+ `ALPH`) file.  The host reads the key frame's header
+            // and bool-decodes its partitions (csrc/vp8_read.cpp), the pixels are made in csrc/vp8_decode.hip; libwebp's default options.
+            ifhip::Vp8Job J;
+            ifhip::vp8_prepare_job(P, &J);                                            // on this job's thread, like webp_prepare_job
+            uint32_t status = J.frame.status;
+            const ifhip::Vp8Job* job = &J;
+            const size_t bytes = f->bytes();
+            if (!status) status = decoded_status("decode(webp lossy)", [&](uint32_t* d_status) { return ifhip::vp8_decode_prepared_device(&job, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream); });
+            if (status) raise(kImageMalformed, "ImageMalformed: libwebp decoding error %s (io_id %d, status %u)", ifhip::vp8_status_text(status), io_id, status);
+            if (convert) convert_to_srgb(f, color_plan);
+            decodes.push_back({io_id, P.w, P.h, "image/webp", "webp"});
+            return f;
+        }
         ifhip::WebpJob J;
         ifhip::webp_prepare_job(P, &J);                                               // on this job's thread, like ifhip_jpeg_entropy_prepare
         if (J.status) raise(kImageMalformed, "ImageMalformed: libwebp decoding error %s (io_id %d, status %u)", ifhip::webp_status_text(J.status), io_id, J.status);
@@ -2726,6 +2744,13 @@ bool ifhip_shim_context_set_gif_animation(struct imageflow_context* c, int on) {
     c->gif_animation.store(on != 0, std::memory_order_relaxed);
     return true;
 }
+// EXTENSION: lossy WebP inputs (`VP8 `, with or without `ALPH`) are decoded (see Job::decode_webp); off by default, where they
+// stay ImageTypeNotSupported in the words they always had.
+bool ifhip_shim_context_set_webp_lossy_decoder(struct imageflow_context* c, int on) {
+    CTX_OR_ABORT(c);
+    c->webp_lossy_decoder.store(on != 0, std::memory_order_relaxed);
+    return true;
+}
 bool ifhip_shim_context_set_color_management(struct imageflow_context* c, int on) {
     CTX_OR_ABORT(c);
     c->color_management.store(on != 0, std::memory_order_relaxed);
@@ -2893,7 +2918,7 @@ const struct imageflow_json_response* imageflow_context_send_json(struct imagefl
             }
             if (Job::is_webp(in)) {                                  // WebPDecoder: the features of the file, no EXIF orientation (webp.rs:130-179)
                 ifhip::WebpParsed P;
-                Job::walk_webp(in, &P);
+                Job::walk_webp(in, &P, c->webp_lossy_decoder.load(std::memory_order_relaxed));
                 return respond(c, 200, "{\n  \"code\": 200,\n  \"success\": true,\n  \"message\": \"OK\",\n  \"data\": {\n    \"image_info\": {\"preferred_mime_type\": \"image/webp\", "
                                        "\"preferred_extension\": \"webp\", \"image_width\": " + std::to_string(P.w) + ", \"image_height\": " + std::to_string(P.h) +
                                        ", \"frame_decodes_into\": \"" + (P.has_alpha ? "bgra_32" : "bgr_32") + "\"}\n  }\n}");

@@ -364,6 +364,14 @@ class WebpHeadReader {
         if (bits(8) != 0x2Fu) return kWebpDecContainer;
         P->w = bits(14) + 1u; P->h = bits(14) + 1u; P->alpha = bits(1);
         if (bits(3) != 0u) return kWebpDecContainer;
+        return prepare_body(P);
+    }
+    // a stream without signature and size field (the VP8L-coded plane of an ALPH chunk): the image's size is the caller's
+    uint32_t prepare_headless(uint32_t w, uint32_t h, WebpPrepared* P) {
+        P->w = w; P->h = h; P->alpha = 0;
+        return prepare_body(P);
+    }
+    uint32_t prepare_body(WebpPrepared* P) {
         uint32_t xsize = P->w, seen = 0;
         P->n_transforms = 0;
         while (bits(1)) {

@@ -58,7 +58,7 @@ int parse_webp(const uint8_t* d, size_t len, WebpParsed* out) {
                 P.lossless = true; P.payload = q; P.payload_len = static_cast<size_t>(n);
                 P.w = (bits & 0x3FFFu) + 1u; P.h = ((bits >> 14) & 0x3FFFu) + 1u; P.has_alpha = ((bits >> 28) & 1u) != 0u;
             } else {
-                lossy = true;
+                lossy = true; P.vp8 = q; P.vp8_len = static_cast<size_t>(n);
                 if (n < 10u || q[3] != 0x9D || q[4] != 0x01 || q[5] != 0x2A) return malformed("the VP8 frame header");
                 P.w = (q[6] | static_cast<uint32_t>(q[7]) << 8) & 0x3FFFu; P.h = (q[8] | static_cast<uint32_t>(q[9]) << 8) & 0x3FFFu;
                 if (!P.w || !P.h) return malformed("the VP8 frame header");
@@ -68,6 +68,7 @@ int parse_webp(const uint8_t* d, size_t len, WebpParsed* out) {
             return malformed("no image chunk at the start of a file without VP8X");
         } else if (tag_is(tag, "ALPH")) {
             P.has_alpha = true;
+            if (!P.alph && !have_image) { P.alph = q; P.alph_len = static_cast<size_t>(n); }
         } else if (tag_is(tag, "ANIM") || tag_is(tag, "ANMF")) {
             P.animated = true;
         } else if (tag_is(tag, "ICCP")) {
@@ -76,6 +77,7 @@ int parse_webp(const uint8_t* d, size_t len, WebpParsed* out) {
         pos += 8u + static_cast<size_t>(padded);
     }
     if (vp8x && (flags & 0x02u)) P.animated = true;
+    if (P.animated || !lossy) { P.vp8 = P.alph = nullptr; P.vp8_len = P.alph_len = 0; }
     if (P.animated) { P.w = canvas_w; P.h = canvas_h; P.lossless = false; P.payload = nullptr; P.payload_len = 0; P.has_alpha = (flags & 0x10u) != 0u; }
     else if (!have_image) return malformed("no image chunk");
     else if (vp8x && (canvas_w != P.w || canvas_h != P.h)) return malformed("the VP8X canvas is not the image's size");
@@ -90,6 +92,14 @@ int parse_webp_for_decode(const uint8_t* d, size_t len, WebpParsed* out) {
     if (!out->lossless) return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "ImageTypeNotSupported: a lossy WebP (VP8%s): the lossy VP8 decoder is not built, only lossless VP8L files are read",
                                     out->has_alpha ? " + ALPH" : "");
     if (out->payload_len > 0x7FFF0000u) return malformed("a VP8L chunk above 2^31 bytes");
+    return IFHIP_OK;
+}
+
+int parse_webp_lossy_for_decode(const uint8_t* d, size_t len, WebpParsed* out) {
+    if (int rc = parse_webp(d, len, out)) return rc;
+    if (out->animated) return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: libwebp decoding error UNSUPPORTED_FEATURE (an animated WebP: WebPDecode answers the same)");
+    if (out->lossless) return fail(IFHIP_METHOD_NOT_IMPLEMENTED, "ImageTypeNotSupported: not a lossy WebP (VP8L): lossless files are read by the lossless decoder");
+    if (out->vp8_len > 0x7FFF0000u || out->alph_len > 0x7FFF0000u) return malformed("a chunk above 2^31 bytes");
     return IFHIP_OK;
 }
 

@@ -19,6 +19,10 @@ struct WebpParsed {
     size_t payload_len = 0;
     const uint8_t* icc = nullptr;        // the ICCP chunk's bytes behind color_kind 1 or 2, inside the caller's file
     size_t icc_len = 0;
+    const uint8_t* vp8 = nullptr;        // a still lossy file: the `VP8 ` chunk's bytes and, where there is one, the `ALPH` chunk's
+    size_t vp8_len = 0;
+    const uint8_t* alph = nullptr;
+    size_t alph_len = 0;
 };
 // IFHIP_OK, or IFHIP_INVALID_ARGUMENT with an "ImageMalformed: libwebp decoding error ..." message.  A lossy or an animated
 // file parses (lossless = false / animated = true): what to answer is the caller's.
@@ -26,6 +30,9 @@ int parse_webp(const uint8_t* d, size_t len, WebpParsed* out);
 // parse_webp for a decode: IFHIP_METHOD_NOT_IMPLEMENTED "ImageTypeNotSupported: ..." for lossy VP8, ImageMalformed
 // naming UNSUPPORTED_FEATURE for an animation
 int parse_webp_for_decode(const uint8_t* d, size_t len, WebpParsed* out);
+// parse_webp for the lossy decoder (csrc/vp8_read.cpp, csrc/vp8_decode.hip): a still `VP8 ` (+ `ALPH`) file.  A lossless file is
+// IFHIP_METHOD_NOT_IMPLEMENTED "ImageTypeNotSupported: not a lossy WebP ...", an animation ImageMalformed naming UNSUPPORTED_FEATURE.
+int parse_webp_lossy_for_decode(const uint8_t* d, size_t len, WebpParsed* out);
 
 // A file's stream prepared on the host (header, transforms, entropy image, codes) and its padded payload.
 struct WebpJob {

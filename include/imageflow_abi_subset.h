@@ -127,6 +127,12 @@ IMAGEFLOW_SHIM_API int ifhip_shim_context_device(struct imageflow_context *conte
  * cHRM.  Still refused, naming the case: GRAY / CMYK spaces, a Lab PCS, LUT-based profiles.  A malformed profile is a
  * ColorProfileError (ImageMalformed) unless the decoder was told "ignore_color_profile_errors".  Returns true. */
 IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_color_management(struct imageflow_context *context, int on);
+/* EXTENSION: lossy WebP inputs -- a still `VP8 ` chunk, with or without an `ALPH` chunk -- are decoded on the device, to
+ * exactly what WebPDecode(MODE_BGRA) gives with libwebp's default options (csrc/vp8_read.cpp, csrc/vp8_decode.hip): `decode`,
+ * `watermark`, `command_string` and v1/get_image_info then take such a file (bgra_32 where it has alpha, else bgr_32).  Off by
+ * default, where a lossy file stays ImageTypeNotSupported.  max_decode_size, the ICCP policy, webp_decoder_hints and EXIF
+ * are treated as for a lossless file; animated WebP and libwebp's decode-time rescaler stay refused.  Returns true. */
+IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_webp_lossy_decoder(struct imageflow_context *context, int on);
 /* EXTENSION: `encode` with the preset "gif" writes a GIF89a file on the device (ifhip_gif_encode_batch_device: GifEncoder::write_frame,
  * codecs/gif/mod.rs:385-592) and reports image/gif; off by default, where the preset writes the raw BGRA container as ever.  A
  * GIF input of the job hands its loop count and the selected frame's delay and user-input flag to the file. */

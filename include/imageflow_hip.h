@@ -705,6 +705,31 @@ IFHIP_API int ifhip_webp_decode_batch_device(const uint8_t* const* files, const 
 IFHIP_API int ifhip_webp_decode(const uint8_t* webp, size_t len, uint8_t* bgra, uint32_t stride, size_t capacity,
                                 uint32_t* status);
 
+/* Device WebP decoder, lossy files: what WebPDecoder (imageflow_core/src/codecs/webp.rs:162-248) gets from WebPDecode(MODE_BGRA)
+ * for a still `VP8 ` file, with or without an `ALPH` chunk -- libwebp 1.6.0's default options: fancy upsampling, the loop filter
+ * honoured, no dithering, alpha not premultiplied.  The host walks the container, reads the key frame's header and bool-decodes
+ * its partitions (csrc/vp8_read.cpp: modes and un-dequantised coefficient levels); dequantisation, the inverse transforms,
+ * intra prediction, the loop filter, the alpha plane and the conversion to BGRA run on the device (csrc/vp8_decode.hip).
+ * ifhip_webp_info answers the container's facts for these files too (lossless = 0; has_alpha is the VP8X ALPHA flag or an ALPH
+ * chunk).  The batch form, ifhip_webp_lossy_decode_batch_device, is declared in imageflow_hip_webp_lossy.h.
+ * Not built: animation, libwebp's decode-time rescaler.
+ *
+ * Status word of a file: 0, or why it is no image. */
+#define IFHIP_VP8_DEC_CONTAINER 1        /* batch only: the RIFF container did not parse, or the file is animated        */
+#define IFHIP_VP8_DEC_NOT_LOSSY 2        /* batch only: a lossless file (ifhip_webp_decode_batch_device reads those)      */
+#define IFHIP_VP8_DEC_FRAME_HEADER 3     /* no shown key frame of profile 0..3 with its start code, or its header ends early */
+#define IFHIP_VP8_DEC_PARTITIONS 4       /* the first partition or the table of partition sizes reaches beyond the chunk  */
+#define IFHIP_VP8_DEC_END_OF_MODES 5     /* premature end of the first partition (segments, skip flags, modes)           */
+#define IFHIP_VP8_DEC_END_OF_TOKENS 6    /* premature end of a token partition                                           */
+#define IFHIP_VP8_DEC_ALPHA_HEADER 7     /* ALPH: a compression above 1, pre-processing above 1 or a reserved value      */
+#define IFHIP_VP8_DEC_ALPHA_STREAM 8     /* ALPH: raw bytes fewer than the plane, or a VP8L stream that is no image       */
+/* The synchronous host-buffer drop-in for WebPDecode(MODE_BGRA) on a lossy file: one file into `height` BGRA rows of `stride`
+ * bytes at bgra (capacity bytes; bytes between rows are kept).  A non-zero status word comes back in *status (nullable) with
+ * IFHIP_INVALID_ARGUMENT and an "ImageMalformed: libwebp decoding error" message; a lossless file is
+ * IFHIP_METHOD_NOT_IMPLEMENTED with an "ImageTypeNotSupported" message. */
+IFHIP_API int ifhip_webp_lossy_decode(const uint8_t* webp, size_t len, uint8_t* bgra, uint32_t stride, size_t capacity,
+                                      uint32_t* status);
+
 /* Device GIF decoder: what GifDecoder (imageflow_core/src/codecs/gif/mod.rs:21-309) hands on for one frame of a file -- the
  * logical screen after frames 0..frame_index were composed in order with their disposal (gif/screen.rs:25-95,
  * gif/disposal.rs:29-77), as BGRA with meaningful alpha.  The host walks the container (csrc/gif_read.cpp: header, screen,
