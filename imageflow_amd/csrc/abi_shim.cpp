@@ -22,6 +22,11 @@
 //     "gif" is that container too unless ifhip_shim_context_set_gif_encoder switched the device GIF coder on (gif_encode.hip);
 //   * with ifhip_shim_context_set_gif_animation on as well, an animated GIF source runs the job once per frame and the "gif"
 //     encode nodes write one animated file (Job::run_job).
+//
+// Beside this file: shim_errors.hpp (the error categories and the exception a refusal travels in), shim_json.hpp / .cpp (the
+// JSON reader and the parameter readers of the nodes: no GPU runtime, tests/shim_json_check.cpp runs them under the host
+// sanitizers), shim_runtime.hpp / .cpp (a job's stream and device, its device memory, the timing events) and shim_job.hpp
+// (frames, limits, the io table, the context, the records of a result), all in namespace ifshim.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -54,526 +59,13 @@
 #include "webp_read.hpp"        // the RIFF walk, the prepare and the device decode of a lossless WebP (webp_read.cpp, webp_decode.hip)
 #include "layout.hpp"           // imageflow_riapi's constraint layout (constrain / watermark)
 #include "querystring.hpp"      // imageflow_riapi's querystring: Instructions, their expansion into nodes (command_string)
+#include "shim_job.hpp"          // frames, limits, Io, the context, the records; with it shim_json.hpp (JVal, parse_json, the parameter readers),
+                                // shim_errors.hpp (Cat, FlowErr, raise) and shim_runtime.hpp (check, the job's stream, job_malloc / job_free, timing_events)
+
+using namespace ifshim;
 
 namespace {
 
-// ---- errors: ErrorCategory (imageflow_core/src/errors.rs:779-838) with its exit / HTTP maps (:849-902) -----------
-enum Cat { kOk = 0, kOutOfMemory = 1, kArgumentInvalid = 2, kInvalidJson = 3, kImageMalformed = 4, kImageTypeNotSupported = 5,
-           kNodeArgumentInvalid = 6, kGraphInvalid = 7, kActionNotSupported = 8, kIoError = 16, kInternalError = 18,
-           kOperationCancelled = 21 };
-// (ErrorKind::ColorProfileError, a profile the CMS cannot read, is of category ImageMalformed: errors.rs:241 -- code 4, HTTP 400, exit 65)
-int http_code(int c) {
-    switch (c) {
-    case kOk: return 200;
-    case kArgumentInvalid: case kGraphInvalid: case kNodeArgumentInvalid: case kActionNotSupported: case kInvalidJson:
-    case kImageMalformed: case kImageTypeNotSupported: return 400;
-    case kOutOfMemory: return 503;
-    case kOperationCancelled: return 499;
-    default: return 500;
-    }
-}
-int exit_code(int c) {
-    switch (c) {
-    case kOk: return 0;
-    case kArgumentInvalid: case kGraphInvalid: case kActionNotSupported: case kNodeArgumentInvalid: return 64;
-    case kInvalidJson: case kImageMalformed: case kImageTypeNotSupported: return 65;
-    case kOutOfMemory: return 71;
-    case kIoError: return 74;
-    case kOperationCancelled: return 130;
-    default: return 70;
-    }
-}
-struct FlowErr {
-    int cat;
-    std::string msg;
-};
-[[noreturn]] void raise(int cat, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-void raise(int cat, const char* fmt, ...) {
-    char buf[768];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    throw FlowErr{cat, buf};
-}
-void check(int rc) {                                  // ifhip_status -> ErrorCategory
-    if (rc == IFHIP_OK) return;
-    const char* m = ifhip_last_error_message();
-    const std::string msg = m ? m : "";
-    int cat = kInternalError;
-    if (rc == IFHIP_INVALID_ARGUMENT) cat = msg.rfind("ImageMalformed", 0) == 0 ? kImageMalformed : kArgumentInvalid;
-    else if (rc == IFHIP_METHOD_NOT_IMPLEMENTED) cat = kActionNotSupported;
-    else if (rc == IFHIP_ALLOCATION_FAILED) cat = kOutOfMemory;
-    throw FlowErr{cat, msg};
-}
-void hip_check(hipError_t e, const char* what) {
-    if (e != hipSuccess) raise(e == hipErrorOutOfMemory ? kOutOfMemory : kInternalError, "GpuError: %s: %s", what, hipGetErrorString(e));
-}
-
-// ---- JSON ------------------------------------------------------------------------------------------------------
-struct JVal {
-    enum T { Null, Bool, Num, Str, Arr, Obj } t = Null;
-    bool b = false;
-    double n = 0;
-    std::string s;
-    std::vector<JVal> a;
-    std::vector<std::pair<std::string, JVal>> o;
-    const JVal* get(const char* k) const {
-        if (t != Obj) return nullptr;
-        for (const auto& kv : o) if (kv.first == k) return &kv.second;
-        return nullptr;
-    }
-    bool is_null() const { return t == Null; }
-};
-struct JParser {
-    const char *p, *end;
-    int depth = 0;
-    void ws() { while (p < end && (*p == ' ' || *p == '\n' || *p == '\r' || *p == '\t')) ++p; }
-    [[noreturn]] void bad(const char* what) { raise(kInvalidJson, "InvalidJson: %s at byte %ld", what, static_cast<long>(end - p)); }
-    void lit(const char* w) { const size_t n = std::strlen(w); if (static_cast<size_t>(end - p) < n || std::memcmp(p, w, n)) bad("bad literal"); p += n; }
-    std::string str() {
-        std::string out;
-        ++p;
-        while (true) {
-            if (p >= end) bad("unterminated string");
-            const unsigned char c = static_cast<unsigned char>(*p++);
-            if (c == '"') return out;
-            if (c < 0x20) bad("control character in string");
-            if (c != '\\') { out.push_back(static_cast<char>(c)); continue; }
-            if (p >= end) bad("unterminated escape");
-            const char e = *p++;
-            switch (e) {
-            case '"': case '\\': case '/': out.push_back(e); break;
-            case 'b': out.push_back('\b'); break;
-            case 'f': out.push_back('\f'); break;
-            case 'n': out.push_back('\n'); break;
-            case 'r': out.push_back('\r'); break;
-            case 't': out.push_back('\t'); break;
-            case 'u': {
-                if (end - p < 4) bad("short \\u escape");
-                unsigned v = 0;
-                for (int i = 0; i < 4; ++i) {
-                    const char h = *p++;
-                    v = v * 16 + (h >= '0' && h <= '9' ? h - '0' : h >= 'a' && h <= 'f' ? h - 'a' + 10 : h >= 'A' && h <= 'F' ? h - 'A' + 10 : (bad("bad hex digit"), 0));
-                }
-                if (v < 0x80) out.push_back(static_cast<char>(v));
-                else if (v < 0x800) { out.push_back(static_cast<char>(0xC0 | (v >> 6))); out.push_back(static_cast<char>(0x80 | (v & 63))); }
-                else { out.push_back(static_cast<char>(0xE0 | (v >> 12))); out.push_back(static_cast<char>(0x80 | ((v >> 6) & 63))); out.push_back(static_cast<char>(0x80 | (v & 63))); }
-                break;
-            }
-            default: bad("bad escape");
-            }
-        }
-    }
-    JVal value() {
-        if (++depth > 64) bad("nesting too deep");
-        ws();
-        if (p >= end) bad("unexpected end");
-        JVal v;
-        const char c = *p;
-        if (c == '{') {
-            v.t = JVal::Obj; ++p; ws();
-            if (p < end && *p == '}') { ++p; --depth; return v; }
-            while (true) {
-                ws();
-                if (p >= end || *p != '"') bad("expected a key");
-                std::string k = str();
-                ws();
-                if (p >= end || *p != ':') bad("expected ':'");
-                ++p;
-                v.o.emplace_back(std::move(k), value());
-                ws();
-                if (p < end && *p == ',') { ++p; continue; }
-                if (p < end && *p == '}') { ++p; break; }
-                bad("expected ',' or '}'");
-            }
-        } else if (c == '[') {
-            v.t = JVal::Arr; ++p; ws();
-            if (p < end && *p == ']') { ++p; --depth; return v; }
-            while (true) {
-                v.a.push_back(value());
-                ws();
-                if (p < end && *p == ',') { ++p; continue; }
-                if (p < end && *p == ']') { ++p; break; }
-                bad("expected ',' or ']'");
-            }
-        } else if (c == '"') { v.t = JVal::Str; v.s = str(); }
-        else if (c == 't') { lit("true"); v.t = JVal::Bool; v.b = true; }
-        else if (c == 'f') { lit("false"); v.t = JVal::Bool; }
-        else if (c == 'n') { lit("null"); }
-        else {
-            // RFC 8259 number grammar only: strtod alone would also take "inf", "nan", hex floats and leading '+'
-            const char* q = p;
-            if (q < end && *q == '-') ++q;
-            if (q >= end || *q < '0' || *q > '9') bad("unexpected character");
-            if (*q == '0') ++q; else while (q < end && *q >= '0' && *q <= '9') ++q;
-            if (q < end && *q == '.') { ++q; if (q >= end || *q < '0' || *q > '9') bad("bad number"); while (q < end && *q >= '0' && *q <= '9') ++q; }
-            if (q < end && (*q == 'e' || *q == 'E')) {
-                ++q;
-                if (q < end && (*q == '+' || *q == '-')) ++q;
-                if (q >= end || *q < '0' || *q > '9') bad("bad number");
-                while (q < end && *q >= '0' && *q <= '9') ++q;
-            }
-            if (q - p > 64) bad("number too long");
-            const std::string tmp(p, static_cast<size_t>(q - p));
-            v.n = std::strtod(tmp.c_str(), nullptr);
-            if (!std::isfinite(v.n)) bad("number out of range");
-            p = q;
-            v.t = JVal::Num;
-        }
-        --depth;
-        return v;
-    }
-};
-JVal parse_json(const uint8_t* buf, size_t n) {
-    JParser P{reinterpret_cast<const char*>(buf), reinterpret_cast<const char*>(buf) + n};
-    JVal v = P.value();
-    P.ws();
-    if (P.p != P.end) P.bad("trailing characters");
-    return v;
-}
-// Which coder `encode` hands a preset to (IFHIP_ENCODE_CODER_*): the object forms by their key, in the order `encode` asks;
-// EncoderPreset::WebPLossless is a unit variant, so its JSON is the string "webplossless".  Everything else -- "gif",
-// "webplossy" in any form, lodepng, no preset -- is the raw BGRA container.
-int encode_coder(const JVal* preset) {
-    if (!preset) return IFHIP_ENCODE_CODER_RAW;
-    if (preset->get("libjpeg_turbo")) return IFHIP_ENCODE_CODER_JPEG;
-    if (preset->get("libpng")) return IFHIP_ENCODE_CODER_PNG;
-    if (preset->get("pngquant")) return IFHIP_ENCODE_CODER_PNGQUANT;
-    if (preset->get("mozjpeg")) return IFHIP_ENCODE_CODER_MOZJPEG;
-    if (preset->t == JVal::Str && preset->s == "webplossless") return IFHIP_ENCODE_CODER_WEBP_LOSSLESS;
-    return IFHIP_ENCODE_CODER_RAW;
-}
-int64_t want_int(const JVal& o, const char* key, const char* node) {
-    const JVal* v = o.get(key);
-    if (!v || v->t != JVal::Num || v->n != std::floor(v->n) || std::fabs(v->n) > 9007199254740992.0)
-        raise(kInvalidJson, "InvalidJson: %s.%s must be an integer", node, key);
-    return static_cast<int64_t>(v->n);
-}
-uint32_t want_u32(const JVal& o, const char* key, const char* node) {
-    const int64_t v = want_int(o, key, node);
-    if (v < 0 || v > 0x7fffffff) raise(kInvalidJson, "InvalidJson: %s.%s out of range", node, key);
-    return static_cast<uint32_t>(v);
-}
-
-// imageflow_types::Color (lib.rs:807-824) + imageflow_helpers/src/colors.rs:36-61 -> Color32 0xAARRGGBB
-uint32_t parse_color(const JVal* v, const char* node) {
-    if (!v || v->is_null()) return 0u;
-    if (v->t == JVal::Str) {
-        if (v->s == "transparent") return 0u;
-        if (v->s == "black") return 0xFF000000u;
-        raise(kInvalidJson, "InvalidJson: %s: unknown colour '%s'", node, v->s.c_str());
-    }
-    const JVal* srgb = v->get("srgb");
-    const JVal* hex = srgb ? srgb->get("hex") : nullptr;
-    if (!hex || hex->t != JVal::Str) raise(kInvalidJson, "InvalidJson: %s: colour must be \"transparent\", \"black\" or {\"srgb\":{\"hex\":..}}", node);
-    std::string s = hex->s;
-    if (!s.empty() && s[0] == '#') s.erase(0, 1);
-    if (s.size() == 3 || s.size() == 4) { std::string d; for (char c : s) { d.push_back(c); d.push_back(c); } s = d; }
-    if (s.size() == 6) s += "FF";
-    if (s.size() != 8) raise(kArgumentInvalid, "InvalidNodeParams: %s: bad colour '%s'", node, hex->s.c_str());
-    uint32_t ch[4];
-    for (int i = 0; i < 4; ++i) {
-        char* e = nullptr;
-        const std::string part = s.substr(static_cast<size_t>(2 * i), 2);
-        ch[i] = static_cast<uint32_t>(std::strtoul(part.c_str(), &e, 16));
-        if (e != part.c_str() + 2) raise(kArgumentInvalid, "InvalidNodeParams: %s: bad colour '%s'", node, hex->s.c_str());
-    }
-    return (ch[3] << 24) | (ch[0] << 16) | (ch[1] << 8) | ch[2];
-}
-// s::Color::Transparent, the enum value (a missing colour reads as it): the only colour create_canvas.rs:79-82 turns into a
-// ReplaceSelf canvas -- an srgb colour whose alpha is 0 still makes a BlendWithMatte canvas
-bool keyword_transparent(const JVal* v) { return !v || v->is_null() || (v->t == JVal::Str && v->s == "transparent"); }
-int parse_filter(const JVal* v, int dflt) {                      // imageflow_types/src/lib.rs:144-205
-    if (!v || v->is_null()) return dflt;
-    static const std::pair<const char*, int> names[] = {
-        {"robidoux_fast", 1}, {"robidoux", 2}, {"robidoux_sharp", 3}, {"ginseng", 4}, {"ginseng_sharp", 5}, {"lanczos", 6},
-        {"lanczos_sharp", 7}, {"lanczos_2", 8}, {"lanczos_2_sharp", 9}, {"cubic", 11}, {"cubic_sharp", 12}, {"catmull_rom", 13},
-        {"mitchell", 14}, {"cubic_b_spline", 15}, {"hermite", 16}, {"jinc", 17}, {"triangle", 22}, {"linear", 23}, {"box", 24},
-        {"fastest", 27}, {"n_cubic", 29}, {"n_cubic_sharp", 30}};
-    if (v->t == JVal::Str)
-        for (const auto& kv : names) if (v->s == kv.first) return kv.second;
-    raise(kInvalidJson, "InvalidJson: unknown filter");
-}
-
-// JVal -> text: command_string.watermarks goes to the querystring expansion as text, and every number reads back as itself
-void to_json(const JVal& v, std::string* o) {
-    switch (v.t) {
-    case JVal::Null: *o += "null"; break;
-    case JVal::Bool: *o += v.b ? "true" : "false"; break;
-    case JVal::Num: { char buf[40]; std::snprintf(buf, sizeof buf, "%.17g", v.n); *o += buf; break; }
-    case JVal::Str:
-        o->push_back('"');
-        for (unsigned char ch : v.s) {
-            if (ch == '"' || ch == '\\') { o->push_back('\\'); o->push_back(static_cast<char>(ch)); }
-            else if (ch < 0x20) { char buf[8]; std::snprintf(buf, sizeof buf, "\\u%04x", ch); *o += buf; }
-            else o->push_back(static_cast<char>(ch));
-        }
-        o->push_back('"');
-        break;
-    case JVal::Arr:
-        o->push_back('[');
-        for (size_t i = 0; i < v.a.size(); ++i) { if (i) o->push_back(','); to_json(v.a[i], o); }
-        o->push_back(']');
-        break;
-    case JVal::Obj:
-        o->push_back('{');
-        for (size_t i = 0; i < v.o.size(); ++i) { if (i) o->push_back(','); to_json(JVal{JVal::Str, false, 0, v.o[i].first, {}, {}}, o); o->push_back(':'); to_json(v.o[i].second, o); }
-        o->push_back('}');
-        break;
-    }
-}
-
-// ---- frames in HBM ---------------------------------------------------------------------------------------------
-// A decoded JPEG whose pixel stage has not run: when the frame's one consumer is a resample, decode and resample run as ONE
-// device call (ifhip_jpeg_decode_resample_batch_device: no decoded BGRA bitmap in HBM); any other consumer gets the bitmap
-// through Job::dev(), which runs the pixel stage then.
-// ---- the stream of a job ------------------------------------------------------------------------------------------------
-// One Context per thread (imageflow_abi/src/lib.rs:20-27): every job runs on a stream of its own (non-blocking: nothing a
-// job does waits for another thread's job), leased from a pool for the duration of one send_json; device memory comes from
-// the library's size-class cache (devmem.cpp) and goes back without a driver call.  Whatever a job frees it frees behind
-// quiesce() -- a look at the job's stream, a wait if it is still busy -- so the block is idle (ifhip::QuiescedScope around
-// the whole job); nodes themselves do not wait for the device.
-std::mutex g_stream_mu;
-struct DeviceQueues { std::vector<hipStream_t> pool; int slots_taken = 0; std::condition_variable slot_cv; };
-std::map<int, DeviceQueues> g_queues;                     // per device ordinal: a stream belongs to the device it was created on
-thread_local hipStream_t t_job_stream = nullptr;          // the stream of the job this thread is running (null outside a job)
-// Admission: jobs beyond kJobSlots PER DEVICE wait for a slot on the host.  The rate grows with the jobs admitted -- batches
-// of the coalesced decode fill up, the device always has somebody's pixel stage to run -- until the host's CPUs are the
-// limit: 7 800 jobs/s at 20, 9 900 at 40, 11 100 at 48 for the thumbnail job on a 16-CPU container (round 5,
-// profiles/r5_abi_jobs_slots_after_host_fixes.txt); 40 leaves a quarter of that container's CPUs to the caller.  (Rounds 4
-// and 5 measured a FALL above 20 admitted jobs and blamed the runtime's hardware queues; it was the 17-32-file decode
-// batches, see kMaxCoalesce.)
-constexpr int kJobSlots = 40;
-// Contexts and devices.  The reference's guidance is one Context per thread (imageflow_abi/src/lib.rs:20-27) and jobs are
-// independent, so a node's GPUs are fed by giving every context a device: with ifhip_shim_spread_contexts(1) a new context
-// takes the next usable device round-robin and all its jobs run there, whichever thread calls (no collective: a job's
-// outputs are host buffers).  Without it (the default) a context follows the calling thread's current device, as before.
-std::atomic<int> g_spread_contexts{0};
-std::atomic<uint32_t> g_context_counter{0};
-// HIP ordinals of the gfx950 devices, asked of the driver once (hipGetDeviceProperties fills a kilobyte struct per call, and
-// a service creates thousands of contexts a second)
-const std::vector<int>& usable_devices() {
-    static const std::vector<int> list = [] {
-        std::vector<int> v;
-        int n = 0;
-        if (hipGetDeviceCount(&n) != hipSuccess) { (void)hipGetLastError(); return v; }
-        for (int i = 0; i < n; ++i) {
-            hipDeviceProp_t prop;
-            if (hipGetDeviceProperties(&prop, i) == hipSuccess && std::strncmp(prop.gcnArchName, "gfx950", 6) == 0) v.push_back(i);
-            else (void)hipGetLastError();
-        }
-        return v;
-    }();
-    return list;
-}
-struct DeviceScope {                                      // the calling thread on the context's device for one call
-    int prev = -1;
-    bool switched = false;
-    explicit DeviceScope(int dev) {
-        if (dev < 0) return;
-        if (hipGetDevice(&prev) != hipSuccess) { (void)hipGetLastError(); prev = -1; }
-        if (prev != dev) {
-            if (hipSetDevice(dev) == hipSuccess) switched = true;
-            else (void)hipGetLastError();                 // (the first GPU call of the job reports)
-        }
-    }
-    ~DeviceScope() { if (switched && prev >= 0) (void)hipSetDevice(prev); }
-};
-struct StreamLease {
-    hipStream_t st = nullptr;
-    int dev = 0;
-    StreamLease() {
-        if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
-        {
-            std::unique_lock<std::mutex> lk(g_stream_mu);
-            constexpr int slots = kJobSlots;
-            DeviceQueues& q = g_queues[dev];              // (map nodes do not move: the reference survives the wait)
-            while (q.slots_taken >= slots) q.slot_cv.wait(lk);
-            ++q.slots_taken;
-            if (!q.pool.empty()) { st = q.pool.back(); q.pool.pop_back(); }
-        }
-        if (!st && hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) { (void)hipGetLastError(); st = nullptr; }   // (no device: the null stream, the first GPU call reports)
-        t_job_stream = st;
-        ifhip_set_thread_stream(st);
-    }
-    ~StreamLease() {
-        t_job_stream = nullptr;
-        ifhip_set_thread_stream(nullptr);
-        if (st) (void)static_cast<hipError_t>(ifhip::wait_stream(st));
-        {
-            std::lock_guard<std::mutex> lk(g_stream_mu);
-            DeviceQueues& q = g_queues[dev];
-            if (st) q.pool.push_back(st);
-            --q.slots_taken;
-            q.slot_cv.notify_one();                       // (one waiter of THIS device; waking all of them cost a third of the job rate at 64 threads)
-        }
-    }
-};
-// Before anything of a job goes back to the cache: the job's stream -- the only one its blocks were ever used on -- is idle.
-void quiesce() {
-    if (t_job_stream && hipStreamQuery(t_job_stream) != hipSuccess) (void)static_cast<hipError_t>(ifhip::wait_stream(t_job_stream));
-    (void)hipGetLastError();
-}
-hipError_t job_malloc(void** p, size_t bytes) { return static_cast<hipError_t>(ifhip::cached_malloc(p, bytes)); }
-void job_free(void* p) { if (p) { quiesce(); (void)ifhip::cached_free(p); } }
-
-// The coefficient planes and quantisation tables of one entropy-decoded BATCH of files (one geometry): jobs of different
-// threads whose decodes were coalesced into one device call each hold a share and read their own image's part.
-struct DecodedBatch {
-    int16_t* coef[3] = {nullptr, nullptr, nullptr};      // [n][bh_c][bw_c][64]
-    size_t per_image[3] = {0, 0, 0};                     // int16 elements per image and component
-    uint16_t* d_qt = nullptr;                            // [n][3][64]
-    uint32_t w = 0, h = 0, bw[3] = {0, 0, 0}, bh[3] = {0, 0, 0};
-    int ncomp = 0;
-    uint8_t hs[3] = {1, 1, 1}, vs[3] = {1, 1, 1};
-    // the last share goes when its job ends -- every job waits for its own stream before it lets go (quiesce), the
-    // batch's decode itself was complete before any share was handed out
-    // (... and on an error path between the decode's launch and its wait this destructor IS the wait: the planes may not
-    // go back to the cache with the decode still writing them)
-    ~DecodedBatch() {
-        quiesce();
-        for (int16_t* p : coef) if (p) (void)ifhip::cached_free(p);
-        if (d_qt) (void)ifhip::cached_free(d_qt);
-    }
-};
-struct PendingJpeg {
-    ifhip_jpeg_stage* st = nullptr;
-    int16_t* coef[3] = {nullptr, nullptr, nullptr};      // this image's planes inside `batch`
-    uint16_t* d_qt = nullptr;
-    std::shared_ptr<DecodedBatch> batch;
-    ~PendingJpeg() {
-        quiesce();
-        if (st) ifhip_jpeg_stage_destroy(st);
-        ifhip::QuiescedScope q;                          // (a job thread has one already; a share that dies elsewhere: see above)
-        batch.reset();
-    }
-};
-struct Frame {                                   // graphics/bitmaps.rs Bitmap: BGRA8, 64-byte row stride
-    uint8_t* d = nullptr;                        // (null while `pending`: read it through Job::dev())
-    uint32_t w = 0, h = 0, stride = 0;
-    bool alpha = false;
-    int compose = IFHIP_REPLACE_SELF;
-    uint32_t matte = 0;
-    std::unique_ptr<PendingJpeg> pending;
-    size_t bytes() const { return static_cast<size_t>(h) * stride; }
-    ~Frame() { job_free(d); }
-};
-using FramePtr = std::shared_ptr<Frame>;
-
-// ExecutionSecurity (imageflow_types/src/lib.rs:1199-1236): the two limits that bound what this library allocates;
-// defaults = sane_defaults(), a job may override them with `security` (v1/execute) / `builder_config.security` (v1/build)
-struct SizeLimit { uint32_t w, h; float megapixels; };
-struct Security {
-    SizeLimit max_decode_size{12000, 12000, 100.f};
-    SizeLimit max_frame_size{10000, 10000, 100.f};
-    // Option<u64>, sane_defaults() 400 megapixels (lib.rs:1212-1235): frame count x width x height of an animation
-    // (GifDecoder::check_total_pixels, codecs/gif/mod.rs:103-118).  Read by the animation path alone.
-    bool has_max_total_file_pixels = true;
-    uint64_t max_total_file_pixels = 400000000ull;
-};
-// Engine::validate_frame_size (flow/execution_engine.rs:286-325); ErrorKind::SizeLimitExceeded -> ArgumentInvalid
-void check_size(const SizeLimit& lim, const char* what, uint64_t w, uint64_t h) {
-    if (w > lim.w) raise(kArgumentInvalid, "SizeLimitExceeded: Frame width %llu exceeds %s.w %u", static_cast<unsigned long long>(w), what, lim.w);
-    if (h > lim.h) raise(kArgumentInvalid, "SizeLimitExceeded: Frame height %llu exceeds %s.h %u", static_cast<unsigned long long>(h), what, lim.h);
-    const float mp = static_cast<float>(w) * static_cast<float>(h) / 1000000.f;
-    if (mp > lim.megapixels) raise(kArgumentInvalid, "SizeLimitExceeded: Frame megapixels %f exceeds %s.megapixels %f", static_cast<double>(mp), what, static_cast<double>(lim.megapixels));
-}
-
-constexpr char kRawMagic[8] = {'I', 'F', 'B', 'G', 'R', 'A', '1', '\0'};
-constexpr size_t kRawHeader = 8 + 16;
-
-// ---- context -----------------------------------------------------------------------------------------------------
-// Output buffers: Ready -> (get_output_buffer_by_id) Lent -> stays Lent; Ready -> (take_output_buffer) Taken
-// (CodecInstanceContainer, imageflow_core/src/codecs/mod.rs:421-436,560-626)
-enum class OutState { Ready, Lent, Taken };
-struct Io {
-    bool is_output = false;
-    const uint8_t* in = nullptr;
-    size_t in_len = 0;
-    std::vector<uint8_t> owned;                  // copied inputs (lifetime_outlives_function_call) / output bytes
-    bool written = false;
-    OutState out_state = OutState::Ready;
-    // v1/tell_decoder {jpeg_downscale_hints} (Context::tell_decoder -> MzDec::tell_decoder, mozjpeg_decoder.rs:560-586): kept
-    // with the input until its decoder runs; a decode node's own `commands` are told after these and win
-    bool out_base64 = false;                     // IoEnum::OutputBase64: the job result carries the bytes as {"base_64": ...}
-    bool told = false;
-    uint32_t told_w = 0, told_h = 0;
-    bool told_spatial = false, told_gamma = false;
-    bool told_discard_profile = false;           // DecoderCommand::DiscardColorProfile (mozjpeg_decoder.rs:88-91)
-    bool told_ignore_profile_errors = false;     // DecoderCommand::IgnoreColorProfileErrors (:93-96): a profile that fails leaves the samples as they are
-    bool told_convert_profile = false;           // EXTENSION "convert_color_profile": this input is converted to sRGB (Job::color_plan_for)
-    // DecoderCommand::WebPDecoderHints (codecs/webp.rs:181-188): the size libwebp's rescaler would decode to; acted on by a WebP input only
-    bool told_webp = false;
-    uint32_t told_webp_w = 0, told_webp_h = 0;
-    // DecoderCommand::SelectFrame (codecs/gif/mod.rs:200-205): the frame a GIF input hands on; the other decoders ignore it
-    bool told_frame = false;
-    int32_t told_frame_n = 0;
-};
-// select_frame: an integer (s::DecoderCommand::SelectFrame(i32))
-void tell_select_frame(Io& in, const JVal& j) {
-    if (j.t != JVal::Num || !(j.n >= -2147483648.0 && j.n <= 2147483647.0)) return;
-    in.told_frame = true;
-    in.told_frame_n = static_cast<int32_t>(j.n);
-}
-// webp_decoder_hints is accepted whatever it holds, as it was before a WebP input could act on it: only a hint that
-// carries both sizes is kept with the input
-void tell_webp_hint(Io& in, const JVal& j) {
-    const JVal* w = j.get("width");
-    const JVal* h = j.get("height");
-    if (!w || !h || w->t != JVal::Num || h->t != JVal::Num || !(w->n >= 0 && w->n <= 4294967295.0) || !(h->n >= 0 && h->n <= 4294967295.0)) return;
-    in.told_webp = true;
-    in.told_webp_w = static_cast<uint32_t>(w->n); in.told_webp_h = static_cast<uint32_t>(h->n);
-}
-struct Response {
-    int64_t status;
-    std::string json;
-};
-}  // namespace
-
-struct imageflow_json_response {                 // opaque to callers; read through imageflow_json_response_read
-    Response r;
-};
-struct imageflow_context {
-    std::mutex mu;
-    std::map<int32_t, Io> io;
-    int err_cat = kOk;
-    std::string err_msg;
-    std::vector<std::unique_ptr<imageflow_json_response>> responses;
-    std::vector<std::unique_ptr<uint8_t[]>> allocations;
-    // CancellationToken (imageflow_core/src/context.rs:50-131): a flag another thread may set while a job holds `mu`,
-    // and the reference's debug-build poll countdown ("cancel at the n-th poll", :96-104) as a test hook
-    std::atomic<bool> cancel{false};
-    std::atomic<int64_t> poll_countdown{INT64_MAX};
-    std::atomic<int64_t> fused_decode_resamples{0};
-    std::atomic<int64_t> device_coded_files{0};          // JPEG outputs whose entropy coding ran on the device (diagnostic)
-    std::atomic<int64_t> coalesced_decodes{0};           // decodes of this context that shared their device call with another thread's job
-    std::atomic<int> device{-1};                         // device ordinal its jobs run on; -1: the calling thread's current device
-    std::atomic<bool> device_jpeg_options{false};        // EXTENSION ifhip_shim_context_set_device_jpeg_options: progressive / optimised tables coded on the device
-    std::atomic<bool> gif_animation{false};              // EXTENSION ifhip_shim_context_set_gif_animation: animated GIFs run once per frame into one file
-    std::atomic<bool> gif_encoder{false};                // EXTENSION ifhip_shim_context_set_gif_encoder: the "gif" preset writes a GIF on the device
-    std::atomic<bool> webp_lossy_decoder{false};         // EXTENSION ifhip_shim_context_set_webp_lossy_decoder: lossy WebP inputs are decoded on the device
-    std::atomic<bool> color_management{false};           // EXTENSION ifhip_shim_context_set_color_management: every input is converted to sRGB
-    bool cancellation_requested() {
-        if (cancel.load(std::memory_order_relaxed)) return true;
-        if (poll_countdown.load(std::memory_order_relaxed) == INT64_MAX) return false;
-        return poll_countdown.fetch_sub(1, std::memory_order_relaxed) < 1;
-    }
-    void set_error(int cat, const std::string& m) { if (err_cat == kOk) { err_cat = cat; err_msg = m; } }   // first error sticks
-};
-
-namespace {
-
-std::string json_escape(const std::string& s) {
-    std::string o;
-    for (unsigned char c : s) {
-        if (c == '"' || c == '\\') { o.push_back('\\'); o.push_back(static_cast<char>(c)); }
-        else if (c == '\n') o += "\\n";
-        else if (c < 0x20) { char b[8]; snprintf(b, sizeof b, "\\u%04x", c); o += b; }
-        else o.push_back(static_cast<char>(c));
-    }
-    return o;
-}
 const imageflow_json_response* respond(imageflow_context* c, int64_t status, const std::string& json) {
     c->responses.emplace_back(new imageflow_json_response{Response{status, json}});
     return c->responses.back().get();
@@ -584,42 +76,6 @@ const imageflow_json_response* respond_error(imageflow_context* c, int cat, cons
     return respond(c, code, "{\n  \"code\": " + std::to_string(code) + ",\n  \"success\": false,\n  \"message\": \"" +
                                 json_escape(msg) + "\",\n  \"data\": \"none\"\n}");      // ResponsePayload::None, a unit variant renamed "none" (imageflow_types/src/lib.rs:2061-2062)
 }
-
-// ---- the job interpreter ---------------------------------------------------------------------------------------
-struct EncodeRecord { int32_t io_id; uint32_t w, h; const char* mime; const char* ext; };
-struct DecodeRecord { int32_t io_id; uint32_t w, h; const char* mime; const char* ext; };
-struct NodePerf { const char* name; uint64_t wall_ns; float gpu_ms; hipEvent_t e0, e1; };   // s::NodePerf (imageflow_types/src/lib.rs:1999-2002); e0/e1: read at the job's end
-// The hipEvents behind a node's `gpu_microseconds`, kept between jobs (two driver calls per node saved) and per device.
-struct TimingEvents {
-    std::mutex mu;
-    std::map<int, std::vector<hipEvent_t>> spare;
-    hipEvent_t take(int device) {
-        {
-            std::lock_guard<std::mutex> lk(mu);
-            auto& v = spare[device];
-            if (!v.empty()) { hipEvent_t e = v.back(); v.pop_back(); return e; }
-        }
-        hipEvent_t e = nullptr;
-        if (hipEventCreate(&e) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-        return e;
-    }
-    void give(int device, hipEvent_t e) {
-        if (!e) return;
-        std::lock_guard<std::mutex> lk(mu);
-        auto& v = spare[device];
-        if (v.size() < 256) v.push_back(e); else (void)hipEventDestroy(e);
-    }
-};
-TimingEvents& timing_events() { static TimingEvents* t = new TimingEvents; return *t; }   // (never destroyed: jobs may outlive static teardown)
-struct ResampleHints {                                                        // s::ResampleHints (lib.rs:925-933), parsed
-    bool has_sharpen = false;
-    float sharpen = 0.f;
-    int down = IFHIP_FILTER_ROBIDOUX, up = IFHIP_FILTER_GINSENG, space = IFHIP_SPACE_LINEAR;   // scale_render.rs:257-261,278-279
-    bool has_bg = false, bg_keyword_transparent = false;
-    uint32_t bg = 0;
-    enum When { kDefault, kSizeDiffers, kSizeDiffersOrSharpen, kAlways } resample_when = kDefault;
-    enum SWhen { kSAlways, kSDown, kSUp, kSSizeDiffers } sharpen_when = kSAlways;
-};
 
 // ---- decodes of different threads as ONE device call ---------------------------------------------------------------------
 // A job decodes one file: 14 workgroups of the entropy kernels for a 4K JPEG, on a chip of 256 CUs, and the HIP runtime
@@ -634,7 +90,6 @@ struct ResampleHints {                                                        //
 // took 20-35 ms each where 16 take 3: the job rate fell from 6 500 to 800 whenever more than ~20 jobs were admitted
 // (round 5, profiles/r5_abi_jobs_cliff_6_batch_cap.txt).
 constexpr uint32_t kMaxCoalesce = 16;
-std::atomic<int> g_jobs_in_flight{0};
 struct DecodeRequest {
     ifhip_jpeg_prepared* prepared = nullptr;             // the job's file, prepared on the job's own thread
     uint32_t w = 0, h = 0;
@@ -1081,27 +536,27 @@ struct Job {
             raise(kActionNotSupported, "ActionNotSupported: webp_decoder_hints %ux%u for io_id %d (%ux%u): libwebp's decode-time rescaler is not built "
                   "(the reference shrinks during the decode, codecs/webp.rs:181-188); decode at full size and resample", in.told_webp_w, in.told_webp_h, io_id, P.w, P.h);
         FramePtr f = new_frame(P.w, P.h, P.has_alpha, 0, true);                       // (max_frame_size inside)
+        const size_t bytes = f->bytes();
+        uint32_t status = 0;
+        const char* status_text = nullptr;                                            // (each decoder words its own status)
         if (!P.lossless) {
             // EXTENSION (ifhip_shim_context_set_webp_lossy_decoder): a still `VP8 ` (+ `ALPH`) file.  The host reads the key frame's header
             // and bool-decodes its partitions (csrc/vp8_read.cpp), the pixels are made in csrc/vp8_decode.hip; libwebp's default options.
             ifhip::Vp8Job J;
             ifhip::vp8_prepare_job(P, &J);                                            // on this job's thread, like webp_prepare_job
-            uint32_t status = J.frame.status;
+            status = J.frame.status;
             const ifhip::Vp8Job* job = &J;
-            const size_t bytes = f->bytes();
             if (!status) status = decoded_status("decode(webp lossy)", [&](uint32_t* d_status) { return ifhip::vp8_decode_prepared_device(&job, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream); });
-            if (status) raise(kImageMalformed, "ImageMalformed: libwebp decoding error %s (io_id %d, status %u)", ifhip::vp8_status_text(status), io_id, status);
-            if (convert) convert_to_srgb(f, color_plan);
-            decodes.push_back({io_id, P.w, P.h, "image/webp", "webp"});
-            return f;
+            if (status) status_text = ifhip::vp8_status_text(status);
+        } else {
+            ifhip::WebpJob J;
+            ifhip::webp_prepare_job(P, &J);                                           // on this job's thread, like ifhip_jpeg_entropy_prepare
+            if (J.status) raise(kImageMalformed, "ImageMalformed: libwebp decoding error %s (io_id %d, status %u)", ifhip::webp_status_text(J.status), io_id, J.status);
+            const ifhip::WebpJob* job = &J;
+            status = decoded_status("decode(webp)", [&](uint32_t* d_status) { return ifhip::webp_decode_prepared_device(&job, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream); });
+            if (status) status_text = ifhip::webp_status_text(status);
         }
-        ifhip::WebpJob J;
-        ifhip::webp_prepare_job(P, &J);                                               // on this job's thread, like ifhip_jpeg_entropy_prepare
-        if (J.status) raise(kImageMalformed, "ImageMalformed: libwebp decoding error %s (io_id %d, status %u)", ifhip::webp_status_text(J.status), io_id, J.status);
-        const ifhip::WebpJob* job = &J;
-        const size_t bytes = f->bytes();
-        const uint32_t status = decoded_status("decode(webp)", [&](uint32_t* d_status) { return ifhip::webp_decode_prepared_device(&job, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream); });
-        if (status) raise(kImageMalformed, "ImageMalformed: libwebp decoding error %s (io_id %d, status %u)", ifhip::webp_status_text(status), io_id, status);
+        if (status) raise(kImageMalformed, "ImageMalformed: libwebp decoding error %s (io_id %d, status %u)", status_text, io_id, status);
         if (convert) convert_to_srgb(f, color_plan);
         decodes.push_back({io_id, P.w, P.h, "image/webp", "webp"});
         return f;
@@ -1663,185 +1118,201 @@ struct Job {
         // that already are).  Annex K tables, libjpeg's standard scan script, no deringing, 4:2:0.
         const bool moz = coder == IFHIP_ENCODE_CODER_MOZJPEG;
         const JVal* classic = coder == IFHIP_ENCODE_CODER_JPEG ? preset->get("libjpeg_turbo") : moz ? preset->get("mozjpeg") : nullptr;
-        if (classic) {
-            auto flag = [&](const char* k) { const JVal* v = classic->get(k); return v && v->t == JVal::Bool && v->b; };
-            const int write_flags = moz ? (IFHIP_JPEG_PROGRESSIVE | IFHIP_JPEG_OPTIMIZE_HUFFMAN)
-                                        : (flag("progressive") ? IFHIP_JPEG_PROGRESSIVE : 0) | (flag("optimize_huffman_coding") ? IFHIP_JPEG_OPTIMIZE_HUFFMAN : 0);
-            const JVal* q = classic->get("quality");
-            int quality = 75;                                                            // mozjpeg.rs:32 DEFAULT_QUALITY
-            if (moz) check_mozjpeg_preset(preset);
-            if (moz && q && q->t == JVal::Num) quality = std::min(100, static_cast<int>(q->n));   // Option<u8> -> u8::min(100, ..) (mozjpeg.rs:53)
-            // Option<i32> -> `q as u8` (codecs/auto.rs:201: the value WRAPS, 300 is 44 and -5 is 251) -> u8::min(100, ..) (mozjpeg.rs:71)
-            if (!moz && q && q->t == JVal::Num) {
-                if (q->n != std::floor(q->n) || q->n < -2147483648.0 || q->n > 2147483647.0) raise(kInvalidJson, "InvalidJson: encode.preset.libjpeg_turbo.quality is a 32-bit integer");
-                quality = std::min(100, static_cast<int>(static_cast<uint8_t>(static_cast<int32_t>(q->n))));
-            }
-            const JVal* m = classic->get("matte");
-            const uint32_t matte = m && !m->is_null() ? parse_color(m, moz ? "encode.preset.mozjpeg.matte" : "encode.preset.libjpeg_turbo.matte") : 0xFFFFFFFFu;   // :88-92
-            if (shared && f->alpha) f = clone(f);
-            check(ifhip_apply_matte_batch_device(dev(f), f->bytes(), 1, f->w, f->h, f->stride, f->alpha ? 1 : 0, matte, t_job_stream));
-            f->alpha = false;                                                            // :94 set_alpha_meaningful(false)
-            const uint8_t hs[3] = {2, 1, 1}, vs[3] = {2, 1, 1};
-            uint16_t qt2[2][64], qt3[3][64];
-            ifhip_jpeg_quality_tables(quality, &qt2[0][0]);
-            std::memcpy(qt3[0], qt2[0], 128); std::memcpy(qt3[1], qt2[1], 128); std::memcpy(qt3[2], qt2[1], 128);
-            ifhip_jpeg_fwd_stage* st = nullptr;
-            check(ifhip_jpeg_fwd_stage_create(&st, f->w, f->h, hs, vs, 1));
-            std::unique_ptr<ifhip_jpeg_fwd_stage, void (*)(ifhip_jpeg_fwd_stage*)> st_guard(st, ifhip_jpeg_fwd_stage_destroy);
-            uint32_t bw[3], bh[3];
-            check(ifhip_jpeg_fwd_stage_block_dims(st, bw, bh));
-            size_t off[4] = {0, 0, 0, 0};
-            for (int k = 0; k < 3; ++k) off[k + 1] = off[k] + static_cast<size_t>(bw[k]) * bh[k] * 64u;
-            int16_t* d_coef = nullptr;
-            uint16_t* d_qt = nullptr;
-            // (the mozjpeg preset: the raw planes of the trellis stage lie behind the quantised ones)
-            hip_check(job_malloc(reinterpret_cast<void**>(&d_coef), off[3] * (moz ? 4u : 2u) + 384u), "hipMalloc(coefficients)");
-            std::unique_ptr<int16_t, void (*)(int16_t*)> coef_guard(d_coef, [](int16_t* p) { job_free(p); });
-            int16_t* d_raw = d_coef + off[3];
-            d_qt = reinterpret_cast<uint16_t*>(d_coef + off[3] * (moz ? 2u : 1u));
-            hip_check(static_cast<hipError_t>(ifhip::copy_to_device(d_qt, qt3, 384)), "upload(quant tables)");
-            if (moz) {
-                ifhip_jpeg_trellis_stage* ts = nullptr;
-                check(ifhip_jpeg_trellis_stage_create(&ts, f->w, f->h, hs, vs, 1));
-                std::unique_ptr<ifhip_jpeg_trellis_stage, void (*)(ifhip_jpeg_trellis_stage*)> ts_guard(ts, [](ifhip_jpeg_trellis_stage* q) { quiesce(); ifhip_jpeg_trellis_stage_destroy(q); });
-                check(ifhip_jpeg_forward_raw_batch_device(st, dev(f), f->bytes(), f->stride, 1, d_raw + off[0], d_raw + off[1], d_raw + off[2], t_job_stream));
-                check(ifhip_jpeg_trellis_batch_device(ts, d_raw + off[0], d_raw + off[1], d_raw + off[2], d_qt, IFHIP_JPEG_TRELLIS_LAMBDA_ONE, 1, d_coef + off[0],
-                                                      d_coef + off[1], d_coef + off[2], t_job_stream));
-            } else {
-                check(ifhip_jpeg_forward_batch_device(st, dev(f), f->bytes(), f->stride, d_qt, 1, d_coef + off[0], d_coef + off[1], d_coef + off[2], t_job_stream));
-            }
-            poll_cancel();
-            // (the mozjpeg preset goes to the device coder without the switch: that guards what older callers pinned for libjpeg_turbo)
-            if (write_flags == 0 || moz || c->device_jpeg_options.load(std::memory_order_relaxed)) {
-                // the preset's default (baseline, Annex K tables) -- and, where the caller switched it on
-                // (ifhip_shim_context_set_device_jpeg_options), progressive / optimize_huffman_coding:
-                // the device entropy coder -- only the file leaves the device.
-                // First with room for a scan half the size of its coefficients (what the host path assumes too), then, for an
-                // image that is denser than that, with the geometry's worst case.
-                for (int attempt = 0; attempt < 2; ++attempt) {
-                    const size_t scan_cap = attempt == 0 ? std::max<size_t>(65536u, off[3]) : 0u;
-                    // A geometry the coder does not take (more than 2.58 M blocks: a `security` override above ~110 MP) or a
-                    // stage that cannot be allocated is not the job's failure: the host writer below codes the same file.
-                    ifhip_jpeg_enc_stage* es = nullptr;
-                    if (ifhip_jpeg_enc_stage_create(&es, f->w, f->h, 3, hs, vs, bw, bh, 1, scan_cap) != IFHIP_OK) break;
-                    std::unique_ptr<ifhip_jpeg_enc_stage, void (*)(ifhip_jpeg_enc_stage*)> es_guard(es, [](ifhip_jpeg_enc_stage* q) { quiesce(); ifhip_jpeg_enc_stage_destroy(q); });
-                    const size_t pitch = ifhip_jpeg_enc_stage_max_file_bytes_for(es, write_flags);
-                    if (pitch == 0) break;                                               // (the flagged forms refuse the geometry)
-                    CodedFile file;
-                    if (file.alloc(pitch, (pitch + 3u) & ~static_cast<size_t>(3u)) != hipSuccess) break;
-                    // (a flagged call allocates its scratch first; where that fails the host writer codes the file)
-                    const int erc = ifhip_jpeg_encode_flags_batch_device(es, d_coef + off[0], d_coef + off[1], d_coef + off[2], quality, write_flags, 1, file.d,
-                                                                         pitch, file.d_len, file.d_len + 1, t_job_stream);
-                    if (erc != IFHIP_OK && write_flags != 0) break;
-                    check(erc);
-                    file.fetch(o);
-                    if (file.status & IFHIP_ENC_BAD_COEFFICIENT)
-                        raise(kArgumentInvalid, "InvalidArgument: coefficient out of range for 8-bit JPEG (more than 11 DC / 10 AC magnitude bits)");
-                    if (file.status != 0) continue;
-                    o.written = true;
-                    encodes.push_back({io_id, f->w, f->h, "image/jpeg", "jpg"});
-                    c->device_coded_files.fetch_add(1, std::memory_order_relaxed);
-                    return;
-                }
-            }                                                                            // (not coded on the device: the host writer)
-            std::vector<int16_t> coef(off[3]);
-            hip_check(static_cast<hipError_t>(ifhip::copy_to_host(coef.data(), d_coef, off[3] * 2u)), "download(coefficients)");
-            size_t len = 0;
-            o.owned.assign(std::max<size_t>(4096u, off[3]), 0);                          // a file is smaller than its coefficients: one pass
-            int wrc = ifhip_jpeg_write(coef.data() + off[0], coef.data() + off[1], coef.data() + off[2], bw, bh, 3, hs, vs, f->w, f->h, quality, write_flags,
-                                       o.owned.data(), o.owned.size(), &len);
-            if (wrc != IFHIP_OK && len > o.owned.size()) {
-                o.owned.assign(len, 0);
-                wrc = ifhip_jpeg_write(coef.data() + off[0], coef.data() + off[1], coef.data() + off[2], bw, bh, 3, hs, vs, f->w, f->h, quality, write_flags,
-                                       o.owned.data(), o.owned.size(), &len);
-            }
-            check(wrc);
-            o.owned.resize(len);
-            o.written = true;
-            encodes.push_back({io_id, f->w, f->h, "image/jpeg", "jpg"});
-            return;
+        if (classic) return encode_jpeg(f, o, io_id, preset, classic, moz, shared);
+        if (const JVal* png = coder == IFHIP_ENCODE_CODER_PNG ? preset->get("libpng") : nullptr) return encode_png(f, o, io_id, png, shared);
+        if (const JVal* pq = coder == IFHIP_ENCODE_CODER_PNGQUANT ? preset->get("pngquant") : nullptr) return encode_pngquant(f, o, io_id, pq);
+        if (coder == IFHIP_ENCODE_CODER_WEBP_LOSSLESS) return encode_webp_lossless(f, o, io_id);
+        if (preset && preset->t == JVal::Str && preset->s == "gif" && c->gif_encoder.load(std::memory_order_relaxed)) return encode_gif(f, o, io_id);
+        encode_raw(f, o, io_id);
+    }
+
+    // the libjpeg_turbo and mozjpeg presets: `classic` is the preset's object
+    void encode_jpeg(FramePtr f, Io& o, int32_t io_id, const JVal* preset, const JVal* classic, bool moz, bool shared) {
+        auto flag = [&](const char* k) { const JVal* v = classic->get(k); return v && v->t == JVal::Bool && v->b; };
+        const int write_flags = moz ? (IFHIP_JPEG_PROGRESSIVE | IFHIP_JPEG_OPTIMIZE_HUFFMAN)
+                                    : (flag("progressive") ? IFHIP_JPEG_PROGRESSIVE : 0) | (flag("optimize_huffman_coding") ? IFHIP_JPEG_OPTIMIZE_HUFFMAN : 0);
+        const JVal* q = classic->get("quality");
+        int quality = 75;                                                            // mozjpeg.rs:32 DEFAULT_QUALITY
+        if (moz) check_mozjpeg_preset(preset);
+        if (moz && q && q->t == JVal::Num) quality = std::min(100, static_cast<int>(q->n));   // Option<u8> -> u8::min(100, ..) (mozjpeg.rs:53)
+        // Option<i32> -> `q as u8` (codecs/auto.rs:201: the value WRAPS, 300 is 44 and -5 is 251) -> u8::min(100, ..) (mozjpeg.rs:71)
+        if (!moz && q && q->t == JVal::Num) {
+            if (q->n != std::floor(q->n) || q->n < -2147483648.0 || q->n > 2147483647.0) raise(kInvalidJson, "InvalidJson: encode.preset.libjpeg_turbo.quality is a 32-bit integer");
+            quality = std::min(100, static_cast<int>(static_cast<uint8_t>(static_cast<int32_t>(q->n))));
         }
-        if (const JVal* png = coder == IFHIP_ENCODE_CODER_PNG ? preset->get("libpng") : nullptr) {
-            // EncoderPreset::Libpng {depth, matte, zlib_compression} (imageflow_types/src/lib.rs:751-755, codecs/auto.rs:241-268)
-            // -> LibPngEncoder::write_frame (codecs/libpng_encoder.rs:43-72): the file is coded on the device
-            // (csrc/png_encode.hip), only its bytes leave it.
-            int color_type = -1;                                                         // by the frame's alpha, below
-            if (const JVal* d = png->get("depth"); d && !d->is_null()) {
-                if (d->t != JVal::Str || (d->s != "png_32" && d->s != "png_24")) raise(kInvalidJson, "InvalidJson: encode.preset.libpng.depth is \"png_32\" or \"png_24\"");
-                if (d->s == "png_24") color_type = IFHIP_PNG_RGB;
-            }
-            int level = -1;                                                              // absent: zlib's default (6)
-            if (const JVal* z = png->get("zlib_compression"); z && !z->is_null()) {
-                if (z->t != JVal::Num || z->n != std::floor(z->n) || z->n < -2147483648.0 || z->n > 2147483647.0)
-                    raise(kInvalidJson, "InvalidJson: encode.preset.libpng.zlib_compression is a 32-bit integer");
-                // i32 clamped to 0..255 (auto.rs:265); above 9 libpng is left at its default (codec_png_wrapper.c:380-387)
-                const int v = static_cast<int>(std::min(255.0, std::max(0.0, z->n)));
-                level = v > 9 ? -1 : v;
-            }
-            const JVal* m = png->get("matte");
-            if (m && !m->is_null() && f->alpha) {                                       // libpng_encoder.rs:55-57, bitmaps.rs:528-541
-                const uint32_t matte = parse_color(m, "encode.preset.libpng.matte");
-                if (shared) f = clone(f);
-                check(ifhip_apply_matte_batch_device(dev(f), f->bytes(), 1, f->w, f->h, f->stride, 1, matte, t_job_stream));
-                if ((matte >> 24) == 0xFFu) f->alpha = false;                            // matte.is_opaque(): set_alpha_meaningful(false)
-            } else if (m && !m->is_null()) {
-                (void)parse_color(m, "encode.preset.libpng.matte");                      // (still parsed: a malformed colour is an error)
-            }
-            if (color_type < 0) color_type = f->alpha ? IFHIP_PNG_RGBA : IFHIP_PNG_RGB;  // codec_png_wrapper.c:402-410
-            write_png(f, color_type, level, o, io_id);
-            return;
+        const JVal* m = classic->get("matte");
+        const uint32_t matte = m && !m->is_null() ? parse_color(m, moz ? "encode.preset.mozjpeg.matte" : "encode.preset.libjpeg_turbo.matte") : 0xFFFFFFFFu;   // :88-92
+        if (shared && f->alpha) f = clone(f);
+        check(ifhip_apply_matte_batch_device(dev(f), f->bytes(), 1, f->w, f->h, f->stride, f->alpha ? 1 : 0, matte, t_job_stream));
+        f->alpha = false;                                                            // :94 set_alpha_meaningful(false)
+        const uint8_t hs[3] = {2, 1, 1}, vs[3] = {2, 1, 1};
+        uint16_t qt2[2][64], qt3[3][64];
+        ifhip_jpeg_quality_tables(quality, &qt2[0][0]);
+        std::memcpy(qt3[0], qt2[0], 128); std::memcpy(qt3[1], qt2[1], 128); std::memcpy(qt3[2], qt2[1], 128);
+        ifhip_jpeg_fwd_stage* st = nullptr;
+        check(ifhip_jpeg_fwd_stage_create(&st, f->w, f->h, hs, vs, 1));
+        std::unique_ptr<ifhip_jpeg_fwd_stage, void (*)(ifhip_jpeg_fwd_stage*)> st_guard(st, ifhip_jpeg_fwd_stage_destroy);
+        uint32_t bw[3], bh[3];
+        check(ifhip_jpeg_fwd_stage_block_dims(st, bw, bh));
+        size_t off[4] = {0, 0, 0, 0};
+        for (int k = 0; k < 3; ++k) off[k + 1] = off[k] + static_cast<size_t>(bw[k]) * bh[k] * 64u;
+        int16_t* d_coef = nullptr;
+        uint16_t* d_qt = nullptr;
+        // (the mozjpeg preset: the raw planes of the trellis stage lie behind the quantised ones)
+        hip_check(job_malloc(reinterpret_cast<void**>(&d_coef), off[3] * (moz ? 4u : 2u) + 384u), "hipMalloc(coefficients)");
+        std::unique_ptr<int16_t, void (*)(int16_t*)> coef_guard(d_coef, [](int16_t* p) { job_free(p); });
+        int16_t* d_raw = d_coef + off[3];
+        d_qt = reinterpret_cast<uint16_t*>(d_coef + off[3] * (moz ? 2u : 1u));
+        hip_check(static_cast<hipError_t>(ifhip::copy_to_device(d_qt, qt3, 384)), "upload(quant tables)");
+        if (moz) {
+            ifhip_jpeg_trellis_stage* ts = nullptr;
+            check(ifhip_jpeg_trellis_stage_create(&ts, f->w, f->h, hs, vs, 1));
+            std::unique_ptr<ifhip_jpeg_trellis_stage, void (*)(ifhip_jpeg_trellis_stage*)> ts_guard(ts, [](ifhip_jpeg_trellis_stage* q) { quiesce(); ifhip_jpeg_trellis_stage_destroy(q); });
+            check(ifhip_jpeg_forward_raw_batch_device(st, dev(f), f->bytes(), f->stride, 1, d_raw + off[0], d_raw + off[1], d_raw + off[2], t_job_stream));
+            check(ifhip_jpeg_trellis_batch_device(ts, d_raw + off[0], d_raw + off[1], d_raw + off[2], d_qt, IFHIP_JPEG_TRELLIS_LAMBDA_ONE, 1, d_coef + off[0],
+                                                  d_coef + off[1], d_coef + off[2], t_job_stream));
+        } else {
+            check(ifhip_jpeg_forward_batch_device(st, dev(f), f->bytes(), f->stride, d_qt, 1, d_coef + off[0], d_coef + off[1], d_coef + off[2], t_job_stream));
         }
-        if (const JVal* pq = coder == IFHIP_ENCODE_CODER_PNGQUANT ? preset->get("pngquant") : nullptr) {
-            // EncoderPreset::Pngquant {quality, minimum_quality, speed, maximum_deflate} (imageflow_types/src/lib.rs:756-761)
-            // -> PngquantEncoder (codecs/pngquant.rs:35-139): quantised, dithered and written as a palette PNG on the device
-            // (csrc/png_quantize.hip); no matte (codecs/auto.rs:98-110).  The three numbers are u8.
-            auto u8_option = [&](const char* key) -> int {
-                const JVal* v = pq->get(key);
-                if (!v || v->is_null()) return -1;
-                if (v->t != JVal::Num || v->n != std::floor(v->n) || v->n < 0.0 || v->n > 255.0) raise(kInvalidJson, "InvalidJson: encode.preset.pngquant.%s is an integer in 0..255", key);
-                return static_cast<int>(v->n);
-            };
-            const int quality = u8_option("quality"), min_quality = u8_option("minimum_quality"), speed = u8_option("speed");
-            bool maximum_deflate = false;
-            if (const JVal* z = pq->get("maximum_deflate"); z && !z->is_null()) {
-                if (z->t != JVal::Bool) raise(kInvalidJson, "InvalidJson: encode.preset.pngquant.maximum_deflate is a boolean");
-                maximum_deflate = z->b;
+        poll_cancel();
+        // (the mozjpeg preset goes to the device coder without the switch: that guards what older callers pinned for libjpeg_turbo)
+        if (write_flags == 0 || moz || c->device_jpeg_options.load(std::memory_order_relaxed)) {
+            // the preset's default (baseline, Annex K tables) -- and, where the caller switched it on
+            // (ifhip_shim_context_set_device_jpeg_options), progressive / optimize_huffman_coding:
+            // the device entropy coder -- only the file leaves the device.
+            // First with room for a scan half the size of its coefficients (what the host path assumes too), then, for an
+            // image that is denser than that, with the geometry's worst case.
+            for (int attempt = 0; attempt < 2; ++attempt) {
+                const size_t scan_cap = attempt == 0 ? std::max<size_t>(65536u, off[3]) : 0u;
+                // A geometry the coder does not take (more than 2.58 M blocks: a `security` override above ~110 MP) or a
+                // stage that cannot be allocated is not the job's failure: the host writer below codes the same file.
+                ifhip_jpeg_enc_stage* es = nullptr;
+                if (ifhip_jpeg_enc_stage_create(&es, f->w, f->h, 3, hs, vs, bw, bh, 1, scan_cap) != IFHIP_OK) break;
+                std::unique_ptr<ifhip_jpeg_enc_stage, void (*)(ifhip_jpeg_enc_stage*)> es_guard(es, [](ifhip_jpeg_enc_stage* q) { quiesce(); ifhip_jpeg_enc_stage_destroy(q); });
+                const size_t pitch = ifhip_jpeg_enc_stage_max_file_bytes_for(es, write_flags);
+                if (pitch == 0) break;                                               // (the flagged forms refuse the geometry)
+                CodedFile file;
+                if (file.alloc(pitch, (pitch + 3u) & ~static_cast<size_t>(3u)) != hipSuccess) break;
+                // (a flagged call allocates its scratch first; where that fails the host writer codes the file)
+                const int erc = ifhip_jpeg_encode_flags_batch_device(es, d_coef + off[0], d_coef + off[1], d_coef + off[2], quality, write_flags, 1, file.d,
+                                                                     pitch, file.d_len, file.d_len + 1, t_job_stream);
+                if (erc != IFHIP_OK && write_flags != 0) break;
+                check(erc);
+                file.fetch(o);
+                if (file.status & IFHIP_ENC_BAD_COEFFICIENT)
+                    raise(kArgumentInvalid, "InvalidArgument: coefficient out of range for 8-bit JPEG (more than 11 DC / 10 AC magnitude bits)");
+                if (file.status != 0) continue;
+                o.written = true;
+                encodes.push_back({io_id, f->w, f->h, "image/jpeg", "jpg"});
+                c->device_coded_files.fetch_add(1, std::memory_order_relaxed);
+                return;
             }
-            const int level = maximum_deflate ? 9 : 6;                                    // lode.rs:162-195
-            const uint32_t status = write_coded_frame(
-                f, o, io_id, kPalettePngNames, IFHIP_PNG_QUALITY_TOO_LOW, [&](ifhip_png_quant_stage** s) { return ifhip_png_quant_stage_create(s, f->w, f->h, 1); },
-                ifhip_png_quant_stage_destroy, ifhip_png_quant_stage_max_file_bytes, [&](ifhip_png_quant_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
-                    return ifhip_png_quantize_batch_device(s, dev(f), f->bytes(), f->stride, f->alpha ? 1 : 0, 1, quality, min_quality, speed, 256, 1, level, d_file, pitch,
-                                                           d_len, d_len + 1, nullptr, nullptr, nullptr, t_job_stream);
-                });
-            // pngquant.rs:105-139: below minimum_quality the frame is written losslessly, RGBA or RGB by its alpha
-            if (status == IFHIP_PNG_QUALITY_TOO_LOW) write_png(f, f->alpha ? IFHIP_PNG_RGBA : IFHIP_PNG_RGB, level, o, io_id);
-            return;
+        }                                                                            // (not coded on the device: the host writer)
+        write_jpeg_on_host(f, o, io_id, d_coef, off, bw, bh, hs, vs, quality, write_flags);
+    }
+    // the coefficients back to the host, Huffman coding and markers there (csrc/jpeg_write.cpp)
+    void write_jpeg_on_host(const FramePtr& f, Io& o, int32_t io_id, const int16_t* d_coef, const size_t off[4], const uint32_t bw[3], const uint32_t bh[3],
+                            const uint8_t hs[3], const uint8_t vs[3], int quality, int write_flags) {
+        std::vector<int16_t> coef(off[3]);
+        hip_check(static_cast<hipError_t>(ifhip::copy_to_host(coef.data(), d_coef, off[3] * 2u)), "download(coefficients)");
+        size_t len = 0;
+        o.owned.assign(std::max<size_t>(4096u, off[3]), 0);                          // a file is smaller than its coefficients: one pass
+        int wrc = ifhip_jpeg_write(coef.data() + off[0], coef.data() + off[1], coef.data() + off[2], bw, bh, 3, hs, vs, f->w, f->h, quality, write_flags,
+                                   o.owned.data(), o.owned.size(), &len);
+        if (wrc != IFHIP_OK && len > o.owned.size()) {
+            o.owned.assign(len, 0);
+            wrc = ifhip_jpeg_write(coef.data() + off[0], coef.data() + off[1], coef.data() + off[2], bw, bh, 3, hs, vs, f->w, f->h, quality, write_flags,
+                                   o.owned.data(), o.owned.size(), &len);
         }
-        if (coder == IFHIP_ENCODE_CODER_WEBP_LOSSLESS) {
-            // EncoderPreset::WebPLossless (imageflow_types/src/lib.rs:773, codecs/auto.rs:282-319) -> WebPEncoder::write_frame
-            // (codecs/webp.rs:281-345: WebPEncodeLosslessBGRA, or ...BGR when the frame's alpha is not meaningful); no matte
-            // (the reference passes None).  The file is coded on the device (csrc/webp_encode.hip), only its bytes leave it.
-            write_coded_frame(
-                f, o, io_id, kWebpNames, 0u, [&](ifhip_webp_enc_stage** s) { return ifhip_webp_enc_stage_create(s, f->w, f->h, f->alpha ? 1 : 0, 1); },
-                ifhip_webp_enc_stage_destroy, ifhip_webp_enc_stage_max_file_bytes, [&](ifhip_webp_enc_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
-                    return ifhip_webp_encode_batch_device(s, dev(f), f->bytes(), f->stride, 1, d_file, pitch, d_len, d_len + 1, t_job_stream);
-                });
-            return;
+        check(wrc);
+        o.owned.resize(len);
+        o.written = true;
+        encodes.push_back({io_id, f->w, f->h, "image/jpeg", "jpg"});
+        return;
+    }
+    void encode_png(FramePtr f, Io& o, int32_t io_id, const JVal* png, bool shared) {
+        // EncoderPreset::Libpng {depth, matte, zlib_compression} (imageflow_types/src/lib.rs:751-755, codecs/auto.rs:241-268)
+        // -> LibPngEncoder::write_frame (codecs/libpng_encoder.rs:43-72): the file is coded on the device
+        // (csrc/png_encode.hip), only its bytes leave it.
+        int color_type = -1;                                                         // by the frame's alpha, below
+        if (const JVal* d = png->get("depth"); d && !d->is_null()) {
+            if (d->t != JVal::Str || (d->s != "png_32" && d->s != "png_24")) raise(kInvalidJson, "InvalidJson: encode.preset.libpng.depth is \"png_32\" or \"png_24\"");
+            if (d->s == "png_24") color_type = IFHIP_PNG_RGB;
         }
-        if (preset && preset->t == JVal::Str && preset->s == "gif" && c->gif_encoder.load(std::memory_order_relaxed)) {
-            // EXTENSION (ifhip_shim_context_set_gif_encoder): EncoderPreset::Gif -> GifEncoder::write_frame (codecs/gif/mod.rs:385-592):
-            // the alpha rule, the palette and the LZW stream on the device (csrc/gif_encode.hip), only the file leaves it.  The
-            // frame itself is left as it is (the rule is applied where the pixels are read); a side above 65535 is size_16()'s
-            // InvalidArgument.  A GIF decoder of the job hands on its repeat count and its last frame's delay and user-input flag.
-            write_coded_frame(
-                f, o, io_id, kGifNames, 0u, [&](ifhip_gif_enc_stage** s) { return ifhip_gif_enc_stage_create(s, f->w, f->h, 1); }, ifhip_gif_enc_stage_destroy,
-                ifhip_gif_enc_stage_max_file_bytes, [&](ifhip_gif_enc_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
-                    return ifhip_gif_encode_batch_device(s, dev(f), f->bytes(), f->stride, f->alpha ? 1 : 0, 1, gif_source.seen ? gif_source.repeat : -1, gif_source.delay,
-                                                         gif_source.user_input ? 1 : 0, d_file, pitch, d_len, d_len + 1, nullptr, nullptr, t_job_stream);
-                });
-            return;
+        int level = -1;                                                              // absent: zlib's default (6)
+        if (const JVal* z = png->get("zlib_compression"); z && !z->is_null()) {
+            if (z->t != JVal::Num || z->n != std::floor(z->n) || z->n < -2147483648.0 || z->n > 2147483647.0)
+                raise(kInvalidJson, "InvalidJson: encode.preset.libpng.zlib_compression is a 32-bit integer");
+            // i32 clamped to 0..255 (auto.rs:265); above 9 libpng is left at its default (codec_png_wrapper.c:380-387)
+            const int v = static_cast<int>(std::min(255.0, std::max(0.0, z->n)));
+            level = v > 9 ? -1 : v;
         }
+        const JVal* m = png->get("matte");
+        if (m && !m->is_null() && f->alpha) {                                       // libpng_encoder.rs:55-57, bitmaps.rs:528-541
+            const uint32_t matte = parse_color(m, "encode.preset.libpng.matte");
+            if (shared) f = clone(f);
+            check(ifhip_apply_matte_batch_device(dev(f), f->bytes(), 1, f->w, f->h, f->stride, 1, matte, t_job_stream));
+            if ((matte >> 24) == 0xFFu) f->alpha = false;                            // matte.is_opaque(): set_alpha_meaningful(false)
+        } else if (m && !m->is_null()) {
+            (void)parse_color(m, "encode.preset.libpng.matte");                      // (still parsed: a malformed colour is an error)
+        }
+        if (color_type < 0) color_type = f->alpha ? IFHIP_PNG_RGBA : IFHIP_PNG_RGB;  // codec_png_wrapper.c:402-410
+        write_png(f, color_type, level, o, io_id);
+        return;
+    }
+    void encode_pngquant(const FramePtr& f, Io& o, int32_t io_id, const JVal* pq) {
+        // EncoderPreset::Pngquant {quality, minimum_quality, speed, maximum_deflate} (imageflow_types/src/lib.rs:756-761)
+        // -> PngquantEncoder (codecs/pngquant.rs:35-139): quantised, dithered and written as a palette PNG on the device
+        // (csrc/png_quantize.hip); no matte (codecs/auto.rs:98-110).  The three numbers are u8.
+        auto u8_option = [&](const char* key) -> int {
+            const JVal* v = pq->get(key);
+            if (!v || v->is_null()) return -1;
+            if (v->t != JVal::Num || v->n != std::floor(v->n) || v->n < 0.0 || v->n > 255.0) raise(kInvalidJson, "InvalidJson: encode.preset.pngquant.%s is an integer in 0..255", key);
+            return static_cast<int>(v->n);
+        };
+        const int quality = u8_option("quality"), min_quality = u8_option("minimum_quality"), speed = u8_option("speed");
+        bool maximum_deflate = false;
+        if (const JVal* z = pq->get("maximum_deflate"); z && !z->is_null()) {
+            if (z->t != JVal::Bool) raise(kInvalidJson, "InvalidJson: encode.preset.pngquant.maximum_deflate is a boolean");
+            maximum_deflate = z->b;
+        }
+        const int level = maximum_deflate ? 9 : 6;                                    // lode.rs:162-195
+        const uint32_t status = write_coded_frame(
+            f, o, io_id, kPalettePngNames, IFHIP_PNG_QUALITY_TOO_LOW, [&](ifhip_png_quant_stage** s) { return ifhip_png_quant_stage_create(s, f->w, f->h, 1); },
+            ifhip_png_quant_stage_destroy, ifhip_png_quant_stage_max_file_bytes, [&](ifhip_png_quant_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
+                return ifhip_png_quantize_batch_device(s, dev(f), f->bytes(), f->stride, f->alpha ? 1 : 0, 1, quality, min_quality, speed, 256, 1, level, d_file, pitch,
+                                                       d_len, d_len + 1, nullptr, nullptr, nullptr, t_job_stream);
+            });
+        // pngquant.rs:105-139: below minimum_quality the frame is written losslessly, RGBA or RGB by its alpha
+        if (status == IFHIP_PNG_QUALITY_TOO_LOW) write_png(f, f->alpha ? IFHIP_PNG_RGBA : IFHIP_PNG_RGB, level, o, io_id);
+        return;
+    }
+    void encode_webp_lossless(const FramePtr& f, Io& o, int32_t io_id) {
+        // EncoderPreset::WebPLossless (imageflow_types/src/lib.rs:773, codecs/auto.rs:282-319) -> WebPEncoder::write_frame
+        // (codecs/webp.rs:281-345: WebPEncodeLosslessBGRA, or ...BGR when the frame's alpha is not meaningful); no matte
+        // (the reference passes None).  The file is coded on the device (csrc/webp_encode.hip), only its bytes leave it.
+        write_coded_frame(
+            f, o, io_id, kWebpNames, 0u, [&](ifhip_webp_enc_stage** s) { return ifhip_webp_enc_stage_create(s, f->w, f->h, f->alpha ? 1 : 0, 1); },
+            ifhip_webp_enc_stage_destroy, ifhip_webp_enc_stage_max_file_bytes, [&](ifhip_webp_enc_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
+                return ifhip_webp_encode_batch_device(s, dev(f), f->bytes(), f->stride, 1, d_file, pitch, d_len, d_len + 1, t_job_stream);
+            });
+        return;
+    }
+    void encode_gif(const FramePtr& f, Io& o, int32_t io_id) {
+        // EXTENSION (ifhip_shim_context_set_gif_encoder): EncoderPreset::Gif -> GifEncoder::write_frame (codecs/gif/mod.rs:385-592):
+        // the alpha rule, the palette and the LZW stream on the device (csrc/gif_encode.hip), only the file leaves it.  The
+        // frame itself is left as it is (the rule is applied where the pixels are read); a side above 65535 is size_16()'s
+        // InvalidArgument.  A GIF decoder of the job hands on its repeat count and its last frame's delay and user-input flag.
+        write_coded_frame(
+            f, o, io_id, kGifNames, 0u, [&](ifhip_gif_enc_stage** s) { return ifhip_gif_enc_stage_create(s, f->w, f->h, 1); }, ifhip_gif_enc_stage_destroy,
+            ifhip_gif_enc_stage_max_file_bytes, [&](ifhip_gif_enc_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
+                return ifhip_gif_encode_batch_device(s, dev(f), f->bytes(), f->stride, f->alpha ? 1 : 0, 1, gif_source.seen ? gif_source.repeat : -1, gif_source.delay,
+                                                     gif_source.user_input ? 1 : 0, d_file, pitch, d_len, d_len + 1, nullptr, nullptr, t_job_stream);
+            });
+        return;
+    }
+    // EXTENSION: the raw BGRA container
+    void encode_raw(const FramePtr& f, Io& o, int32_t io_id) {
         o.owned.assign(kRawHeader + f->bytes(), 0);
         std::memcpy(o.owned.data(), kRawMagic, 8);
         const uint32_t hdr[4] = {f->w, f->h, f->stride, f->alpha ? 1u : 0u};
@@ -2023,23 +1494,22 @@ struct Job {
         if (name == "decode") {
             uint32_t hw = 0, hh = 0;
             bool spatial = false, gamma = false;
-            {
-                const Io& told = input(static_cast<int32_t>(want_int(p, "io_id", "decode")));
-                if (told.told) { hw = told.told_w; hh = told.told_h; spatial = told.told_spatial; gamma = told.told_gamma; }
-            }
+            const int32_t io_id = static_cast<int32_t>(want_int(p, "io_id", "decode"));
+            Io& src = input(io_id);
+            if (src.told) { hw = src.told_w; hh = src.told_h; spatial = src.told_spatial; gamma = src.told_gamma; }
             if (const JVal* cmds = p.get("commands")) {
                 if (cmds->t == JVal::Arr) {
                     for (const JVal& cmd : cmds->a) {
                         if (cmd.t == JVal::Str && cmd.s == "discard_color_profile") {
-                            input(static_cast<int32_t>(want_int(p, "io_id", "decode"))).told_discard_profile = true;
+                            src.told_discard_profile = true;
                         } else if (cmd.t == JVal::Str && cmd.s == "ignore_color_profile_errors") {
-                            input(static_cast<int32_t>(want_int(p, "io_id", "decode"))).told_ignore_profile_errors = true;
+                            src.told_ignore_profile_errors = true;
                         } else if (cmd.t == JVal::Str && cmd.s == "convert_color_profile") {  // EXTENSION: colour management for this input
-                            input(static_cast<int32_t>(want_int(p, "io_id", "decode"))).told_convert_profile = true;
+                            src.told_convert_profile = true;
                         } else if (const JVal* j = cmd.get("select_frame")) {                // s::DecoderCommand::SelectFrame(i32): a GIF input acts on it
-                            tell_select_frame(input(static_cast<int32_t>(want_int(p, "io_id", "decode"))), *j);
+                            tell_select_frame(src, *j);
                         } else if (const JVal* j = cmd.get("webp_decoder_hints")) {          // s::WebPDecoderHints {width, height}
-                            tell_webp_hint(input(static_cast<int32_t>(want_int(p, "io_id", "decode"))), *j);
+                            tell_webp_hint(src, *j);
                         } else if (const JVal* j = cmd.get("jpeg_downscale_hints")) {        // s::JpegIDCTDownscaleHints
                             hw = want_u32(*j, "width", "jpeg_downscale_hints"); hh = want_u32(*j, "height", "jpeg_downscale_hints");
                             if (const JVal* b = j->get("scale_luma_spatially")) spatial = b->t == JVal::Bool && b->b;
@@ -2049,7 +1519,7 @@ struct Job {
                 }
             }
             anim.in_decode_node = true;                                              // (a watermark's or a command_string's own decode does not animate)
-            FramePtr f = decode_oriented(static_cast<int32_t>(want_int(p, "io_id", "decode")), hw, hh, spatial, gamma);
+            FramePtr f = decode_oriented(io_id, hw, hh, spatial, gamma);
             anim.in_decode_node = false;
             return f;
         }

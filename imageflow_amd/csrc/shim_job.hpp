@@ -1,0 +1,188 @@
+// shim_job.hpp -- what a job of the ABI shim (abi_shim.cpp) works on: frames in HBM, the limits, the io table, the context,
+// the records of a job's result and the parsed resample hints.  (The interpreter itself, `Job`, is still defined in abi_shim.cpp.)
+#pragma once
+#include <atomic>
+#include <chrono>
+#include <climits>
+#include <cstdint>
+#include <cstring>
+#include <map>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/imageflow_abi_subset.h"
+#include "../../include/imageflow_hip.h"
+#include "common.hpp"           // the library's per-job memory cache and thread stream (devmem.cpp)
+#include "shim_json.hpp"
+#include "shim_runtime.hpp"
+
+namespace ifshim {
+
+// ---- frames in HBM ---------------------------------------------------------------------------------------------
+// A decoded JPEG whose pixel stage has not run: when the frame's one consumer is a resample, decode and resample run as ONE
+// device call (ifhip_jpeg_decode_resample_batch_device: no decoded BGRA bitmap in HBM); any other consumer gets the bitmap
+// through Job::dev(), which runs the pixel stage then.
+// The coefficient planes and quantisation tables of one entropy-decoded BATCH of files (one geometry): jobs of different
+// threads whose decodes were coalesced into one device call each hold a share and read their own image's part.
+struct DecodedBatch {
+    int16_t* coef[3] = {nullptr, nullptr, nullptr};      // [n][bh_c][bw_c][64]
+    size_t per_image[3] = {0, 0, 0};                     // int16 elements per image and component
+    uint16_t* d_qt = nullptr;                            // [n][3][64]
+    uint32_t w = 0, h = 0, bw[3] = {0, 0, 0}, bh[3] = {0, 0, 0};
+    int ncomp = 0;
+    uint8_t hs[3] = {1, 1, 1}, vs[3] = {1, 1, 1};
+    // the last share goes when its job ends -- every job waits for its own stream before it lets go (quiesce), the
+    // batch's decode itself was complete before any share was handed out
+    // (... and on an error path between the decode's launch and its wait this destructor IS the wait: the planes may not
+    // go back to the cache with the decode still writing them)
+    ~DecodedBatch() {
+        quiesce();
+        for (int16_t* p : coef) if (p) (void)ifhip::cached_free(p);
+        if (d_qt) (void)ifhip::cached_free(d_qt);
+    }
+};
+struct PendingJpeg {
+    ifhip_jpeg_stage* st = nullptr;
+    int16_t* coef[3] = {nullptr, nullptr, nullptr};      // this image's planes inside `batch`
+    uint16_t* d_qt = nullptr;
+    std::shared_ptr<DecodedBatch> batch;
+    ~PendingJpeg() {
+        quiesce();
+        if (st) ifhip_jpeg_stage_destroy(st);
+        ifhip::QuiescedScope q;                          // (a job thread has one already; a share that dies elsewhere: see above)
+        batch.reset();
+    }
+};
+struct Frame {                                   // graphics/bitmaps.rs Bitmap: BGRA8, 64-byte row stride
+    uint8_t* d = nullptr;                        // (null while `pending`: read it through Job::dev())
+    uint32_t w = 0, h = 0, stride = 0;
+    bool alpha = false;
+    int compose = IFHIP_REPLACE_SELF;
+    uint32_t matte = 0;
+    std::unique_ptr<PendingJpeg> pending;
+    size_t bytes() const { return static_cast<size_t>(h) * stride; }
+    ~Frame() { job_free(d); }
+};
+using FramePtr = std::shared_ptr<Frame>;
+
+// ExecutionSecurity (imageflow_types/src/lib.rs:1199-1236): the two limits that bound what this library allocates;
+// defaults = sane_defaults(), a job may override them with `security` (v1/execute) / `builder_config.security` (v1/build)
+struct SizeLimit { uint32_t w, h; float megapixels; };
+struct Security {
+    SizeLimit max_decode_size{12000, 12000, 100.f};
+    SizeLimit max_frame_size{10000, 10000, 100.f};
+    // Option<u64>, sane_defaults() 400 megapixels (lib.rs:1212-1235): frame count x width x height of an animation
+    // (GifDecoder::check_total_pixels, codecs/gif/mod.rs:103-118).  Read by the animation path alone.
+    bool has_max_total_file_pixels = true;
+    uint64_t max_total_file_pixels = 400000000ull;
+};
+// Engine::validate_frame_size (flow/execution_engine.rs:286-325); ErrorKind::SizeLimitExceeded -> ArgumentInvalid
+inline void check_size(const SizeLimit& lim, const char* what, uint64_t w, uint64_t h) {
+    if (w > lim.w) raise(kArgumentInvalid, "SizeLimitExceeded: Frame width %llu exceeds %s.w %u", static_cast<unsigned long long>(w), what, lim.w);
+    if (h > lim.h) raise(kArgumentInvalid, "SizeLimitExceeded: Frame height %llu exceeds %s.h %u", static_cast<unsigned long long>(h), what, lim.h);
+    const float mp = static_cast<float>(w) * static_cast<float>(h) / 1000000.f;
+    if (mp > lim.megapixels) raise(kArgumentInvalid, "SizeLimitExceeded: Frame megapixels %f exceeds %s.megapixels %f", static_cast<double>(mp), what, static_cast<double>(lim.megapixels));
+}
+
+constexpr char kRawMagic[8] = {'I', 'F', 'B', 'G', 'R', 'A', '1', '\0'};
+constexpr size_t kRawHeader = 8 + 16;
+
+// ---- context -----------------------------------------------------------------------------------------------------
+// Output buffers: Ready -> (get_output_buffer_by_id) Lent -> stays Lent; Ready -> (take_output_buffer) Taken
+// (CodecInstanceContainer, imageflow_core/src/codecs/mod.rs:421-436,560-626)
+enum class OutState { Ready, Lent, Taken };
+struct Io {
+    bool is_output = false;
+    const uint8_t* in = nullptr;
+    size_t in_len = 0;
+    std::vector<uint8_t> owned;                  // copied inputs (lifetime_outlives_function_call) / output bytes
+    bool written = false;
+    OutState out_state = OutState::Ready;
+    // v1/tell_decoder {jpeg_downscale_hints} (Context::tell_decoder -> MzDec::tell_decoder, mozjpeg_decoder.rs:560-586): kept
+    // with the input until its decoder runs; a decode node's own `commands` are told after these and win
+    bool out_base64 = false;                     // IoEnum::OutputBase64: the job result carries the bytes as {"base_64": ...}
+    bool told = false;
+    uint32_t told_w = 0, told_h = 0;
+    bool told_spatial = false, told_gamma = false;
+    bool told_discard_profile = false;           // DecoderCommand::DiscardColorProfile (mozjpeg_decoder.rs:88-91)
+    bool told_ignore_profile_errors = false;     // DecoderCommand::IgnoreColorProfileErrors (:93-96): a profile that fails leaves the samples as they are
+    bool told_convert_profile = false;           // EXTENSION "convert_color_profile": this input is converted to sRGB (Job::color_plan_for)
+    // DecoderCommand::WebPDecoderHints (codecs/webp.rs:181-188): the size libwebp's rescaler would decode to; acted on by a WebP input only
+    bool told_webp = false;
+    uint32_t told_webp_w = 0, told_webp_h = 0;
+    // DecoderCommand::SelectFrame (codecs/gif/mod.rs:200-205): the frame a GIF input hands on; the other decoders ignore it
+    bool told_frame = false;
+    int32_t told_frame_n = 0;
+};
+// select_frame: an integer (s::DecoderCommand::SelectFrame(i32))
+inline void tell_select_frame(Io& in, const JVal& j) {
+    if (j.t != JVal::Num || !(j.n >= -2147483648.0 && j.n <= 2147483647.0)) return;
+    in.told_frame = true;
+    in.told_frame_n = static_cast<int32_t>(j.n);
+}
+// webp_decoder_hints is accepted whatever it holds, as it was before a WebP input could act on it: only a hint that
+// carries both sizes is kept with the input
+inline void tell_webp_hint(Io& in, const JVal& j) {
+    const JVal* w = j.get("width");
+    const JVal* h = j.get("height");
+    if (!w || !h || w->t != JVal::Num || h->t != JVal::Num || !(w->n >= 0 && w->n <= 4294967295.0) || !(h->n >= 0 && h->n <= 4294967295.0)) return;
+    in.told_webp = true;
+    in.told_webp_w = static_cast<uint32_t>(w->n); in.told_webp_h = static_cast<uint32_t>(h->n);
+}
+struct Response {
+    int64_t status;
+    std::string json;
+};
+}  // namespace ifshim
+
+struct imageflow_json_response {                 // opaque to callers; read through imageflow_json_response_read
+    ifshim::Response r;
+};
+struct imageflow_context {
+    std::mutex mu;
+    std::map<int32_t, ifshim::Io> io;
+    int err_cat = ifshim::kOk;
+    std::string err_msg;
+    std::vector<std::unique_ptr<imageflow_json_response>> responses;
+    std::vector<std::unique_ptr<uint8_t[]>> allocations;
+    // CancellationToken (imageflow_core/src/context.rs:50-131): a flag another thread may set while a job holds `mu`,
+    // and the reference's debug-build poll countdown ("cancel at the n-th poll", :96-104) as a test hook
+    std::atomic<bool> cancel{false};
+    std::atomic<int64_t> poll_countdown{INT64_MAX};
+    std::atomic<int64_t> fused_decode_resamples{0};
+    std::atomic<int64_t> device_coded_files{0};          // JPEG outputs whose entropy coding ran on the device (diagnostic)
+    std::atomic<int64_t> coalesced_decodes{0};           // decodes of this context that shared their device call with another thread's job
+    std::atomic<int> device{-1};                         // device ordinal its jobs run on; -1: the calling thread's current device
+    std::atomic<bool> device_jpeg_options{false};        // EXTENSION ifhip_shim_context_set_device_jpeg_options: progressive / optimised tables coded on the device
+    std::atomic<bool> gif_animation{false};              // EXTENSION ifhip_shim_context_set_gif_animation: animated GIFs run once per frame into one file
+    std::atomic<bool> gif_encoder{false};                // EXTENSION ifhip_shim_context_set_gif_encoder: the "gif" preset writes a GIF on the device
+    std::atomic<bool> webp_lossy_decoder{false};         // EXTENSION ifhip_shim_context_set_webp_lossy_decoder: lossy WebP inputs are decoded on the device
+    std::atomic<bool> color_management{false};           // EXTENSION ifhip_shim_context_set_color_management: every input is converted to sRGB
+    bool cancellation_requested() {
+        if (cancel.load(std::memory_order_relaxed)) return true;
+        if (poll_countdown.load(std::memory_order_relaxed) == INT64_MAX) return false;
+        return poll_countdown.fetch_sub(1, std::memory_order_relaxed) < 1;
+    }
+    void set_error(int cat, const std::string& m) { if (err_cat == ifshim::kOk) { err_cat = cat; err_msg = m; } }   // first error sticks
+};
+
+namespace ifshim {
+
+// ---- the job interpreter ---------------------------------------------------------------------------------------
+struct EncodeRecord { int32_t io_id; uint32_t w, h; const char* mime; const char* ext; };
+struct DecodeRecord { int32_t io_id; uint32_t w, h; const char* mime; const char* ext; };
+struct NodePerf { const char* name; uint64_t wall_ns; float gpu_ms; hipEvent_t e0, e1; };   // s::NodePerf (imageflow_types/src/lib.rs:1999-2002); e0/e1: read at the job's end
+struct ResampleHints {                                                        // s::ResampleHints (lib.rs:925-933), parsed
+    bool has_sharpen = false;
+    float sharpen = 0.f;
+    int down = IFHIP_FILTER_ROBIDOUX, up = IFHIP_FILTER_GINSENG, space = IFHIP_SPACE_LINEAR;   // scale_render.rs:257-261,278-279
+    bool has_bg = false, bg_keyword_transparent = false;
+    uint32_t bg = 0;
+    enum When { kDefault, kSizeDiffers, kSizeDiffersOrSharpen, kAlways } resample_when = kDefault;
+    enum SWhen { kSAlways, kSDown, kSUp, kSSizeDiffers } sharpen_when = kSAlways;
+};
+
+}  // namespace ifshim

@@ -7,6 +7,7 @@ import pytest
 
 from imageflow_amd import abi
 from imageflow_amd.abi import Context
+from tests.shim_jobs import GRAMMAR_NUMBERS, INVALID_BODIES, MUTATED_JOBS
 
 
 def test_version_handshake():
@@ -27,8 +28,7 @@ def test_get_version_info_and_unknown_endpoint():
         assert c.has_error()
 
 
-@pytest.mark.parametrize("body", [b"{bad", b"", b'{"framewise": ', b'{"a": 1} trailing', b'{"framewise":{"steps":[{"decode":{"io_id":"x"}}]}}',
-                                  b"[" * 100 + b"]" * 100])
+@pytest.mark.parametrize("body", INVALID_BODIES)
 def test_invalid_json_is_category_3_http_400_exit_65(body):
     with Context() as c:
         status, r = c.send_json("v1/execute", body)
@@ -108,20 +108,8 @@ def test_json_reader_survives_mutated_jobs():
     import json
     import random
     rnd = random.Random(11)
-    jobs = [
-        {"io": [{"io_id": 0, "direction": "in", "io": "placeholder"}, {"io_id": 1, "direction": "out", "io": "output_buffer"}],
-         "framewise": {"steps": [{"decode": {"io_id": 0, "commands": [{"jpeg_downscale_hints": {"width": 800, "height": 600, "scale_luma_spatially": True,
-                                                                                                "gamma_correct_for_srgb_during_spatial_luma_scaling": True}}]}},
-                                 {"resample_2d": {"w": 200, "h": 200, "hints": {"down_filter": "robidoux", "scaling_colorspace": "linear", "sharpen_percent": 15,
-                                                                                  "background_color": {"srgb": {"hex": "FFFFFFFF"}}}}},
-                                 {"encode": {"io_id": 1, "preset": {"libjpeg_turbo": {"quality": 90, "progressive": True}}}}]}},
-        {"framewise": {"graph": {"nodes": {"0": {"create_canvas": {"w": 64, "h": 64, "format": "bgra_32", "color": "transparent"}},
-                                           "1": {"fill_rect": {"x1": 0, "y1": 0, "x2": 10, "y2": 10, "color": {"srgb": {"hex": "EECCFFFF"}}}},
-                                           "2": {"constrain": {"mode": "within", "w": 32}}, "3": {"command_string": {"kind": "ir4", "value": "width=20&mode=max"}}},
-                                 "edges": [{"from": 0, "to": 1, "kind": "input"}, {"from": 1, "to": 2, "kind": "input"}, {"from": 2, "to": 3, "kind": "input"}]}}},
-    ]
     answered = 0
-    for job in jobs:
+    for job in MUTATED_JOBS:
         body = json.dumps(job).encode()
         with Context() as c:
             c.add_input_buffer(0, b"\xff\xd8\xff" + bytes(16))
@@ -223,7 +211,7 @@ def test_print_and_exit_if_error():
     assert r.returncode == 65 and "InvalidJson" in r.stderr and "still here" not in r.stdout
 
 
-@pytest.mark.parametrize("number", [b"inf", b"Infinity", b"nan", b"0x10", b"+1", b"1e999", b"01", b"1.", b".5", b"-"])
+@pytest.mark.parametrize("number", GRAMMAR_NUMBERS)
 def test_json_numbers_follow_the_grammar(number):
     with Context() as c:
         status, r = c.send_json("v1/execute", b'{"framewise":{"steps":[{"create_canvas":{"w":' + number + b',"h":8,"format":"bgra_32","color":"transparent"}}]}}')
