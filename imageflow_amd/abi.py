@@ -74,6 +74,8 @@ def _bind():
     L.ifhip_shim_context_set_color_management.restype = C.c_bool
     L.ifhip_shim_context_set_webp_lossy_decoder.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_webp_lossy_decoder.restype = C.c_bool
+    L.ifhip_shim_context_set_webp_lossy_encoder.argtypes = [vp, C.c_int]
+    L.ifhip_shim_context_set_webp_lossy_encoder.restype = C.c_bool
     L.ifhip_shim_context_set_gif_encoder.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_gif_encoder.restype = C.c_bool
     L.ifhip_shim_context_set_gif_animation.argtypes = [vp, C.c_int]
@@ -173,6 +175,11 @@ class Context:
         libwebp's pixels -- `decode`, `watermark`, `command_string` and v1/get_image_info take them -- instead of being
         ImageTypeNotSupported."""
         return self.L.ifhip_shim_context_set_webp_lossy_decoder(self.p, 1 if on else 0)
+
+    def set_webp_lossy_encoder(self, on):
+        """EXTENSION, off by default: `encode` with the preset {"webplossy": {"quality": q}} writes a lossy WebP file on the device
+        (image/webp) instead of the raw BGRA container; the bare string and a missing or non-numeric quality are then InvalidJson."""
+        return self.L.ifhip_shim_context_set_webp_lossy_encoder(self.p, 1 if on else 0)
 
     def set_gif_encoder(self, on):
         """EXTENSION, off by default: `encode` with the preset "gif" writes a GIF89a file on the device (image/gif) instead of

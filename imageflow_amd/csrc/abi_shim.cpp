@@ -51,6 +51,7 @@
 
 #include "../../include/imageflow_abi_subset.h"
 #include "../../include/imageflow_hip.h"
+#include "../../include/imageflow_hip_webp_lossy_enc.h"   // the device lossy WebP coder (vp8_encode.hip), in a header of its own
 #include "common.hpp"           // the library's per-job memory cache and thread stream (devmem.cpp)
 #include "color_profile.hpp"   // a colour profile as a conversion plan (color_profile.cpp; the kernel: color_profile.hip)
 #include "png_read.hpp"         // the PNG chunk walk and the device decode of a walked file (png_read.cpp, png_decode.hip)
@@ -1123,6 +1124,7 @@ struct Job {
         if (const JVal* pq = coder == IFHIP_ENCODE_CODER_PNGQUANT ? preset->get("pngquant") : nullptr) return encode_pngquant(f, o, io_id, pq);
         if (coder == IFHIP_ENCODE_CODER_WEBP_LOSSLESS) return encode_webp_lossless(f, o, io_id);
         if (preset && preset->t == JVal::Str && preset->s == "gif" && c->gif_encoder.load(std::memory_order_relaxed)) return encode_gif(f, o, io_id);
+        if (names_webplossy(preset) && c->webp_lossy_encoder.load(std::memory_order_relaxed)) return encode_webp_lossy(f, o, io_id, preset);
         encode_raw(f, o, io_id);
     }
 
@@ -1308,6 +1310,20 @@ struct Job {
             ifhip_gif_enc_stage_max_file_bytes, [&](ifhip_gif_enc_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
                 return ifhip_gif_encode_batch_device(s, dev(f), f->bytes(), f->stride, f->alpha ? 1 : 0, 1, gif_source.seen ? gif_source.repeat : -1, gif_source.delay,
                                                      gif_source.user_input ? 1 : 0, d_file, pitch, d_len, d_len + 1, nullptr, nullptr, t_job_stream);
+            });
+        return;
+    }
+    void encode_webp_lossy(const FramePtr& f, Io& o, int32_t io_id, const JVal* preset) {
+        // EXTENSION (ifhip_shim_context_set_webp_lossy_encoder): EncoderPreset::WebPLossy {quality} -> WebPEncoder::write_frame
+        // (codecs/webp.rs: WebPEncodeBGRA, or ...BGR when the frame's alpha is not meaningful; quality clamped to 0..100); no matte.
+        // The file is coded on the device (csrc/vp8_encode.hip), only its bytes leave it.  libwebp returns nothing for a side
+        // above 16383, which the reference answers with ImageEncodingError.
+        const float quality = check_webplossy_preset(preset);
+        if (f->w > 16383u || f->h > 16383u) raise(kInternalError, "ImageEncodingError: libwebp encoding error");
+        write_coded_frame(
+            f, o, io_id, kWebpNames, 0u, [&](ifhip_webp_lossy_enc_stage** s) { return ifhip_webp_lossy_enc_stage_create(s, f->w, f->h, f->alpha ? 1 : 0, 1); },
+            ifhip_webp_lossy_enc_stage_destroy, ifhip_webp_lossy_enc_stage_max_file_bytes, [&](ifhip_webp_lossy_enc_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
+                return ifhip_webp_lossy_encode_batch_device(s, dev(f), f->bytes(), f->stride, 1, quality, d_file, pitch, d_len, d_len + 1, t_job_stream);
             });
         return;
     }
@@ -1696,10 +1712,22 @@ struct Job {
         if (q && q->t == JVal::Num && (q->n != std::floor(q->n) || q->n < 0.0 || q->n > 255.0))
             raise(kInvalidJson, "InvalidJson: encode.preset.mozjpeg.quality is an integer 0..255");
     }
-    static void check_encode_node(const JVal& n) {
+    // EncoderPreset::WebPLossy is a struct variant with a required f32: the bare string, a missing or a non-numeric quality do
+    // not deserialise.  Looked at only where the context's lossy WebP encoder is on; -> the quality.
+    static bool names_webplossy(const JVal* preset) {
+        return preset && ((preset->t == JVal::Str && preset->s == "webplossy") || (preset->t == JVal::Obj && preset->get("webplossy")));
+    }
+    static float check_webplossy_preset(const JVal* preset) {
+        const JVal* lossy = preset->t == JVal::Obj ? preset->get("webplossy") : nullptr;
+        const JVal* q = lossy && lossy->t == JVal::Obj ? lossy->get("quality") : nullptr;
+        if (!q || q->t != JVal::Num) raise(kInvalidJson, "InvalidJson: encode.preset.webplossy.quality is a number");
+        return static_cast<float>(q->n);
+    }
+    void check_encode_node(const JVal& n) {
         if (n.t != JVal::Obj || n.o.size() != 1 || n.o[0].first != "encode") return;
         const JVal* preset = n.o[0].second.get("preset");
         if (encode_coder(preset) == IFHIP_ENCODE_CODER_MOZJPEG) check_mozjpeg_preset(preset);
+        if (names_webplossy(preset) && c->webp_lossy_encoder.load(std::memory_order_relaxed)) (void)check_webplossy_preset(preset);
     }
 
 
@@ -2219,6 +2247,13 @@ bool ifhip_shim_context_set_gif_animation(struct imageflow_context* c, int on) {
 bool ifhip_shim_context_set_webp_lossy_decoder(struct imageflow_context* c, int on) {
     CTX_OR_ABORT(c);
     c->webp_lossy_decoder.store(on != 0, std::memory_order_relaxed);
+    return true;
+}
+// EXTENSION: the "webplossy" preset of `encode` writes a lossy WebP on the device (see Job::encode_webp_lossy); off by default,
+// where the preset stays the raw-container tap it has always been.
+bool ifhip_shim_context_set_webp_lossy_encoder(struct imageflow_context* c, int on) {
+    CTX_OR_ABORT(c);
+    c->webp_lossy_encoder.store(on != 0, std::memory_order_relaxed);
     return true;
 }
 bool ifhip_shim_context_set_color_management(struct imageflow_context* c, int on) {

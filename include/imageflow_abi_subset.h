@@ -133,6 +133,12 @@ IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_color_management(struct imageflow
  * default, where a lossy file stays ImageTypeNotSupported.  max_decode_size, the ICCP policy, webp_decoder_hints and EXIF
  * are treated as for a lossless file; animated WebP and libwebp's decode-time rescaler stay refused.  Returns true. */
 IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_webp_lossy_decoder(struct imageflow_context *context, int on);
+/* EXTENSION: `encode` with the preset {"webplossy": {"quality": q}} writes a lossy WebP file on the device
+ * (ifhip_webp_lossy_encode_batch_device: WebPEncoder::write_frame over WebPEncodeBGRA / WebPEncodeBGR, codecs/webp.rs) and reports
+ * image/webp; off by default, where the preset writes the raw BGRA container as ever.  With it on, the bare string "webplossy" and a
+ * missing or non-numeric quality are InvalidJson before any node runs (the reference's variant is a struct with a required f32), and
+ * a side above 16383 is "ImageEncodingError: libwebp encoding error".  Returns true. */
+IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_webp_lossy_encoder(struct imageflow_context *context, int on);
 /* EXTENSION: `encode` with the preset "gif" writes a GIF89a file on the device (ifhip_gif_encode_batch_device: GifEncoder::write_frame,
  * codecs/gif/mod.rs:385-592) and reports image/gif; off by default, where the preset writes the raw BGRA container as ever.  A
  * GIF input of the job hands its loop count and the selected frame's delay and user-input flag to the file. */
