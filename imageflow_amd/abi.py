@@ -176,10 +176,10 @@ class Context:
         ImageTypeNotSupported."""
         return self.L.ifhip_shim_context_set_webp_lossy_decoder(self.p, 1 if on else 0)
 
-    def set_webp_lossy_encoder(self, on):
+    def set_webp_lossy_encoder(self, on, intra4=False):
         """EXTENSION, off by default: `encode` with the preset {"webplossy": {"quality": q}} writes a lossy WebP file on the device
         (image/webp) instead of the raw BGRA container; the bare string and a missing or non-numeric quality are then InvalidJson."""
-        return self.L.ifhip_shim_context_set_webp_lossy_encoder(self.p, 1 if on else 0)
+        return self.L.ifhip_shim_context_set_webp_lossy_encoder(self.p, (2 if intra4 else 1) if on else 0)
 
     def set_gif_encoder(self, on):
         """EXTENSION, off by default: `encode` with the preset "gif" writes a GIF89a file on the device (image/gif) instead of

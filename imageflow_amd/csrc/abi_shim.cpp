@@ -1317,11 +1317,12 @@ struct Job {
         // EXTENSION (ifhip_shim_context_set_webp_lossy_encoder): EncoderPreset::WebPLossy {quality} -> WebPEncoder::write_frame
         // (codecs/webp.rs: WebPEncodeBGRA, or ...BGR when the frame's alpha is not meaningful; quality clamped to 0..100); no matte.
         // The file is coded on the device (csrc/vp8_encode.hip), only its bytes leave it.  libwebp returns nothing for a side
-        // above 16383, which the reference answers with ImageEncodingError.
+        // above 16383, which the reference answers with ImageEncodingError.  The switch's value 2 adds the 4x4 luma modes.
         const float quality = check_webplossy_preset(preset);
+        const uint32_t flags = c->webp_lossy_intra4.load(std::memory_order_relaxed) ? IFHIP_VP8_ENC_INTRA4 : 0u;
         if (f->w > 16383u || f->h > 16383u) raise(kInternalError, "ImageEncodingError: libwebp encoding error");
         write_coded_frame(
-            f, o, io_id, kWebpNames, 0u, [&](ifhip_webp_lossy_enc_stage** s) { return ifhip_webp_lossy_enc_stage_create(s, f->w, f->h, f->alpha ? 1 : 0, 1); },
+            f, o, io_id, kWebpNames, 0u, [&](ifhip_webp_lossy_enc_stage** s) { return ifhip_webp_lossy_enc_stage_create_flags(s, f->w, f->h, f->alpha ? 1 : 0, 1, flags); },
             ifhip_webp_lossy_enc_stage_destroy, ifhip_webp_lossy_enc_stage_max_file_bytes, [&](ifhip_webp_lossy_enc_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
                 return ifhip_webp_lossy_encode_batch_device(s, dev(f), f->bytes(), f->stride, 1, quality, d_file, pitch, d_len, d_len + 1, t_job_stream);
             });
@@ -2250,9 +2251,10 @@ bool ifhip_shim_context_set_webp_lossy_decoder(struct imageflow_context* c, int 
     return true;
 }
 // EXTENSION: the "webplossy" preset of `encode` writes a lossy WebP on the device (see Job::encode_webp_lossy); off by default,
-// where the preset stays the raw-container tap it has always been.
+// where the preset stays the raw-container tap it has always been.  2: on, with the sixteen 4x4 luma modes (IFHIP_VP8_ENC_INTRA4).
 bool ifhip_shim_context_set_webp_lossy_encoder(struct imageflow_context* c, int on) {
     CTX_OR_ABORT(c);
+    c->webp_lossy_intra4.store(on == 2, std::memory_order_relaxed);
     c->webp_lossy_encoder.store(on != 0, std::memory_order_relaxed);
     return true;
 }

@@ -159,31 +159,15 @@ IFHIP_HD int vp8_pred_large(const uint8_t* p, uint32_t pitch, uint32_t x0, uint3
 
 IFHIP_HD int vp8_avg2(int a, int b) { return (a + b + 1) >> 1; }
 IFHIP_HD int vp8_avg3(int a, int b, int c) { return (a + 2 * b + c + 2) >> 2; }
-// One 4x4 sub-block (bx, by) of macroblock (mbx, mby): prediction from the plane plus the block's residuals, stored to the plane.
-// The above-right of the sub-blocks in the macroblock's last column is, for all four rows, the bottom row of the macroblock
-// above and to the right (the above macroblock's last pixel four times at the frame's right edge).
-IFHIP_HD void vp8_predict_sub(uint8_t* p, uint32_t pitch, uint32_t mbw, uint32_t mbx, uint32_t mby, uint32_t bx, uint32_t by, uint32_t mode, const int16_t* res) {
-    const uint32_t x0 = mbx * 16u + bx * 4u, y0 = mby * 16u + by * 4u;
-    int T[8], L[4];
-    const int X = vp8_corner(p, pitch, x0, y0);
-    VP8_UNROLL
-    for (uint32_t i = 0; i < 4u; ++i) { T[i] = vp8_top(p, pitch, x0 + i, y0); L[i] = vp8_left(p, pitch, x0, y0 + i); }
-    VP8_UNROLL
-    for (uint32_t i = 0; i < 4u; ++i) {
-        int v = 127;
-        if (mby) {
-            if (bx < 3u) v = p[static_cast<size_t>(y0 - 1u) * pitch + x0 + 4u + i];
-            else {
-                const size_t row = static_cast<size_t>(mby * 16u - 1u) * pitch;
-                v = mbx + 1u < mbw ? p[row + x0 + 4u + i] : p[row + mbx * 16u + 15u];
-            }
-        } else if (by && bx < 3u) {
-            v = p[static_cast<size_t>(y0 - 1u) * pitch + x0 + 4u + i];
-        }
-        T[4u + i] = v;
-    }
-    const int A = T[0], B = T[1], C = T[2], D = T[3], E = T[4], F = T[5], G = T[6], H = T[7];
-    const int I = L[0], J = L[1], K = L[2], M = L[3];
+// The sixteen predicted values of a 4x4 sub-block in raster order from its edge: T the four pixels above and the four above-right,
+// L the four to the left, X the corner.  Modes in libwebp's numbering: DC TM VE HE RD VR LD VL HD HU.  The decoder
+// (vp8_predict_sub) and the coder's 4x4 search (vp8_encode_core.hpp) both predict with this function.
+// (the edge and the result are copied through locals: arrays reached through the pointers of an inlined call are not promoted to
+// registers by the gfx950 build, locals are)
+IFHIP_HD void vp8_pred_sub16(uint32_t mode, const int* edge_above, const int* edge_left, int X, int* out) {
+    const int A = edge_above[0], B = edge_above[1], C = edge_above[2], D = edge_above[3], E = edge_above[4], F = edge_above[5], G = edge_above[6], H = edge_above[7];
+    const int I = edge_left[0], J = edge_left[1], K = edge_left[2], M = edge_left[3];
+    const int T[4] = {A, B, C, D}, L[4] = {I, J, K, M};
     int o[16];
 #define VP8_DST(x, y) o[(x) + 4 * (y)]
     switch (mode) {
@@ -272,10 +256,75 @@ IFHIP_HD void vp8_predict_sub(uint8_t* p, uint32_t pitch, uint32_t mbw, uint32_t
     }
 #undef VP8_DST
     VP8_UNROLL
+    for (int i = 0; i < 16; ++i) out[i] = o[i];
+}
+// A luma macroblock under construction with its edge, as the 4x4 search of the coder keeps it (in LDS on the device): row 0 is
+// the corner, the sixteen pixels above and the four above-right; rows 1..16 are the pixel to the left and the macroblock's own
+// sixteen.  The borders of the frame are filled in by vp8_tile_load_edge with the values vp8_predict_sub reads there.
+constexpr uint32_t kVp8TilePitch = 24;
+constexpr uint32_t kVp8TileBytes = 17u * kVp8TilePitch;
+// edge byte i of 37: 0 the corner, 1..16 above, 17..20 above-right, 21..36 the left column
+IFHIP_HD void vp8_tile_load_edge(uint8_t* tile, const uint8_t* p, uint32_t pitch, uint32_t mbw, uint32_t mbx, uint32_t mby, uint32_t i) {
+    const uint32_t x0 = mbx * 16u, y0 = mby * 16u;
+    if (i == 0u) tile[0] = static_cast<uint8_t>(vp8_corner(p, pitch, x0, y0));
+    else if (i <= 16u) tile[i] = static_cast<uint8_t>(vp8_top(p, pitch, x0 + i - 1u, y0));
+    else if (i <= 20u) {
+        int v = 127;
+        if (mby) { const size_t row = static_cast<size_t>(y0 - 1u) * pitch; v = mbx + 1u < mbw ? p[row + x0 + i - 1u] : p[row + x0 + 15u]; }
+        tile[i] = static_cast<uint8_t>(v);
+    } else tile[(i - 20u) * kVp8TilePitch] = static_cast<uint8_t>(vp8_left(p, pitch, x0, y0 + i - 21u));
+}
+// the edge of sub-block (bx, by) from such a tile: what vp8_predict_sub gathers from the plane (the above-right of the last
+// sub-block column comes from row 0 for all four rows)
+IFHIP_HD void vp8_tile_sub_edge(const uint8_t* tile, uint32_t bx, uint32_t by, int* T, int* L, int* X) {
+    const uint8_t* above = tile + 4u * by * kVp8TilePitch + 4u * bx;      // the corner of the sub-block
+    *X = above[0];
+    VP8_UNROLL
+    for (uint32_t i = 0; i < 4u; ++i) { T[i] = above[1u + i]; L[i] = above[(1u + i) * kVp8TilePitch]; }
+    VP8_UNROLL
+    for (uint32_t i = 0; i < 4u; ++i) T[4u + i] = bx < 3u ? above[5u + i] : tile[17u + i];
+}
+// One 4x4 sub-block (bx, by) of macroblock (mbx, mby): prediction from the plane plus the block's residuals, stored to the plane.
+// The above-right of the sub-blocks in the macroblock's last column is, for all four rows, the bottom row of the macroblock
+// above and to the right (the above macroblock's last pixel four times at the frame's right edge).
+IFHIP_HD void vp8_predict_sub(uint8_t* p, uint32_t pitch, uint32_t mbw, uint32_t mbx, uint32_t mby, uint32_t bx, uint32_t by, uint32_t mode, const int16_t* res) {
+    const uint32_t x0 = mbx * 16u + bx * 4u, y0 = mby * 16u + by * 4u;
+    int T[8], L[4], o[16];
+    const int X = vp8_corner(p, pitch, x0, y0);
+    VP8_UNROLL
+    for (uint32_t i = 0; i < 4u; ++i) { T[i] = vp8_top(p, pitch, x0 + i, y0); L[i] = vp8_left(p, pitch, x0, y0 + i); }
+    VP8_UNROLL
+    for (uint32_t i = 0; i < 4u; ++i) {
+        int v = 127;
+        if (mby) {
+            if (bx < 3u) v = p[static_cast<size_t>(y0 - 1u) * pitch + x0 + 4u + i];
+            else {
+                const size_t row = static_cast<size_t>(mby * 16u - 1u) * pitch;
+                v = mbx + 1u < mbw ? p[row + x0 + 4u + i] : p[row + mbx * 16u + 15u];
+            }
+        } else if (by && bx < 3u) {
+            v = p[static_cast<size_t>(y0 - 1u) * pitch + x0 + 4u + i];
+        }
+        T[4u + i] = v;
+    }
+    vp8_pred_sub16(mode, T, L, X, o);
+    VP8_UNROLL
     for (uint32_t i = 0; i < 16u; ++i)
         p[static_cast<size_t>(y0 + (i >> 2)) * pitch + x0 + (i & 3u)] = static_cast<uint8_t>(vp8_clip8(o[i] + res[i]));
 }
 
+// the two chroma planes of macroblock (mbx, mby): its second half, which the coder also runs alone behind its 4x4 search
+IFHIP_HD void vp8_predict_mb_chroma(const Vp8Planes& P, const Vp8Mb& mb, const int16_t* res, uint32_t mbx, uint32_t mby, uint32_t lane, uint32_t nlanes) {
+    const uint32_t x0 = mbx * 8u, y0 = mby * 8u;
+    const int dcu = mb.uvmode == 0u ? vp8_dc_large(P.u, P.uvpitch, x0, y0, 8u) : 0;
+    const int dcv = mb.uvmode == 0u ? vp8_dc_large(P.v, P.uvpitch, x0, y0, 8u) : 0;
+    for (uint32_t i = lane; i < 128u; i += nlanes) {
+        const uint32_t c = i >> 6, px = i & 7u, py = (i >> 3) & 7u;
+        uint8_t* plane = c ? P.v : P.u;
+        const int r = res[16u * (16u + 4u * c + (py >> 2) * 2u + (px >> 2)) + (py & 3u) * 4u + (px & 3u)];
+        plane[static_cast<size_t>(y0 + py) * P.uvpitch + x0 + px] = static_cast<uint8_t>(vp8_clip8(vp8_pred_large(plane, P.uvpitch, x0, y0, mb.uvmode, px, py, c ? dcv : dcu) + r));
+    }
+}
 // Macroblock (mbx, mby) by `nlanes` lanes: prediction plus residual into the three planes.  The pixels of a whole-macroblock
 // mode and of the chroma blocks are independent and spread over the lanes; the sixteen 4x4 sub-blocks of a 4x4-mode
 // macroblock depend on each other and are lane 0's, in raster order.  Reads the finished macroblocks to the left, above,
@@ -293,15 +342,7 @@ IFHIP_HD void vp8_predict_mb(const Vp8Planes& P, const Vp8Mb& mb, const int16_t*
             P.y[static_cast<size_t>(y0 + py) * P.ypitch + x0 + px] = static_cast<uint8_t>(vp8_clip8(vp8_pred_large(P.y, P.ypitch, x0, y0, mb.ymode, px, py, dc) + r));
         }
     }
-    const uint32_t x0 = mbx * 8u, y0 = mby * 8u;
-    const int dcu = mb.uvmode == 0u ? vp8_dc_large(P.u, P.uvpitch, x0, y0, 8u) : 0;
-    const int dcv = mb.uvmode == 0u ? vp8_dc_large(P.v, P.uvpitch, x0, y0, 8u) : 0;
-    for (uint32_t i = lane; i < 128u; i += nlanes) {
-        const uint32_t c = i >> 6, px = i & 7u, py = (i >> 3) & 7u;
-        uint8_t* plane = c ? P.v : P.u;
-        const int r = res[16u * (16u + 4u * c + (py >> 2) * 2u + (px >> 2)) + (py & 3u) * 4u + (px & 3u)];
-        plane[static_cast<size_t>(y0 + py) * P.uvpitch + x0 + px] = static_cast<uint8_t>(vp8_clip8(vp8_pred_large(plane, P.uvpitch, x0, y0, mb.uvmode, px, py, c ? dcv : dcu) + r));
-    }
+    vp8_predict_mb_chroma(P, mb, res, mbx, mby, lane, nlanes);
 }
 
 // ---- the loop filter (libwebp's dsp: DoFilter2 / 4 / 6 behind NeedsFilter and Hev) ------------------------------------------------------------

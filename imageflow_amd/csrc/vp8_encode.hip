@@ -7,7 +7,8 @@
 //   convert   grid-wide, a thread per 2x2 pixels: Y and the box-averaged U, V into planes of whole macroblocks (edges
 //             replicated), the grey frame B = G = R = alpha for the inner lossless coder, "any alpha below 255" per image
 //   (inner)   the lossless coder's own launches over the grey frames (csrc/webp_encode.hip), where the stage has alpha
-//   code      ONE WORKGROUP OF 8 WAVES PER IMAGE: whole-macroblock modes need the left, above and above-left neighbours,
+//   code      (a stage with IFHIP_VP8_ENC_INTRA4 launches vp8e_code4_kernel of csrc/vp8_encode_intra4.hip in its place)
+//             ONE WORKGROUP OF 8 WAVES PER IMAGE: whole-macroblock modes need the left, above and above-left neighbours,
 //             so macroblock (x, y) runs in step x + y, the macroblocks of a step dealt to the waves, a workgroup barrier
 //             between steps.  A wave tries the 4 x 16 (mode, luma block) and 4 x 8 (mode, chroma block) pairs a lane each:
 //             prediction, forward DCT / WHT, dead-zone quantisation, the decoder's own reconstruction, squared error +
@@ -30,46 +31,11 @@
 #include "../../include/imageflow_hip_webp_lossy_enc.h"
 #include "encode_handoff.hpp"
 #include "stage_scratch.hpp"
+#include "vp8_encode_args.hpp"
 #include "vp8_encode_core.hpp"
 #include "webp_encode_core.hpp"
 
 namespace ifhip {
-
-constexpr uint32_t kVp8eWaves = 8u;              // waves of the one workgroup an image's wavefront runs in
-constexpr uint32_t kVp8eCountWords = 2u * kVp8eProbs + 8u;       // branch counts, then [0] skipped macroblocks, [1] any alpha below 255
-constexpr uint32_t kVp8eProbBytes = 2u * kVp8eProbs + 16u;       // probabilities, update flags, then the skip probability
-constexpr uint32_t kVp8eStreams = 9u;            // the first partition and at most eight token partitions
-
-struct Vp8eArgs {
-    const uint8_t* images;
-    size_t image_bytes;
-    uint32_t stride, w, h, mbw, mbh, alpha, n_images;
-    Vp8eParams p;
-    const Vp8eTables* T;
-    uint8_t* planes;                    // [n][6 planes]: source Y, U, V and reconstruction Y, U, V, 768 bytes a macroblock
-    uint32_t* grey;                     // [n][h * w] (null without alpha)
-    Vp8Mb* mbs;                         // [n][mbw * mbh]
-    int16_t* levels;                    // [n][mbw * mbh][400]
-    uint32_t* counts;                   // [n][kVp8eCountWords], zeroed per batch
-    uint8_t* probs;                     // [n][kVp8eProbBytes]
-    uint8_t* streams;                   // [n][stream_pitch]: the first partition's room, then each token partition's
-    size_t stream_pitch;
-    uint32_t first_cap, part_cap;
-    uint32_t* stream_len;               // [n][kVp8eStreams]
-    const uint8_t* inner_files;         // the inner lossless coder's files of the grey frames
-    size_t inner_pitch;
-    const uint32_t *inner_len, *inner_status;
-    uint8_t* files;
-    size_t file_pitch;
-    uint32_t *lengths, *status_out;
-};
-
-__device__ __forceinline__ size_t vp8e_mb_count(const Vp8eArgs& a) { return static_cast<size_t>(a.mbw) * a.mbh; }
-__device__ __forceinline__ Vp8Planes vp8e_planes(const Vp8eArgs& a, uint32_t img, bool rec) {
-    const size_t n = vp8e_mb_count(a);
-    uint8_t* base = a.planes + (static_cast<size_t>(img) * 2u + (rec ? 1u : 0u)) * n * 384u;
-    return Vp8Planes{base, base + n * 256u, base + n * 320u, a.mbw * 16u, a.mbw * 8u, a.mbw, a.mbh};
-}
 
 __global__ __launch_bounds__(256) void vp8e_convert_kernel(const Vp8eArgs a) {
     const uint32_t img = blockIdx.y;
@@ -120,7 +86,7 @@ __global__ __launch_bounds__(256) void vp8e_count_kernel(const Vp8eArgs a) {
         if (vp8e_mb_skipped(mbs[m])) atomicAdd(&hist[2u * kVp8eProbs], 1u);
         else {
             Vp8eAtomicCountSink s{hist};
-            vp8e_mb_tokens(*a.T, a.levels + (static_cast<size_t>(img) * n + m) * kVp8MbLevels, mbs[m], m >= a.mbw ? mbs[m - a.mbw].nz : 0u, m % a.mbw ? mbs[m - 1u].nz : 0u, s);
+            vp8e_mb_tokens(*a.T, a.levels + (static_cast<size_t>(img) * n + m) * kVp8MbLevels, mbs[m], m >= a.mbw ? vp8e_ctx_above(mbs[m - a.mbw]) : 0u, m % a.mbw ? vp8e_ctx_left(mbs[m - 1u]) : 0u, s);
         }
     }
     __syncthreads();
@@ -150,7 +116,7 @@ __global__ __launch_bounds__(64) void vp8e_streams_kernel(const Vp8eArgs a) {
     const uint8_t* probs = a.probs + static_cast<size_t>(img) * kVp8eProbBytes;
     const Vp8Mb* mbs = a.mbs + static_cast<size_t>(img) * n;
     uint32_t len;
-    if (k == 0u) len = vp8e_first_partition(*a.T, a.p, probs, probs + kVp8eProbs, probs[2u * kVp8eProbs], mbs, n, vp8e_stream(a, img, 0u), a.first_cap);
+    if (k == 0u) len = vp8e_first_partition(*a.T, a.p, probs, probs + kVp8eProbs, probs[2u * kVp8eProbs], mbs, n, vp8e_stream(a, img, 0u), a.first_cap, a.mbw);
     else len = vp8e_token_partition(*a.T, probs, mbs, a.levels + static_cast<size_t>(img) * n * kVp8MbLevels, a.mbw, a.mbh, k - 1u, a.p.n_parts, vp8e_stream(a, img, k), a.part_cap);
     a.stream_len[static_cast<size_t>(img) * kVp8eStreams + k] = len;
 }
@@ -202,7 +168,7 @@ __global__ __launch_bounds__(256) void vp8e_layout_kernel(const Vp8eArgs a) {
 using namespace ifhip;
 
 struct ifhip_webp_lossy_enc_stage {
-    uint32_t width = 0, height = 0, alpha = 0, max_images = 0, mbw = 0, mbh = 0;
+    uint32_t width = 0, height = 0, alpha = 0, max_images = 0, mbw = 0, mbh = 0, flags = 0;
     ifhip_webp_enc_stage* inner = nullptr;       // the lossless coder of the alpha planes
     size_t inner_pitch = 0, stream_pitch = 0;
     uint32_t first_cap = 0, part_cap = 0;
@@ -238,17 +204,22 @@ struct ifhip_webp_lossy_enc_stage {
 extern "C" {
 
 int ifhip_webp_lossy_enc_stage_create(ifhip_webp_lossy_enc_stage** stage, uint32_t width, uint32_t height, int alpha_meaningful, uint32_t max_images) {
+    return ifhip_webp_lossy_enc_stage_create_flags(stage, width, height, alpha_meaningful, max_images, 0u);
+}
+
+int ifhip_webp_lossy_enc_stage_create_flags(ifhip_webp_lossy_enc_stage** stage, uint32_t width, uint32_t height, int alpha_meaningful, uint32_t max_images, uint32_t flags) {
     if (!stage) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null stage out-pointer");
     *stage = nullptr;
+    if (flags & ~static_cast<uint32_t>(IFHIP_VP8_ENC_INTRA4)) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: unknown lossy WebP coder flags 0x%x", flags);
     if (width == 0 || height == 0) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: Bitmap dimensions cannot be zero");
     if (width > kVp8eMaxDim || height > kVp8eMaxDim)
         return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: a WebP frame is at most %u x %u (14 bits each), not %u x %u", kVp8eMaxDim, kVp8eMaxDim, width, height);
     if (max_images == 0 || max_images > 65535u) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: 1..65535 images per stage");
     std::unique_ptr<ifhip_webp_lossy_enc_stage> s(new ifhip_webp_lossy_enc_stage);
-    s->width = width; s->height = height; s->alpha = alpha_meaningful ? 1u : 0u; s->max_images = max_images;
+    s->width = width; s->height = height; s->alpha = alpha_meaningful ? 1u : 0u; s->max_images = max_images; s->flags = flags;
     s->mbw = (width + 15u) / 16u; s->mbh = (height + 15u) / 16u;
     const uint64_t mbs = static_cast<uint64_t>(s->mbw) * s->mbh;
-    const uint64_t first = vp8e_first_cap(mbs), part = vp8e_part_cap(s->mbw, s->mbh, 1u << vp8e_partitions_log2(s->mbh));
+    const uint64_t first = vp8e_first_cap(mbs, flags), part = vp8e_part_cap(s->mbw, s->mbh, 1u << vp8e_partitions_log2(s->mbh));
     s->first_cap = static_cast<uint32_t>(((first > kVp8eFirstPartMax ? kVp8eFirstPartMax : first) + 15u) & ~15ull);
     s->part_cap = static_cast<uint32_t>((part + 15u) & ~15ull);           // (at most 2^20 macroblocks of 2664 bytes: below 2^32)
     s->stream_pitch = s->first_cap + (static_cast<size_t>(s->part_cap) << vp8e_partitions_log2(s->mbh));
@@ -264,7 +235,7 @@ void ifhip_webp_lossy_enc_stage_destroy(ifhip_webp_lossy_enc_stage* stage) { del
 
 size_t ifhip_webp_lossy_enc_stage_max_file_bytes(const ifhip_webp_lossy_enc_stage* stage) {
     if (!stage) return 0u;
-    return static_cast<size_t>(vp8e_max_file_bytes(stage->width, stage->height, stage->alpha ? webp_max_file_bytes(stage->width, stage->height) : 0u));
+    return static_cast<size_t>(vp8e_max_file_bytes(stage->width, stage->height, stage->alpha ? webp_max_file_bytes(stage->width, stage->height) : 0u, stage->flags));
 }
 
 int ifhip_webp_lossy_encode_batch_device(ifhip_webp_lossy_enc_stage* stage, const uint8_t* d_images, size_t image_bytes, uint32_t stride, uint32_t n_images, float quality,
@@ -277,7 +248,7 @@ int ifhip_webp_lossy_encode_batch_device(ifhip_webp_lossy_enc_stage* stage, cons
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
     Vp8eArgs a{};
     a.images = d_images; a.image_bytes = image_bytes; a.stride = stride; a.w = stage->width; a.h = stage->height; a.mbw = stage->mbw; a.mbh = stage->mbh;
-    a.alpha = stage->alpha; a.n_images = n_images;
+    a.alpha = stage->alpha; a.n_images = n_images; a.flags = stage->flags;
     a.p = vp8e_params(vp8e_host_tables(), vp8e_quality_to_index(quality), stage->mbh, kVp8eFilterNum);
     a.T = stage->d_tables; a.planes = stage->d_planes; a.grey = stage->d_grey; a.mbs = stage->d_mbs; a.levels = stage->d_levels; a.counts = stage->d_counts;
     a.probs = stage->d_probs; a.streams = stage->d_streams; a.stream_pitch = stage->stream_pitch; a.first_cap = stage->first_cap; a.part_cap = stage->part_cap;
@@ -295,7 +266,8 @@ int ifhip_webp_lossy_encode_batch_device(ifhip_webp_lossy_enc_stage* stage, cons
                                                     stage->width * 4u, n_images, stage->d_inner_files, stage->inner_pitch, stage->d_inner_len,
                                                     stage->d_inner_len + stage->max_images, hip_stream)) return rc;
     if (stops("alpha")) { HIP_TRY(hipGetLastError()); return IFHIP_OK; }
-    hipLaunchKernelGGL(vp8e_code_kernel, dim3(n_images), dim3(64u * kVp8eWaves), 0, st, a);
+    if (stage->flags & kVp8eIntra4) vp8e_launch_code4(a, st);
+    else hipLaunchKernelGGL(vp8e_code_kernel, dim3(n_images), dim3(64u * kVp8eWaves), 0, st, a);
     if (stops("code")) { HIP_TRY(hipGetLastError()); return IFHIP_OK; }
     hipLaunchKernelGGL(vp8e_count_kernel, dim3(static_cast<uint32_t>((mbs + 255u) / 256u), n_images), dim3(256), 0, st, a);
     hipLaunchKernelGGL(vp8e_decide_kernel, dim3(n_images), dim3(64), 0, st, a);
@@ -309,10 +281,15 @@ int ifhip_webp_lossy_encode_batch_device(ifhip_webp_lossy_enc_stage* stage, cons
 
 int ifhip_webp_lossy_encode(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int alpha_meaningful, float quality, uint8_t* out, size_t capacity,
                             size_t* len) {
+    return ifhip_webp_lossy_encode_flags(bgra, width, height, stride, alpha_meaningful, quality, 0u, out, capacity, len);
+}
+
+int ifhip_webp_lossy_encode_flags(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int alpha_meaningful, float quality, uint32_t flags, uint8_t* out,
+                                  size_t capacity, size_t* len) {
     uint32_t status = 0;
     if (int rc = encode_host_frame(
             bgra, width, height, stride, out, capacity, len, &status,
-            [&](ifhip_webp_lossy_enc_stage** s) { return ifhip_webp_lossy_enc_stage_create(s, width, height, alpha_meaningful, 1); }, ifhip_webp_lossy_enc_stage_destroy,
+            [&](ifhip_webp_lossy_enc_stage** s) { return ifhip_webp_lossy_enc_stage_create_flags(s, width, height, alpha_meaningful, 1, flags); }, ifhip_webp_lossy_enc_stage_destroy,
             ifhip_webp_lossy_enc_stage_max_file_bytes, [&](ifhip_webp_lossy_enc_stage* s, const HostFrame& f, size_t pitch, uint32_t* d_len) {
                 return ifhip_webp_lossy_encode_batch_device(s, f.d, f.image_bytes, stride, 1, quality, f.side_output(), pitch, d_len, d_len + 1, nullptr);
             })) return rc;

@@ -1,13 +1,15 @@
 // vp8_encode_core.hpp -- the one statement of the device lossy WebP coder: one VP8 key frame (RFC 6386, profile 0, no
-// segments, whole-macroblock modes only) and its RIFF framing with an optional VP8L-coded ALPH plane.  The kernels of
-// csrc/vp8_encode.hip and the CPU emulation of the tests (tests/vp8_encode_emulate.cpp) are built from the same functions.
+// segments; whole-macroblock modes, and the sixteen 4x4 luma modes of a macroblock where kVp8eIntra4 asks for them) and its RIFF
+// framing with an optional VP8L-coded ALPH plane.  The kernels of csrc/vp8_encode.hip and csrc/vp8_encode_intra4.hip and the CPU
+// emulations of the tests (tests/vp8_encode_emulate.cpp, tests/vp8_encode_intra4_emulate.cpp) are built from the same functions.
 // It stands on vp8_decode_core.hpp: prediction, dequantisation, the inverse WHT and DCT and the store into the planes are the
 // decoder's own functions, fed with the decoder's own macroblock record, so that what the coder reconstructs is what a
 // decoder will see.  The contract is not libwebp's bytes: device file == emulation file, and libwebp decodes that file to
 // the pixels the emulation expects.
 //
 // Known differences from libwebp's encoder, by choice: chroma is a plain box average of the 2x2 RGB sums (no gamma-aware
-// averaging, no sharp YUV); 16x16 luma modes only; one segment; one pass; the RGB under transparent pixels is coded as it is.
+// averaging, no sharp YUV); 16x16 luma modes only unless kVp8eIntra4 is set; one segment; one pass; the RGB under transparent
+// pixels is coded as it is.
 //
 // Every function with lanes in its signature is written for `nlanes` cooperating lanes (a wave on the device, one on the CPU)
 // with sync() between the phases that hand values from lane to lane.
@@ -25,6 +27,8 @@ constexpr uint32_t kVp8eFileOverflow = 1;        // include/imageflow_hip_webp_l
 constexpr uint32_t kVp8eMaxLevel = 2047;
 constexpr uint32_t kVp8eProbs = 4u * 8u * 3u * 11u;
 constexpr uint32_t kVp8eFirstPartMax = (1u << 19) - 1u;      // the frame tag holds the first partition's size in 19 bits
+constexpr uint32_t kVp8eIntra4 = 1;              // include/imageflow_hip_webp_lossy_enc.h IFHIP_VP8_ENC_INTRA4: a macroblock may take sixteen 4x4 luma modes
+constexpr uint32_t kVp8eIntra4Penalty = 8;       // bits a B_PRED macroblock is charged: the best mean gain of the family {0, 2, 4, 8, 16}
 constexpr uint32_t kVp8eFilterNum = 8;           // vp8e_filter_level = index / 2: the best mean PSNR of the family {0, 2, 4, 6, 8} / 16
 
 // the format's constants where device code can reach them (csrc/vp8_tables.inc on the host, a device copy at the stage)
@@ -34,7 +38,14 @@ struct Vp8eTables {
     uint8_t proba0[kVp8eProbs], update[kVp8eProbs];
     uint8_t zigzag[16], bands[17];
     uint8_t cat[4][12];
+    // the sixteen 4x4 modes of a B_PRED macroblock: the contextual probabilities [above][left][tree node], each mode's way down
+    // kVp8BModeTree as (node << 1 | bit) entries behind their count, and what the way costs under every context (vp8e_cost units)
+    uint8_t bmode_proba[10][10][9];
+    uint8_t bmode_path[10][10];
+    uint16_t bmode_cost[10][10][10];
+    uint32_t bmode_dearest;             // the largest entry of bmode_cost
 };
+IFHIP_HD uint32_t vp8e_cost(uint32_t p);
 // (host only)
 inline const Vp8eTables& vp8e_host_tables() {
     static const Vp8eTables T = [] {
@@ -48,7 +59,24 @@ inline const Vp8eTables& vp8e_host_tables() {
         for (int i = 0; i < 5; ++i) t.cat[1][i] = kVp8Cat4[i];
         for (int i = 0; i < 6; ++i) t.cat[2][i] = kVp8Cat5[i];
         for (int i = 0; i < 12; ++i) t.cat[3][i] = kVp8Cat6[i];
-        (void)kVp8BModesProba; (void)kVp8BModeTree;
+        for (int a = 0; a < 10; ++a) for (int l = 0; l < 10; ++l) for (int n = 0; n < 9; ++n) t.bmode_proba[a][l][n] = kVp8BModesProba[a][l][n];
+        // the tree as the decoder walks it (csrc/vp8_read.cpp): node n has the children tree[2n] and tree[2n + 1]; above 0 a node, else leaf -child
+        struct Walk { static void go(Vp8eTables& tt, const int8_t* tree, int node, uint8_t* path, int depth) {
+            for (int bit = 0; bit < 2; ++bit) {
+                const int child = tree[2 * node + bit];
+                path[depth] = static_cast<uint8_t>(node << 1 | bit);
+                if (child > 0) go(tt, tree, child, path, depth + 1);
+                else { tt.bmode_path[-child][0] = static_cast<uint8_t>(depth + 1); for (int i = 0; i <= depth; ++i) tt.bmode_path[-child][1 + i] = path[i]; }
+            }
+        } };
+        uint8_t path[9];
+        Walk::go(t, kVp8BModeTree, 0, path, 0);
+        for (int a = 0; a < 10; ++a) for (int l = 0; l < 10; ++l) for (int m = 0; m < 10; ++m) {
+            uint32_t c = 0;
+            for (uint32_t i = 0; i < t.bmode_path[m][0]; ++i) { const uint32_t e = t.bmode_path[m][1u + i], pr = t.bmode_proba[a][l][e >> 1]; c += vp8e_cost((e & 1u) ? 256u - pr : pr); }
+            t.bmode_cost[a][l][m] = static_cast<uint16_t>(c);
+            if (c > t.bmode_dearest) t.bmode_dearest = c;
+        }
         return t;
     }();
     return T;
@@ -66,7 +94,8 @@ inline uint32_t vp8e_quality_to_index(float quality) {
 struct Vp8eParams {
     Vp8Quant q;
     uint32_t index, filter_level, lambda, n_parts, log2_parts;
-    uint8_t limit, ilevel, hev, pad;
+    uint8_t limit, ilevel, hev;
+    uint8_t i4_penalty;                 // whole bits a B_PRED macroblock is charged beyond its exact price (kVp8eIntra4Penalty)
 };
 IFHIP_HD uint32_t vp8e_filter_level(uint32_t index, uint32_t num) { const uint32_t l = (index * num) >> 4; return l > 63u ? 63u : l; }
 IFHIP_HD uint32_t vp8e_partitions_log2(uint32_t mbh) { return mbh >= 8u ? 3u : mbh >= 4u ? 2u : mbh >= 2u ? 1u : 0u; }
@@ -84,6 +113,7 @@ IFHIP_HD Vp8eParams vp8e_params(const Vp8eTables& T, uint32_t index, uint32_t mb
     const uint32_t ac = p.q.y1[1];
     p.lambda = (ac * ac * 3u) >> 5;                          // what a bit is worth in squared error
     if (p.lambda < 1u) p.lambda = 1u;
+    p.i4_penalty = static_cast<uint8_t>(kVp8eIntra4Penalty);
     p.log2_parts = vp8e_partitions_log2(mbh);
     p.n_parts = 1u << p.log2_parts;
     return p;
@@ -158,7 +188,8 @@ IFHIP_HD void vp8e_fwht(const int* dc, int* out) {           // the sixteen luma
     }
 }
 // quantisation with a dead zone: bias / 256 of a step is added before the division (128 would round to nearest)
-enum : uint32_t { kVp8eBiasY1Ac = 110, kVp8eBiasY2Dc = 96, kVp8eBiasY2Ac = 108, kVp8eBiasUvDc = 110, kVp8eBiasUvAc = 115 };
+enum : uint32_t { kVp8eBiasY1Ac = 110, kVp8eBiasY2Dc = 96, kVp8eBiasY2Ac = 108, kVp8eBiasUvDc = 110, kVp8eBiasUvAc = 115,
+                  kVp8eBiasI4Dc = 96 };          // the DC of a 4x4-mode luma block: a y1 DC level inside the block
 IFHIP_HD int vp8e_quantise(int coef, uint32_t step, uint32_t bias) {
     const uint32_t a = static_cast<uint32_t>(vp8_abs(coef));
     uint32_t level = (a + ((step * bias) >> 8)) / step;
@@ -212,8 +243,44 @@ IFHIP_HD Vp8Mb vp8e_mb_record(const Vp8eParams& p, const int16_t* lv, uint32_t y
     }
     mb.limit = p.limit; mb.ilevel = p.ilevel; mb.hev = p.hev;
     mb.inner = coded ? 1 : 0;
+    mb.pad = (mb.nz >> 24) & 1u ? 3u : 0u;                  // the Y2 contexts it hands on (vp8e_ctx_left, vp8e_ctx_above): its own Y2 block's
     return mb;
 }
+// The record of a B_PRED macroblock: sixteen 4x4 modes, no Y2 block, luma blocks that start at their DC, inner edges always
+// filtered.  y2_left, y2_above: the Y2 contexts it found, which it hands on as they are (below).
+IFHIP_HD Vp8Mb vp8e_mb_record4(const Vp8eParams& p, const int16_t* lv, const uint8_t* imodes, uint32_t uvmode, uint32_t y2_left, uint32_t y2_above) {
+    Vp8Mb mb{};
+    mb.ymode = static_cast<uint8_t>(kVp8ModeB); mb.uvmode = static_cast<uint8_t>(uvmode);
+    for (uint32_t b = 0; b < 16u; ++b) {
+        const uint32_t nz = vp8e_last(lv + 16u * b);
+        mb.imodes[b] = imodes[b];
+        if (nz) mb.nz |= 1u << b;
+        if (nz <= 1u) mb.dc_only |= 1u << b; else if (nz <= 3u) mb.ac3 |= 1u << b;
+    }
+    for (uint32_t ch = 0; ch < 4u; ch += 2u) {
+        bool plane_full = false;
+        for (uint32_t k = 0; k < 4u; ++k) {
+            const uint32_t b = 16u + 2u * ch + k, nz = vp8e_last(lv + 16u * b);
+            if (nz) mb.nz |= 1u << b;
+            if (nz > 1u) plane_full = true;
+        }
+        if (!plane_full) mb.dc_only |= 0xFu << (16u + 2u * ch);
+    }
+    mb.limit = p.limit; mb.ilevel = p.ilevel; mb.hev = p.hev;
+    mb.inner = 1;
+    mb.pad = static_cast<uint8_t>((y2_left & 1u) | (y2_above & 1u) << 1);
+    return mb;
+}
+// The Y2 context trap: a B_PRED macroblock has no Y2 block and leaves the left and the above Y2 context as it found them, so
+// the context of a 16x16 macroblock's Y2 block is that of the NEAREST macroblock with a Y2 block along its row and up its
+// column -- two chains, which differ.  Each record carries what it hands on in its pad byte (the decoder does not read it):
+// bit 0 to the right, bit 1 downwards.  Row starts and the top row are 0.  The word a macroblock's tokens take for a
+// neighbour is its nz with bit 24 replaced by the chain's bit.
+IFHIP_HD uint32_t vp8e_ctx_left(const Vp8Mb& left) { return (left.nz & 0xFFFFFFu) | static_cast<uint32_t>(left.pad & 1u) << 24; }
+IFHIP_HD uint32_t vp8e_ctx_above(const Vp8Mb& above) { return (above.nz & 0xFFFFFFu) | static_cast<uint32_t>((above.pad >> 1) & 1u) << 24; }
+// The sub-mode a neighbouring macroblock shows to the contexts of kVp8BModesProba at its sub-block b: its own where it is B_PRED,
+// the sub-mode of its 16x16 mode's number otherwise (DC TM V H -> DC TM VE HE, as csrc/vp8_read.cpp spreads it), B_DC outside the frame.
+IFHIP_HD uint32_t vp8e_bmode_of(const Vp8Mb* mb, uint32_t b) { return !mb ? 0u : mb->ymode == kVp8ModeB ? mb->imodes[b] : mb->ymode; }
 IFHIP_HD bool vp8e_mb_skipped(const Vp8Mb& mb) { return (mb.nz & 0x1FFFFFFu) == 0u; }
 
 // ---- one macroblock: mode decision, forward path, reconstruction --------------------------------------------------------------
@@ -244,10 +311,11 @@ IFHIP_HD void vp8e_block_diff(const uint8_t* src, const uint8_t* rec, uint32_t p
         d[i] = static_cast<int>(src[static_cast<size_t>(y0 + py) * pitch + x0 + px]) - pred[i];
     }
 }
+// The trial of the whole-macroblock modes: W.ymode, W.uvmode and the levels of every mode in W.  luma_cost (nullable): where
+// lane 0 leaves the chosen luma mode's squared error + lambda * bits.
 template <typename Sync>
-IFHIP_HD void vp8e_code_mb(const Vp8eTables& T, const Vp8eFrame& F, Vp8eMbWork& W, uint32_t mbx, uint32_t mby, uint32_t lane, uint32_t nlanes, Sync sync) {
+IFHIP_HD void vp8e_try_mb(const Vp8eFrame& F, Vp8eMbWork& W, uint32_t mbx, uint32_t mby, uint32_t lane, uint32_t nlanes, Sync sync, uint64_t* luma_cost) {
     const Vp8Quant& q = F.p.q;
-    const size_t m = static_cast<size_t>(mby) * F.src.mbw + mbx;
     // luma, phase 1: every (mode, block) -- prediction, differences, forward DCT; the AC levels, the DC set aside for the WHT
     for (uint32_t t = lane; t < 64u; t += nlanes) {
         const uint32_t mode = t >> 4, b = t & 15u;
@@ -339,8 +407,15 @@ IFHIP_HD void vp8e_code_mb(const Vp8eTables& T, const Vp8eFrame& F, Vp8eMbWork& 
             const uint64_t ccost = csse + F.p.lambda * cbits;
             if (ccost < cbest) { cbest = ccost; W.uvmode = mode; }
         }
+        if (luma_cost) *luma_cost = best;
     }
     sync();
+}
+// the chosen whole-macroblock modes into the frame
+template <typename Sync>
+IFHIP_HD void vp8e_store_mb(const Vp8eFrame& F, Vp8eMbWork& W, uint32_t mbx, uint32_t mby, uint32_t lane, uint32_t nlanes, Sync sync) {
+    const Vp8Quant& q = F.p.q;
+    const size_t m = static_cast<size_t>(mby) * F.src.mbw + mbx;
     // the levels of the chosen modes, in the decoder's layout; the record; the decoder's residuals and its store into the planes
     int16_t* out = F.levels + m * kVp8MbLevels;
     for (uint32_t i = lane; i < kVp8MbLevels; i += nlanes) {
@@ -353,6 +428,122 @@ IFHIP_HD void vp8e_code_mb(const Vp8eTables& T, const Vp8eFrame& F, Vp8eMbWork& 
     for (uint32_t b = lane; b < 24u; b += nlanes) vp8_residual_mb_block(W.res, W.mb, q, b);
     sync();
     vp8_predict_mb(F.rec, W.mb, W.res, mbx, mby, lane, nlanes);
+    sync();
+}
+template <typename Sync>
+IFHIP_HD void vp8e_code_mb(const Vp8eTables&, const Vp8eFrame& F, Vp8eMbWork& W, uint32_t mbx, uint32_t mby, uint32_t lane, uint32_t nlanes, Sync sync) {
+    vp8e_try_mb(F, W, mbx, mby, lane, nlanes, sync, nullptr);
+    vp8e_store_mb(F, W, mbx, mby, lane, nlanes, sync);
+}
+
+// ---- the sixteen 4x4 luma modes (kVp8eIntra4) ---------------------------------------------------------------------------------------
+// Sub-block (bx, by) needs its left, above and above-right neighbours reconstructed: the sub-blocks run on the anti-diagonal
+// schedule bx + 2 by, ten steps of at most two sub-blocks, the (sub-block, mode) pairs of a step a lane each.  The candidate
+// reconstruction lives in a tile with its edge (vp8_decode_core.hpp), the candidates' levels beside it: nothing of a B_PRED
+// trial touches the planes before it has won.
+struct Vp8eI4Work {
+    uint8_t tile[kVp8TileBytes];
+    int16_t cand_lv[20][16];            // per (sub-block of the step, mode): levels, reconstruction, cost
+    uint8_t cand_rec[20][16];
+    uint64_t cand_cost[20];
+    int16_t lv[16][16];                 // the chosen modes' levels
+    uint64_t block_cost[16];
+    uint8_t imodes[16];
+    uint8_t above_modes[4], left_modes[4];      // the sub-mode contexts from the macroblocks above and to the left
+    uint64_t cost16, cost4;             // in 1 / 256 of the decision's unit: (squared error + lambda * bits) * 256
+    uint32_t y2_left, y2_above, i4;
+};
+struct Vp8eMb4Work { Vp8eMbWork w; Vp8eI4Work i4; };
+IFHIP_HD uint32_t vp8e_i4_first_row(uint32_t step) { return step > 3u ? (step - 2u) >> 1 : 0u; }        // the by of a step's first sub-block: bx = step - 2 by <= 3
+IFHIP_HD uint32_t vp8e_i4_count(uint32_t step) { const uint32_t last = step >> 1 < 3u ? step >> 1 : 3u; return last - vp8e_i4_first_row(step) + 1u; }
+template <typename Sync>
+IFHIP_HD void vp8e_try_intra4(const Vp8eTables& T, const Vp8eFrame& F, Vp8eI4Work& W, uint32_t mbx, uint32_t mby, uint32_t lane, uint32_t nlanes, Sync sync) {
+    const Vp8Quant& q = F.p.q;
+    const uint32_t mbw = F.src.mbw;
+    const size_t m = static_cast<size_t>(mby) * mbw + mbx;
+    for (uint32_t i = lane; i < 37u; i += nlanes) vp8_tile_load_edge(W.tile, F.rec.y, F.rec.ypitch, mbw, mbx, mby, i);
+    for (uint32_t i = lane; i < 8u; i += nlanes) {
+        if (i < 4u) W.above_modes[i] = static_cast<uint8_t>(vp8e_bmode_of(mby ? &F.mbs[m - mbw] : nullptr, 12u + i));
+        else W.left_modes[i - 4u] = static_cast<uint8_t>(vp8e_bmode_of(mbx ? &F.mbs[m - 1u] : nullptr, 4u * (i - 4u) + 3u));
+    }
+    sync();
+    for (uint32_t step = 0; step < 10u; ++step) {
+        const uint32_t by0 = vp8e_i4_first_row(step), n = vp8e_i4_count(step);
+        for (uint32_t t = lane; t < 10u * n; t += nlanes) {
+            const uint32_t mode = t % 10u, by = by0 + t / 10u, bx = step - 2u * by, b = 4u * by + bx;
+            int Tp[8], L[4], X, pred[16], d[16], c[16];
+            vp8_tile_sub_edge(W.tile, bx, by, Tp, L, &X);
+            vp8_pred_sub16(mode, Tp, L, X, pred);
+            const uint8_t* src = F.src.y + static_cast<size_t>(mby * 16u + 4u * by) * F.src.ypitch + mbx * 16u + 4u * bx;
+            VP8_UNROLL
+            for (uint32_t i = 0; i < 16u; ++i) d[i] = static_cast<int>(src[static_cast<size_t>(i >> 2) * F.src.ypitch + (i & 3u)]) - pred[i];
+            vp8e_fdct(d, c);
+            int16_t blk[16];
+            uint32_t bits = 0;
+            VP8_UNROLL
+            for (uint32_t i = 0; i < 16u; ++i) {
+                const int l = vp8e_quantise(c[i], i ? q.y1[1] : q.y1[0], i ? kVp8eBiasY1Ac : kVp8eBiasI4Dc);
+                blk[i] = static_cast<int16_t>(l); W.cand_lv[t][i] = static_cast<int16_t>(l); bits += vp8e_level_bits(l);
+            }
+            const uint32_t nz = vp8e_last(blk);
+            if (nz) vp8_residual_block(blk, vp8_dequant(blk[0], q.y1[0]), q.y1[1], nz <= 1u, !(nz == 2u || nz == 3u));
+            uint32_t sse = 0;
+            VP8_UNROLL
+            for (uint32_t i = 0; i < 16u; ++i) {
+                const int r = vp8_clip8(pred[i] + blk[i]), e = pred[i] + d[i] - r;
+                W.cand_rec[t][i] = static_cast<uint8_t>(r); sse += static_cast<uint32_t>(e * e);
+            }
+            const uint32_t above = by ? W.imodes[b - 4u] : W.above_modes[bx], left = bx ? W.imodes[b - 1u] : W.left_modes[by];
+            W.cand_cost[t] = (static_cast<uint64_t>(sse) + static_cast<uint64_t>(F.p.lambda) * bits) * 256u + static_cast<uint64_t>(F.p.lambda) * T.bmode_cost[above][left][mode];
+        }
+        sync();
+        for (uint32_t j = lane; j < n; j += nlanes) {             // the cheapest mode of each sub-block, a tie to the lower number
+            const uint32_t by = by0 + j, bx = step - 2u * by, b = 4u * by + bx;
+            uint32_t best = 0;
+            for (uint32_t mode = 1; mode < 10u; ++mode) if (W.cand_cost[10u * j + mode] < W.cand_cost[10u * j + best]) best = mode;
+            const uint32_t t = 10u * j + best;
+            W.imodes[b] = static_cast<uint8_t>(best); W.block_cost[b] = W.cand_cost[t];
+            uint8_t* dst = W.tile + (1u + 4u * by) * kVp8TilePitch + 1u + 4u * bx;
+            for (uint32_t i = 0; i < 16u; ++i) { W.lv[b][i] = W.cand_lv[t][i]; dst[(i >> 2) * kVp8TilePitch + (i & 3u)] = W.cand_rec[t][i]; }
+        }
+        sync();
+    }
+}
+// One macroblock under kVp8eIntra4: the whole-macroblock trial as ever, the 4x4 trial, and B_PRED where that is cheaper -- each
+// side with its bit of the is_i4 flag under its probability 145; a tie goes to 16x16.  The winner is stored once.  Needs the
+// macroblocks to the left, above, above-left and above-right finished: skew 2.
+template <typename Sync>
+IFHIP_HD void vp8e_code_mb4(const Vp8eTables& T, const Vp8eFrame& F, Vp8eMb4Work& W4, uint32_t mbx, uint32_t mby, uint32_t lane, uint32_t nlanes, Sync sync) {
+    Vp8eMbWork& W = W4.w;
+    Vp8eI4Work& I = W4.i4;
+    const Vp8Quant& q = F.p.q;
+    const size_t m = static_cast<size_t>(mby) * F.src.mbw + mbx;
+    vp8e_try_mb(F, W, mbx, mby, lane, nlanes, sync, &I.cost16);
+    vp8e_try_intra4(T, F, I, mbx, mby, lane, nlanes, sync);
+    if (lane == 0u) {
+        uint64_t c4 = static_cast<uint64_t>(F.p.lambda) * (vp8e_cost(145u) + 256u * F.p.i4_penalty);
+        for (uint32_t b = 0; b < 16u; ++b) c4 += I.block_cost[b];
+        I.cost4 = c4;
+        I.cost16 = I.cost16 * 256u + static_cast<uint64_t>(F.p.lambda) * vp8e_cost(256u - 145u);
+        I.i4 = I.cost4 < I.cost16 ? 1u : 0u;
+        I.y2_left = mbx ? F.mbs[m - 1u].pad & 1u : 0u;
+        I.y2_above = mby ? (F.mbs[m - F.src.mbw].pad >> 1) & 1u : 0u;
+    }
+    sync();
+    if (!I.i4) { vp8e_store_mb(F, W, mbx, mby, lane, nlanes, sync); return; }      // (uniform over the lanes)
+    int16_t* out = F.levels + m * kVp8MbLevels;
+    for (uint32_t i = lane; i < kVp8MbLevels; i += nlanes) {
+        const int16_t v = i < 256u ? I.lv[i >> 4][i & 15u] : i < 384u ? W.cv[W.uvmode][i - 256u] : 0;
+        out[i] = v; W.res[i] = v;
+    }
+    sync();
+    if (lane == 0u) { W.mb = vp8e_mb_record4(F.p, W.res, I.imodes, W.uvmode, I.y2_left, I.y2_above); F.mbs[m] = W.mb; }
+    sync();
+    for (uint32_t b = 16u + lane; b < 24u; b += nlanes) vp8_residual_mb_block(W.res, W.mb, q, b);
+    sync();
+    for (uint32_t i = lane; i < 256u; i += nlanes)             // luma: the tile holds what the decoder's vp8_predict_sub will make of these levels
+        F.rec.y[static_cast<size_t>(mby * 16u + (i >> 4)) * F.rec.ypitch + mbx * 16u + (i & 15u)] = I.tile[(1u + (i >> 4)) * kVp8TilePitch + 1u + (i & 15u)];
+    vp8_predict_mb_chroma(F.rec, W.mb, W.res, mbx, mby, lane, nlanes);
     sync();
 }
 
@@ -391,15 +582,17 @@ IFHIP_HD void vp8e_put_block(const Vp8eTables& T, const int16_t* blk, uint32_t t
         ++n; band = T.bands[n]; ctx = v == 1u ? 1u : 2u;
     }
 }
-// The tokens of a macroblock that is not skipped.  above, left: the nz words of those macroblocks' records (0 outside the frame):
-// a block's context is the sum of the non-zero flags of the blocks above it and to its left, which depend on their levels alone.
+// The tokens of a macroblock that is not skipped.  above, left: vp8e_ctx_above / vp8e_ctx_left of those macroblocks' records (0
+// outside the frame; their nz words where no macroblock of the frame is B_PRED): a block's context is the sum of the non-zero
+// flags of the blocks above it and to its left, which depend on their levels alone; bit 24 is the Y2 chain's (above).
 template <typename Sink>
 IFHIP_HD void vp8e_mb_tokens(const Vp8eTables& T, const int16_t* lv, const Vp8Mb& mb, uint32_t above, uint32_t left, Sink& s) {
-    vp8e_put_block(T, lv + 16u * 24u, 1u, ((above >> 24) & 1u) + ((left >> 24) & 1u), 0u, s);
+    const bool i4 = mb.ymode == kVp8ModeB;                 // no Y2 block; luma blocks of type 3 from their first coefficient
+    if (!i4) vp8e_put_block(T, lv + 16u * 24u, 1u, ((above >> 24) & 1u) + ((left >> 24) & 1u), 0u, s);
     for (uint32_t b = 0; b < 16u; ++b) {
         const uint32_t t = b < 4u ? (above >> (12u + b)) & 1u : (mb.nz >> (b - 4u)) & 1u;
         const uint32_t l = (b & 3u) == 0u ? (left >> (b + 3u)) & 1u : (mb.nz >> (b - 1u)) & 1u;
-        vp8e_put_block(T, lv + 16u * b, 0u, t + l, 1u, s);
+        vp8e_put_block(T, lv + 16u * b, i4 ? 3u : 0u, t + l, i4 ? 0u : 1u, s);
     }
     for (uint32_t b = 16u; b < 24u; ++b) {
         const uint32_t k = (b - 16u) & 3u;
@@ -499,8 +692,9 @@ struct Vp8eCodeSink {
 };
 
 // the first partition: the frame header, the probability updates, then skip flag and modes of every macroblock
+// (mbw: the macroblocks of a row, for the sub-mode contexts of B_PRED macroblocks; a frame without them does not look at it)
 IFHIP_HD uint32_t vp8e_first_partition(const Vp8eTables& T, const Vp8eParams& p, const uint8_t* probs, const uint8_t* updated, uint32_t skip_p, const Vp8Mb* mbs, size_t n_mbs,
-                                       uint8_t* out, uint32_t cap) {
+                                       uint8_t* out, uint32_t cap, uint32_t mbw = 0u) {
     Vp8eBool e;
     e.init(out, cap);
     e.put(0u, 128u); e.put(0u, 128u);                         // colour space, clamping type
@@ -519,9 +713,20 @@ IFHIP_HD uint32_t vp8e_first_partition(const Vp8eTables& T, const Vp8eParams& p,
     for (size_t m = 0; m < n_mbs; ++m) {
         const Vp8Mb& mb = mbs[m];
         e.put(vp8e_mb_skipped(mb) ? 1u : 0u, skip_p);
-        e.put(1u, 145u);
-        if (mb.ymode == 1u || mb.ymode == 3u) { e.put(1u, 156u); e.put(mb.ymode == 1u ? 1u : 0u, 128u); }
-        else { e.put(0u, 156u); e.put(mb.ymode == 2u ? 1u : 0u, 163u); }
+        if (mb.ymode == kVp8ModeB) {
+            e.put(0u, 145u);
+            const Vp8Mb* above = m >= mbw ? &mbs[m - mbw] : nullptr;
+            const Vp8Mb* left = m % mbw ? &mbs[m - 1u] : nullptr;
+            for (uint32_t b = 0; b < 16u; ++b) {
+                const uint32_t a = b >= 4u ? mb.imodes[b - 4u] : vp8e_bmode_of(above, 12u + b), l = (b & 3u) ? mb.imodes[b - 1u] : vp8e_bmode_of(left, b + 3u);
+                const uint8_t* path = T.bmode_path[mb.imodes[b]];
+                for (uint32_t i = 0; i < path[0]; ++i) e.put(path[1u + i] & 1u, T.bmode_proba[a][l][path[1u + i] >> 1]);
+            }
+        } else {
+            e.put(1u, 145u);
+            if (mb.ymode == 1u || mb.ymode == 3u) { e.put(1u, 156u); e.put(mb.ymode == 1u ? 1u : 0u, 128u); }
+            else { e.put(0u, 156u); e.put(mb.ymode == 2u ? 1u : 0u, 163u); }
+        }
         if (mb.uvmode == 0u) e.put(0u, 142u);
         else if (mb.uvmode == 2u) { e.put(1u, 142u); e.put(0u, 114u); }
         else { e.put(1u, 142u); e.put(1u, 114u); e.put(mb.uvmode == 1u ? 1u : 0u, 183u); }
@@ -538,7 +743,7 @@ IFHIP_HD uint32_t vp8e_token_partition(const Vp8eTables& T, const uint8_t* probs
         for (uint32_t x = 0; x < mbw; ++x) {
             const size_t m = static_cast<size_t>(y) * mbw + x;
             if (vp8e_mb_skipped(mbs[m])) continue;
-            vp8e_mb_tokens(T, levels + m * kVp8MbLevels, mbs[m], y ? mbs[m - mbw].nz : 0u, x ? mbs[m - 1u].nz : 0u, s);
+            vp8e_mb_tokens(T, levels + m * kVp8MbLevels, mbs[m], y ? vp8e_ctx_above(mbs[m - mbw]) : 0u, x ? vp8e_ctx_left(mbs[m - 1u]) : 0u, s);
         }
     return e.finish();
 }
@@ -552,12 +757,24 @@ IFHIP_HD uint32_t vp8e_token_partition(const Vp8eTables& T, const uint8_t* probs
 constexpr uint32_t kVp8eMbTokenBytes = (400u * 53u + 25u * 3u + 7u) / 8u + 4u;
 constexpr uint32_t kVp8eMbModeBytes = 2u;                    // skip flag (3 bits by the same argument) + 7.4 bits of modes
 constexpr uint32_t kVp8eHeaderBytes = (kVp8eProbs * 17u + 64u) / 8u + 8u;
-IFHIP_HD uint64_t vp8e_first_cap(uint64_t n_mbs) { return kVp8eHeaderBytes + n_mbs * kVp8eMbModeBytes; }
+// Under kVp8eIntra4 a macroblock's modes are at most: the skip flag (3 bits), the is_i4 bit under 145, sixteen times the dearest
+// leaf of kVp8BModesProba over all contexts (computed from the table: Vp8eTables::bmode_dearest, 15.3 bits) and the dearest
+// chroma mode: 32 bytes.  The frame tag's 19 bits (kVp8eFirstPartMax) cap the first partition's bound from 16 313 macroblocks
+// on; a real first partition of B_PRED macroblocks (4.4 bytes each on photo-like content) outgrows them at about 120 000.
+// (host only)
+inline uint32_t vp8e_mb_mode_bytes(uint32_t flags) {
+    if (!(flags & kVp8eIntra4)) return kVp8eMbModeBytes;
+    const uint32_t uv = vp8e_cost(256u - 142u) + vp8e_cost(256u - 114u) + vp8e_cost(256u - 183u);       // (the dearer of node 183's two sides)
+    const uint32_t bits256 = 3u * 256u + vp8e_cost(145u) + 16u * vp8e_host_tables().bmode_dearest + uv;
+    const uint32_t bytes = (bits256 + 2047u) / 2048u;
+    return bytes > kVp8eMbModeBytes ? bytes : kVp8eMbModeBytes;
+}
+inline uint64_t vp8e_first_cap(uint64_t n_mbs, uint32_t flags = 0u) { return kVp8eHeaderBytes + n_mbs * vp8e_mb_mode_bytes(flags); }
 IFHIP_HD uint64_t vp8e_part_cap(uint32_t mbw, uint32_t mbh, uint32_t n_parts) { return 8u + static_cast<uint64_t>(mbw) * ((mbh + n_parts - 1u) / n_parts) * kVp8eMbTokenBytes; }
 // alph_bound: the inner lossless coder's bound on a file of the grey frame (0: no alpha plane)
-IFHIP_HD uint64_t vp8e_max_file_bytes(uint32_t w, uint32_t h, uint64_t alph_bound) {
+inline uint64_t vp8e_max_file_bytes(uint32_t w, uint32_t h, uint64_t alph_bound, uint32_t flags = 0u) {
     const uint32_t mbw = (w + 15u) / 16u, mbh = (h + 15u) / 16u, n_parts = 1u << vp8e_partitions_log2(mbh);
-    uint64_t first = vp8e_first_cap(static_cast<uint64_t>(mbw) * mbh);
+    uint64_t first = vp8e_first_cap(static_cast<uint64_t>(mbw) * mbh, flags);
     if (first > kVp8eFirstPartMax) first = kVp8eFirstPartMax;
     uint64_t n = 12u + 8u + 10u + first + 3u * (n_parts - 1u) + n_parts * vp8e_part_cap(mbw, mbh, n_parts) + 1u;
     if (alph_bound) n += 18u + 8u + alph_bound + 1u;

@@ -137,7 +137,9 @@ IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_webp_lossy_decoder(struct imagefl
  * (ifhip_webp_lossy_encode_batch_device: WebPEncoder::write_frame over WebPEncodeBGRA / WebPEncodeBGR, codecs/webp.rs) and reports
  * image/webp; off by default, where the preset writes the raw BGRA container as ever.  With it on, the bare string "webplossy" and a
  * missing or non-numeric quality are InvalidJson before any node runs (the reference's variant is a struct with a required f32), and
- * a side above 16383 is "ImageEncodingError: libwebp encoding error".  Returns true. */
+ * a side above 16383 is "ImageEncodingError: libwebp encoding error".  `on`: 0 off; 2 on with the sixteen 4x4 luma modes
+ * (IFHIP_VP8_ENC_INTRA4 of imageflow_hip_webp_lossy_enc.h: smaller files of textured frames, a longer serial chain); any other
+ * value on as ever.  Returns true. */
 IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_webp_lossy_encoder(struct imageflow_context *context, int on);
 /* EXTENSION: `encode` with the preset "gif" writes a GIF89a file on the device (ifhip_gif_encode_batch_device: GifEncoder::write_frame,
  * codecs/gif/mod.rs:385-592) and reports image/gif; off by default, where the preset writes the raw BGRA container as ever.  A

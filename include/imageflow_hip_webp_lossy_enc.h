@@ -8,7 +8,8 @@
  *
  * The contract is not libwebp's bytes: a file equals the CPU emulation's byte for byte (tests/vp8_encode_emulate.cpp, built
  * from the same csrc/vp8_encode_core.hpp), and libwebp decodes it to exactly the pixels the coder reconstructed.  One VP8 key
- * frame: profile 0, no segments, 16x16 luma modes, the normal loop filter, the largest power of two <= min(8, macroblock
+ * frame: profile 0, no segments, 16x16 luma modes (and the sixteen 4x4 modes of a macroblock where a stage is created with
+ * IFHIP_VP8_ENC_INTRA4; csrc/vp8_encode_intra4.hip), the normal loop filter, the largest power of two <= min(8, macroblock
  * rows) token partitions; the quantiser index follows `quality` (clamped to 0..100) by libwebp's QualityToCompression curve.
  * A frame whose alpha is meaningful and somewhere below 255 gets `VP8X` + `ALPH` (the plane coded by the lossless coder,
  * header byte 0x01); every other frame is a simple `RIFF` / `VP8 ` file. */
@@ -28,10 +29,21 @@ typedef struct ifhip_webp_lossy_enc_stage ifhip_webp_lossy_enc_stage;
  * batch); it is bound to ONE stream at a time. */
 IFHIP_API int ifhip_webp_lossy_enc_stage_create(ifhip_webp_lossy_enc_stage** stage, uint32_t width, uint32_t height,
                                                 int alpha_meaningful, uint32_t max_images);
+/* The same with flags.  IFHIP_VP8_ENC_INTRA4: per macroblock the coder also tries the sixteen 4x4 luma sub-blocks with the ten
+ * modes each and codes the macroblock as B_PRED where that is cheaper than the best 16x16 mode; everything else of the file is
+ * as without the flag, and flags 0 is ifhip_webp_lossy_enc_stage_create to the byte.  Any other flag bit is refused
+ * (InvalidArgument).  The stage carries its flags: the batch call's signature is the same, and
+ * ifhip_webp_lossy_enc_stage_max_file_bytes answers for them. */
+#define IFHIP_VP8_ENC_INTRA4 1u
+IFHIP_API int ifhip_webp_lossy_enc_stage_create_flags(ifhip_webp_lossy_enc_stage** stage, uint32_t width, uint32_t height,
+                                                      int alpha_meaningful, uint32_t max_images, uint32_t flags);
 IFHIP_API void ifhip_webp_lossy_enc_stage_destroy(ifhip_webp_lossy_enc_stage* stage);
 /* a file_pitch with which no file overflows, by arithmetic over the coder's choices (csrc/vp8_encode_core.hpp
  * vp8e_max_file_bytes).  One limit is the format's own: the frame tag holds the first partition's size in 19 bits, which the
- * modes of more than about 230 000 macroblocks can outgrow; such a file gets IFHIP_VP8_ENC_FILE_OVERFLOW. */
+ * modes of more than about 230 000 macroblocks can outgrow; such a file gets IFHIP_VP8_ENC_FILE_OVERFLOW.  With
+ * IFHIP_VP8_ENC_INTRA4 a B_PRED macroblock carries sixteen sub-modes: the bound allows 32 bytes of modes a macroblock and is
+ * capped at the limit from 16 313 macroblocks on (2 040 x 2 040 pixels); files of photo-like content (4.4 bytes a B_PRED
+ * macroblock) reach the limit itself at about 120 000 macroblocks. */
 IFHIP_API size_t ifhip_webp_lossy_enc_stage_max_file_bytes(const ifhip_webp_lossy_enc_stage* stage);
 /* n_images frames of the stage's geometry at d_images + i * image_bytes (rows of `stride` bytes; the frame checks of every
  * batch entry, made before the device is asked for).  Image i's file goes to d_files + i * file_pitch, its length to
@@ -46,6 +58,9 @@ IFHIP_API int ifhip_webp_lossy_encode_batch_device(ifhip_webp_lossy_enc_stage* s
  * is written. */
 IFHIP_API int ifhip_webp_lossy_encode(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int alpha_meaningful,
                                       float quality, uint8_t* out, size_t capacity, size_t* len);
+/* the drop-in with the stage's flags (IFHIP_VP8_ENC_INTRA4) */
+IFHIP_API int ifhip_webp_lossy_encode_flags(const uint8_t* bgra, uint32_t width, uint32_t height, uint32_t stride, int alpha_meaningful,
+                                            float quality, uint32_t flags, uint8_t* out, size_t capacity, size_t* len);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""The device lossy WebP coder on batches of frames (tools/bench_webp_lossy_encode.py [--case NAME] [--reps N] [--quality Q]).
+"""The device lossy WebP coder on batches of frames (tools/bench_webp_lossy_encode.py [--case NAME] [--reps N] [--quality Q] [--intra4]).
+--intra4: stages with IFHIP_VP8_ENC_INTRA4, whose code kernel also tries the sixteen 4x4 luma modes of every macroblock.
 Cases: one and 32 frames of 800x450 and one of 3840x2160, each with and without alpha.  Per case one JSON line, device time by
 events around the call after a warm-up (the frames are in HBM already and the files stay there): the whole call, and the
 kernels by difference -- the development switch vp8_encode_stop_after ends the call behind a launch: convert, the inner
@@ -41,7 +42,7 @@ def psnr(a, b):
     return float(10.0 * np.log10(255.0 ** 2 / max(float(np.mean(d * d)), 1e-12)))
 
 
-def run_case(name, reps=None, quality=75.0):
+def run_case(name, reps=None, quality=75.0, intra4=False):
     import numpy as np
     import torch
     from PIL import Image
@@ -57,7 +58,7 @@ def run_case(name, reps=None, quality=75.0):
     for i, f in enumerate(frames):
         rows[i, :, :4 * w] = f.reshape(h, 4 * w)
     bitmap = Bitmap.from_numpy(rows, w, h, stride, dev, alpha_meaningful=alpha)
-    stage = ENC.WebpLossyEncodeStage(w, h, alpha, n, dev)
+    stage = ENC.WebpLossyEncodeStage(w, h, alpha, n, dev, intra4=intra4)
     pitch = (stage.max_file_bytes + 15) // 16 * 16
     files = torch.empty((n, pitch), dtype=torch.uint8, device=dev)
     lengths, status = torch.zeros(n, dtype=torch.int32, device=dev), torch.zeros(n, dtype=torch.int32, device=dev)
@@ -99,7 +100,7 @@ def run_case(name, reps=None, quality=75.0):
         host_ts.append((time.perf_counter() - t0) * 1e3)
         host_psnr = psnr(np.asarray(Image.open(buf).convert("RGBA"))[..., [2, 1, 0, 3]], frames[-1])
     host = float(np.median(host_ts))
-    res = {"case": name, "frames": n, "w": w, "h": h, "alpha": alpha, "quality": quality, "reps": reps, "device": torch.cuda.get_device_name(0),
+    res = {"case": name, "frames": n, "w": w, "h": h, "alpha": alpha, "quality": quality, "intra4": intra4, "reps": reps, "device": torch.cuda.get_device_name(0),
            "whole_call_ms": round(whole, 3), "convert_ms": round(at["convert"], 3), "inner_lossless_alpha_ms": round(at["alpha"] - at["convert"], 3),
            "code_wavefront_ms": round(at["code"] - at["alpha"], 3), "count_and_decide_ms": round(at["decide"] - at["code"], 3),
            "bool_streams_ms": round(at["streams"] - at["decide"], 3), "layout_ms": round(whole - at["streams"], 3),
@@ -112,11 +113,12 @@ def run_case(name, reps=None, quality=75.0):
 def main():
     reps = int(sys.argv[sys.argv.index("--reps") + 1]) if "--reps" in sys.argv else None
     quality = float(sys.argv[sys.argv.index("--quality") + 1]) if "--quality" in sys.argv else 75.0
+    intra4 = "--intra4" in sys.argv
     if "--case" in sys.argv:
-        run_case(sys.argv[sys.argv.index("--case") + 1], reps, quality)
+        run_case(sys.argv[sys.argv.index("--case") + 1], reps, quality, intra4)
         return 0
     for name, case in CASES.items():
-        cmd = ["timeout", "-k", "10", str(case[-1]), sys.executable, os.path.abspath(__file__), "--case", name, "--quality", str(quality)] + (["--reps", str(reps)] if reps else [])
+        cmd = ["timeout", "-k", "10", str(case[-1]), sys.executable, os.path.abspath(__file__), "--case", name, "--quality", str(quality)] + (["--reps", str(reps)] if reps else []) + (["--intra4"] if intra4 else [])
         rc = subprocess.run(cmd, cwd=ROOT).returncode
         if rc != 0:                                                   # a fault, an abort or the time limit: nothing more runs on this device
             print(json.dumps({"case": name, "exit_status": rc, "stopped": True}), flush=True)
