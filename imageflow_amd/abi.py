@@ -76,6 +76,8 @@ def _bind():
     L.ifhip_shim_context_set_webp_lossy_decoder.restype = C.c_bool
     L.ifhip_shim_context_set_webp_lossy_encoder.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_webp_lossy_encoder.restype = C.c_bool
+    L.ifhip_shim_context_set_webp_lossless_flags.argtypes = [vp, C.c_uint32]
+    L.ifhip_shim_context_set_webp_lossless_flags.restype = C.c_bool
     L.ifhip_shim_context_set_gif_encoder.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_gif_encoder.restype = C.c_bool
     L.ifhip_shim_context_set_gif_animation.argtypes = [vp, C.c_int]
@@ -180,6 +182,11 @@ class Context:
         """EXTENSION, off by default: `encode` with the preset {"webplossy": {"quality": q}} writes a lossy WebP file on the device
         (image/webp) instead of the raw BGRA container; the bare string and a missing or non-numeric quality are then InvalidJson."""
         return self.L.ifhip_shim_context_set_webp_lossy_encoder(self.p, (2 if intra4 else 1) if on else 0)
+
+    def set_webp_lossless_flags(self, color_indexing=False):
+        """EXTENSION, all off by default: the stage flags of the "webplossless" preset's coder.  color_indexing
+        (IFHIP_WEBP_ENC_COLOR_INDEXING): frames of at most 256 colours are written with a colour table where that is smaller."""
+        return self.L.ifhip_shim_context_set_webp_lossless_flags(self.p, 1 if color_indexing else 0)
 
     def set_gif_encoder(self, on):
         """EXTENSION, off by default: `encode` with the preset "gif" writes a GIF89a file on the device (image/gif) instead of

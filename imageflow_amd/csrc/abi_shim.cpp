@@ -1293,8 +1293,10 @@ struct Job {
         // EncoderPreset::WebPLossless (imageflow_types/src/lib.rs:773, codecs/auto.rs:282-319) -> WebPEncoder::write_frame
         // (codecs/webp.rs:281-345: WebPEncodeLosslessBGRA, or ...BGR when the frame's alpha is not meaningful); no matte
         // (the reference passes None).  The file is coded on the device (csrc/webp_encode.hip), only its bytes leave it.
+        // The stage is made per frame with the context's flags (ifhip_shim_context_set_webp_lossless_flags), so none outlives a change of them.
+        const uint32_t flags = c->webp_lossless_flags.load(std::memory_order_relaxed);
         write_coded_frame(
-            f, o, io_id, kWebpNames, 0u, [&](ifhip_webp_enc_stage** s) { return ifhip_webp_enc_stage_create(s, f->w, f->h, f->alpha ? 1 : 0, 1); },
+            f, o, io_id, kWebpNames, 0u, [&](ifhip_webp_enc_stage** s) { return ifhip_webp_enc_stage_create_flags(s, f->w, f->h, f->alpha ? 1 : 0, 1, flags); },
             ifhip_webp_enc_stage_destroy, ifhip_webp_enc_stage_max_file_bytes, [&](ifhip_webp_enc_stage* s, uint8_t* d_file, size_t pitch, uint32_t* d_len) {
                 return ifhip_webp_encode_batch_device(s, dev(f), f->bytes(), f->stride, 1, d_file, pitch, d_len, d_len + 1, t_job_stream);
             });
@@ -2256,6 +2258,13 @@ bool ifhip_shim_context_set_webp_lossy_encoder(struct imageflow_context* c, int 
     CTX_OR_ABORT(c);
     c->webp_lossy_intra4.store(on == 2, std::memory_order_relaxed);
     c->webp_lossy_encoder.store(on != 0, std::memory_order_relaxed);
+    return true;
+}
+// EXTENSION: the stage flags of the "webplossless" preset's coder (see Job::encode_webp_lossless); 0 by default.  An unknown bit is refused.
+bool ifhip_shim_context_set_webp_lossless_flags(struct imageflow_context* c, uint32_t flags) {
+    CTX_OR_ABORT(c);
+    if (flags & ~IFHIP_WEBP_ENC_COLOR_INDEXING) return false;
+    c->webp_lossless_flags.store(flags, std::memory_order_relaxed);
     return true;
 }
 bool ifhip_shim_context_set_color_management(struct imageflow_context* c, int on) {

@@ -161,6 +161,7 @@ struct imageflow_context {
     std::atomic<bool> gif_encoder{false};                // EXTENSION ifhip_shim_context_set_gif_encoder: the "gif" preset writes a GIF on the device
     std::atomic<bool> webp_lossy_decoder{false};         // EXTENSION ifhip_shim_context_set_webp_lossy_decoder: lossy WebP inputs are decoded on the device
     std::atomic<bool> webp_lossy_intra4{false};          // ... with IFHIP_VP8_ENC_INTRA4 (the switch's value 2)
+    std::atomic<uint32_t> webp_lossless_flags{0};        // EXTENSION ifhip_shim_context_set_webp_lossless_flags: the stage flags of the "webplossless" preset's coder
     std::atomic<bool> webp_lossy_encoder{false};         // EXTENSION ifhip_shim_context_set_webp_lossy_encoder: the "webplossy" preset writes a lossy WebP on the device
     std::atomic<bool> color_management{false};           // EXTENSION ifhip_shim_context_set_color_management: every input is converted to sRGB
     bool cancellation_requested() {

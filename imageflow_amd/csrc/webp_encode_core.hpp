@@ -138,6 +138,43 @@ IFHIP_HD uint32_t webp_choose_mode(const uint32_t sums[14]) {           // the s
     return best;
 }
 
+// ---- colour indexing --------------------------------------------------------------------------------------------------------
+// A frame of at most 256 distinct colours may open with the colour-indexing transform instead (IFHIP_WEBP_ENC_COLOR_INDEXING):
+// the palette is the frame's distinct ARGB dwords (alpha 255 where it is not meaningful) in ascending order, so that it does
+// not depend on who found a colour first; the main image holds the indices in green, 8, 4 or 2 of them bundled into one
+// pixel where the palette is small.  Nothing follows the transform: no subtract green, no predictor -- the LZ77 parse
+// and the codes below work on the packed pixels as they work on residuals, with the packed width as the row distance.
+constexpr uint32_t kWebpMaxPalette = 256;
+IFHIP_HD uint32_t webp_index_width_bits(uint32_t n_colours) { return n_colours <= 2u ? 3u : n_colours <= 4u ? 2u : n_colours <= 16u ? 1u : 0u; }
+IFHIP_HD uint32_t webp_packed_width(uint32_t w, uint32_t width_bits) { return (w + (1u << width_bits) - 1u) >> width_bits; }
+// the pixel at (x, y) as the palette holds it
+IFHIP_HD uint32_t webp_argb(const uint8_t* frame, uint32_t stride, uint32_t x, uint32_t y, uint32_t alpha_or) {
+    return *reinterpret_cast<const uint32_t*>(frame + static_cast<size_t>(y) * stride + 4u * x) | alpha_or;
+}
+// where `c` lies in the ascending palette of n entries (it does): a binary search of at most 8 steps
+IFHIP_HD uint32_t webp_palette_index(const uint32_t* pal, uint32_t n, uint32_t c) {
+    uint32_t lo = 0, hi = n;
+    while (hi - lo > 1u) {
+        const uint32_t mid = (lo + hi) >> 1;
+        if (pal[mid] <= c) lo = mid; else hi = mid;
+    }
+    return lo;
+}
+// Packed pixel xp of row y: source pixel x of the bundle sits at bit (x mod 2^bits) * (8 >> bits) of green; alpha is 255,
+// red and blue are 0, and the padding behind the row's last pixel is index 0.
+IFHIP_HD uint32_t webp_bundle(const uint8_t* frame, uint32_t stride, uint32_t w, uint32_t xp, uint32_t y, uint32_t alpha_or, const uint32_t* pal, uint32_t n,
+                              uint32_t width_bits) {
+    const uint32_t per = 1u << width_bits, depth = 8u >> width_bits;
+    uint32_t green = 0;
+    for (uint32_t k = 0; k < per; ++k) {
+        const uint32_t x = xp * per + k;
+        if (x < w) green |= webp_palette_index(pal, n, webp_argb(frame, stride, x, y, alpha_or)) << (k * depth);
+    }
+    return 0xFF000000u | (green << 8);
+}
+// entry i of the colour table as the stream codes it: the difference from the entry before, per channel
+IFHIP_HD uint32_t webp_palette_delta(const uint32_t* pal, uint32_t i) { return i ? webp_sub_pixels(pal[i], pal[i - 1u]) : pal[0]; }
+
 // ---- LZ77 symbols -----------------------------------------------------------------------------------------------------------
 // a length or a distance code v >= 1 as prefix symbol and extra bits
 IFHIP_HD void webp_prefix(uint32_t v, uint32_t* sym, uint32_t* ebits, uint32_t* eval) {
@@ -298,6 +335,13 @@ IFHIP_HD void webp_put_front(uint32_t* hdr, uint32_t* pos, uint32_t w, uint32_t 
     put_bits(hdr, pos, 1u, 1); put_bits(hdr, pos, 2u, 2);
     put_bits(hdr, pos, 1u, 1); put_bits(hdr, pos, 0u, 2); put_bits(hdr, pos, kWebpTileBits - 2u, 3);
     put_bits(hdr, pos, 0u, 1);                                   // the mode sub-image: no colour cache
+}
+// the indexed stream's front: signature, size (the frame's own width), alpha_is_used, version 0; the colour-indexing
+// transform and its table's size: 51 bits in front of the colour table, a size x 1 sub-image without a colour cache
+IFHIP_HD void webp_put_front_indexed(uint32_t* hdr, uint32_t* pos, uint32_t w, uint32_t h, uint32_t alpha, uint32_t n_colours) {
+    put_bits(hdr, pos, 0x2Fu, 8); put_bits(hdr, pos, w - 1u, 14); put_bits(hdr, pos, h - 1u, 14); put_bits(hdr, pos, alpha, 1); put_bits(hdr, pos, 0u, 3);
+    put_bits(hdr, pos, 1u, 1); put_bits(hdr, pos, 3u, 2); put_bits(hdr, pos, n_colours - 1u, 8);
+    put_bits(hdr, pos, 0u, 1);
 }
 // no further transform; the main image: no colour cache, meta prefix codes with their tile bits; the entropy sub-image: no cache
 IFHIP_HD void webp_put_middle(uint32_t* hdr, uint32_t* pos) {

@@ -141,6 +141,11 @@ IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_webp_lossy_decoder(struct imagefl
  * (IFHIP_VP8_ENC_INTRA4 of imageflow_hip_webp_lossy_enc.h: smaller files of textured frames, a longer serial chain); any other
  * value on as ever.  Returns true. */
 IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_webp_lossy_encoder(struct imageflow_context *context, int on);
+/* EXTENSION: the stage flags of the "webplossless" preset's device coder (ifhip_webp_enc_stage_create_flags of imageflow_hip.h), in
+ * steps and graphs alike; 0 by default.  IFHIP_WEBP_ENC_COLOR_INDEXING: a frame of at most 256 colours is written with a colour
+ * table where that is the smaller file; no file grows, and the pixels are the same.  Returns false, and changes nothing, for
+ * a bit the coder does not know.  The lossy coder's alpha planes are not concerned. */
+IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_webp_lossless_flags(struct imageflow_context *context, uint32_t flags);
 /* EXTENSION: `encode` with the preset "gif" writes a GIF89a file on the device (ifhip_gif_encode_batch_device: GifEncoder::write_frame,
  * codecs/gif/mod.rs:385-592) and reports image/gif; off by default, where the preset writes the raw BGRA container as ever.  A
  * GIF input of the job hands its loop count and the selected frame's delay and user-input flag to the file. */

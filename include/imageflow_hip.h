@@ -564,7 +564,7 @@ IFHIP_API int ifhip_png_quantize(const uint8_t* bgra, uint32_t width, uint32_t h
  * in HBM.  A lossless coder is free in its choices: the file is NOT libwebp's byte for byte, it decodes through libwebp to
  * exactly the frame's pixels.  The choices are this coder's own: subtract green, one of the 14 predictors per 16 x 16 tile,
  * matches over the residual pixels one pixel back and one row up, a group of five prefix codes per band of 64 rows, no
- * colour cache, no colour indexing.
+ * colour cache; colour indexing only where the stage's flags ask for it (ifhip_webp_enc_stage_create_flags).
  * alpha_meaningful 0 (normalize_unused_alpha): every pixel is coded with alpha 255 and the header says alpha_is_used = 0.
  * There is no matte (the reference passes None).  A stage owns the scratch of a call in flight (residuals, tokens, symbol
  * counts, code tables, bit offsets; allocated by the first batch) and is bound to ONE stream at a time, like
@@ -574,6 +574,16 @@ typedef struct ifhip_webp_enc_stage ifhip_webp_enc_stage;
 /* refused: zero dimensions, a width or a height above 16384 (the format's 14 bits), max_images outside 1..65535 */
 IFHIP_API int ifhip_webp_enc_stage_create(ifhip_webp_enc_stage** stage, uint32_t width, uint32_t height, int alpha_meaningful,
                                           uint32_t max_images);
+/* The same with flags; 0 is ifhip_webp_enc_stage_create to the byte, an unknown bit is refused.
+ * IFHIP_WEBP_ENC_COLOR_INDEXING: a frame of at most 256 distinct colours (alpha forced to 255 where it is not meaningful) is
+ * also sized as a stream that opens with the colour-indexing transform -- the palette in ascending ARGB order, 8, 4 or 2
+ * indices bundled into a pixel for up to 2, 4 or 16 colours, matches and codes over the packed pixels -- and the smaller of
+ * the two files is written, the plain one on a tie: no file is larger than without the flag, so the bound below holds
+ * unchanged.  A frame of more colours is the file without the flag, byte for byte, at the price of a partial read of it.
+ * The stage then owns a second set of scratch for the packed image. */
+#define IFHIP_WEBP_ENC_COLOR_INDEXING 1u
+IFHIP_API int ifhip_webp_enc_stage_create_flags(ifhip_webp_enc_stage** stage, uint32_t width, uint32_t height, int alpha_meaningful,
+                                                uint32_t max_images, uint32_t flags);
 IFHIP_API void ifhip_webp_enc_stage_destroy(ifhip_webp_enc_stage* stage);
 /* a file_pitch with which no file overflows, by arithmetic over the coder's choices (csrc/webp_encode_core.hpp
  * webp_max_file_bytes): a band that would take more is written as literals under four flat codes, which gives 32 bits a

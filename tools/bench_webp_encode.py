@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Sizes and times of the device lossless-WebP coder, on one GPU:
 
-    python tools/bench_webp_encode.py [--out FILE.json]
+    python tools/bench_webp_encode.py [--out FILE.json] [--only-indexing] [--skip-indexing]
 
 Sizes: the photo-like and flat test frames at 800x450 as this coder writes them, as libwebp writes them through Pillow
 (lossless=True, quality=70, method=4: the simple API's defaults) and as this project's `libpng` coder writes them (RGBA,
@@ -9,7 +9,11 @@ and RGB for the opaque frames).  The frames are tests/webp_frames.py photo(800, 
 seed=62) and flat(800, 450).
 Times: 32 frames of 800x450 and 8 frames of 3840x2160, hipEvents around one batch call after warm-up (median, minimum and
 maximum of the repetitions), beside ONE host core's libwebp on the same frames.  Every device file is decoded through
-Pillow and compared with its source before its size counts."""
+Pillow and compared with its source before its size counts.
+Colour indexing (the stage flag IFHIP_WEBP_ENC_COLOR_INDEXING): few_colours(800, 450), few_colours(800, 450, n=200) and
+flat(800, 450) with the flag off and on -- sizes beside libwebp's, and the times of a lone frame and of 32 -- and the
+photographs again with the flag on, where the coder counts colours, gives up and writes the plain file.  --skip-indexing
+leaves these rows out (the tool then runs on a library without the flag as well), --only-indexing everything else."""
 import argparse
 import io
 import json
@@ -61,10 +65,10 @@ def sizes():
     return out
 
 
-def timed(frames, reps):
+def timed(frames, reps, host=True, **flags):
     n, h, w, _ = frames.shape
     bm = bitmap(frames)
-    stage = WEBP.WebpEncodeStage(w, h, True, n, DEV)
+    stage = WEBP.WebpEncodeStage(w, h, True, n, DEV, **flags)
     pitch = (stage.max_file_bytes + 15) // 16 * 16
     files = torch.empty((n, pitch), dtype=torch.uint8, device=DEV)
     ln, st = torch.zeros(n, dtype=torch.int32, device=DEV), torch.zeros(n, dtype=torch.int32, device=DEV)
@@ -80,24 +84,51 @@ def timed(frames, reps):
         torch.cuda.synchronize()
         ms.append(a.elapsed_time(b))
     assert st.cpu().tolist() == [0] * n
-    host = [libwebp(f)[1] for f in frames[:min(n, 4)]]
     res = {"frames": n, "device_ms_median": float(np.median(ms)), "device_ms_min": float(min(ms)), "device_ms_max": float(max(ms)), "reps": reps,
-           "file_bytes_mean": float(ln.float().mean()), "libwebp_one_core_ms_per_frame": 1000 * float(np.mean(host)),
-           "libwebp_one_core_ms_batch": 1000 * float(np.mean(host)) * n}
-    print(f"{n} x {w}x{h}", res, flush=True)
+           "file_bytes_mean": float(ln.float().mean())}
+    if host:
+        host = [libwebp(f)[1] for f in frames[:min(n, 4)]]
+        res.update({"libwebp_one_core_ms_per_frame": 1000 * float(np.mean(host)), "libwebp_one_core_ms_batch": 1000 * float(np.mean(host)) * n})
+    print(f"{n} x {w}x{h}", flags, res, flush=True)
     return res
+
+
+def indexing():
+    """the frames of few colours, flag off and on: sizes against libwebp, times of a lone frame and of 32 (the same frame rolled)"""
+    out = {}
+    kinds = (("few_colours", F.few_colours(800, 450)), ("few_colours_200", F.few_colours(800, 450, n=200)), ("flat", F.flat(800, 450)),
+             ("photo", F.photo(800, 450, seed=61)))
+    for name, frame in kinds:
+        h, w = frame.shape[:2]
+        row = {"libwebp_q70_m4": libwebp(frame)[0]}
+        for key, on in (("flag_off", False), ("flag_on", True)):
+            data = WEBP.WebpEncodeStage(w, h, True, 1, DEV, color_indexing=on).encode(bitmap(frame[None]))[0][0]
+            assert np.array_equal(np.asarray(Image.open(io.BytesIO(data)).convert("RGBA")), F.rgba_of(frame))
+            batch = np.stack([np.roll(frame, 13 * i, 1) for i in range(32)]) if name != "photo" else np.stack([F.photo(800, 450, seed=70 + i) for i in range(32)])
+            row[key] = {"bytes": len(data), "ratio_to_libwebp": len(data) / row["libwebp_q70_m4"],
+                        "lone": timed(frame[None], 30, host=False, color_indexing=on), "batch_32": timed(batch, 30, host=False, color_indexing=on)}
+        out[name] = row
+        print(name, {k: (v if k == "libwebp_q70_m4" else (v["bytes"], round(v["ratio_to_libwebp"], 3))) for k, v in row.items()}, flush=True)
+    return out
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
+    ap.add_argument("--only-indexing", action="store_true")
+    ap.add_argument("--skip-indexing", action="store_true")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("no GPU: this tool measures on the device and has no fall-back")
-    out = {"sizes": sizes(), "times": {}}
-    out["times"]["32x800x450"] = timed(np.stack([F.photo(800, 450, seed=70 + i) for i in range(32)]), 30)
-    big = F.photo(3840, 2160, seed=80)
-    out["times"]["8x3840x2160"] = timed(np.stack([np.roll(big, 97 * i, 1) for i in range(8)]), 10)
+    out = {}
+    if not args.only_indexing:
+        out = {"sizes": sizes(), "times": {}}
+        out["times"]["32x800x450"] = timed(np.stack([F.photo(800, 450, seed=70 + i) for i in range(32)]), 30)
+        out["times"]["1x800x450"] = timed(F.photo(800, 450, seed=61)[None], 30)
+        big = F.photo(3840, 2160, seed=80)
+        out["times"]["8x3840x2160"] = timed(np.stack([np.roll(big, 97 * i, 1) for i in range(8)]), 10)
+    if not args.skip_indexing:
+        out["color_indexing"] = indexing()
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         json.dump(out, open(args.out, "w"), indent=1)
