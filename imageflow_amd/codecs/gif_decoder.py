@@ -1,7 +1,7 @@
 """Host mirror of GifDecoder (imageflow_core/src/codecs/gif/mod.rs:21-309) on the device GIF decoder of libimageflow_hip.so
 (csrc/gif_read.cpp, csrc/gif_decode.hip): GIF files -> the logical screen after the selected frame as 8-bit BGRA in HBM --
 segment-parallel LZW and the frame replay (dispose, blit) on the GPU.  For tests and tools; the job path is `decode` with a
-GIF io_id and the decoder command {"select_frame": N} (csrc/abi_shim.cpp)."""
+GIF io_id and the decoder command {"select_frame": N} (csrc/shim_decode.cpp)."""
 import ctypes as C
 
 import numpy as np

@@ -1,7 +1,7 @@
 """Host mirror of GifEncoder::write_frame (imageflow_core/src/codecs/gif/mod.rs:385-592 over the gif crate) on the device GIF
 coder of libimageflow_hip.so (csrc/gif_encode.hip): BGRA / BGRX frames that stay in HBM -> complete single-frame GIF89a
 files in HBM.  For tests and tools; the job path is the `"gif"` preset of `encode` on a context whose GIF encoder is
-switched on (Context.set_gif_encoder, csrc/abi_shim.cpp)."""
+switched on (Context.set_gif_encoder, csrc/shim_encode.cpp)."""
 import ctypes as C
 
 import torch

@@ -1,7 +1,7 @@
 """Host mirror of LibPngDecoder (imageflow_core/src/codecs/libpng_decoder.rs:36-104,297-299,340-383 over
 c_components/lib/codec_png_wrapper.c:131-212,215-246,266-292) on the device PNG decoder of libimageflow_hip.so
 (csrc/png_read.cpp, csrc/png_decode.hip): PNG files -> 8-bit BGRA frames in HBM -- inflate, un-filter, libpng's transforms
-and the Adam7 scatter on the GPU.  For tests and tools; the job path is `decode` with a PNG io_id (csrc/abi_shim.cpp)."""
+and the Adam7 scatter on the GPU.  For tests and tools; the job path is `decode` with a PNG io_id (csrc/shim_decode.cpp)."""
 import ctypes as C
 
 import numpy as np

@@ -1,7 +1,7 @@
 """Host mirror of LibPngEncoder (imageflow_core/src/codecs/libpng_encoder.rs:43-72,134-160 over
 c_components/lib/codec_png_wrapper.c:349-430) on the device PNG coder of libimageflow_hip.so (csrc/png_encode.hip): BGRA /
 BGRX frames that stay in HBM -> complete PNG files in HBM -- row filters with libpng's default choice, deflate, the chunks
-and their CRCs.  For tests and tools; the job path is the `libpng` preset of `encode` (csrc/abi_shim.cpp)."""
+and their CRCs.  For tests and tools; the job path is the `libpng` preset of `encode` (csrc/shim_encode.cpp)."""
 import ctypes as C
 
 from .. import _native

@@ -3,7 +3,7 @@ coder of libimageflow_hip.so (csrc/png_quantize.hip): BGRA / BGRX frames that st
 -- colour histogram, palette growth and Lloyd refinement, nearest-entry remap with Floyd-Steinberg dithering, deflate, the
 chunks and their CRCs.  A frame whose quantisation misses minimum_quality is written losslessly by the truecolour coder
 (codecs/libpng_encoder.py), as the reference falls back.  For tests and tools; the job path is the `pngquant` preset of
-`encode` (csrc/abi_shim.cpp)."""
+`encode` (csrc/shim_encode.cpp)."""
 import ctypes as C
 
 import torch

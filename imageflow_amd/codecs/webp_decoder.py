@@ -1,6 +1,6 @@
 """Host mirror of WebPDecoder (imageflow_core/src/codecs/webp.rs:20-248) on the device WebP decoder of libimageflow_hip.so
 (csrc/webp_read.cpp, csrc/webp_decode.hip): lossless WebP files -> 8-bit BGRA frames in HBM -- the VP8L token loop and the
-inverse transforms on the GPU.  For tests and tools; the job path is `decode` with a WebP io_id (csrc/abi_shim.cpp)."""
+inverse transforms on the GPU.  For tests and tools; the job path is `decode` with a WebP io_id (csrc/shim_decode.cpp)."""
 import ctypes as C
 
 import numpy as np

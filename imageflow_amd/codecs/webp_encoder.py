@@ -1,7 +1,7 @@
 """Host mirror of the lossless half of WebPEncoder (imageflow_core/src/codecs/webp.rs:281-345 over libwebp's
 WebPEncodeLosslessBGRA / WebPEncodeLosslessBGR; chosen in codecs/auto.rs:282-319) on the device WebP coder of
 libimageflow_hip.so (csrc/webp_encode.hip): BGRA / BGRX frames that stay in HBM -> complete lossless WebP (VP8L) files in
-HBM.  For tests and tools; the job path is the `webplossless` preset of `encode` (csrc/abi_shim.cpp)."""
+HBM.  For tests and tools; the job path is the `webplossless` preset of `encode` (csrc/shim_encode.cpp)."""
 import ctypes as C
 
 import numpy as np

@@ -2,7 +2,7 @@
 libimageflow_hip.so (csrc/vp8_read.cpp, csrc/vp8_decode.hip): still lossy WebP files (`VP8 `, with or without `ALPH`) -> 8-bit
 BGRA frames in HBM -- bool-decoding on the host, dequantisation, inverse transforms, intra prediction, loop filter, alpha plane
 and conversion on the GPU.  For tests and tools; the job path is `decode` with a WebP io_id once
-Context.set_webp_lossy_decoder(True) is told (csrc/abi_shim.cpp)."""
+Context.set_webp_lossy_decoder(True) is told (csrc/shim_decode.cpp)."""
 import ctypes as C
 
 from .. import _native

@@ -1,7 +1,7 @@
 """Host mirror of the lossy half of WebPEncoder (imageflow_core/src/codecs/webp.rs over libwebp's WebPEncodeBGRA / WebPEncodeBGR,
 EncoderPreset::WebPLossy) on the device lossy WebP coder of libimageflow_hip.so (csrc/vp8_encode.hip): BGRA / BGRX frames that
 stay in HBM -> complete lossy WebP files (`VP8 `, with `VP8X` + `ALPH` for a frame with alpha) in HBM.  For tests and tools; the
-job path is the `webplossy` preset of `encode` behind Context.set_webp_lossy_encoder (csrc/abi_shim.cpp)."""
+job path is the `webplossy` preset of `encode` behind Context.set_webp_lossy_encoder (csrc/shim_encode.cpp)."""
 import ctypes as C
 
 from .. import _native

@@ -1,7 +1,7 @@
 // The RIAPI querystring of `command_string` {kind: "ir4"}: imageflow_riapi's Instructions (src/ir4/parsing.rs), parsed from
 // the text, and their expansion into the nodes and decoder commands the reference builds (Ir4Layout::add_steps, ir4/layout.rs
 // :473-647; Ir4Expand::get_decode_commands, ir4/mod.rs:155-210).  Host text and arithmetic only -- no device, no context:
-// the interpreter (abi_shim.cpp) runs what comes out, and ifhip_shim_expand_command_string hands the same expansion to tests.
+// the interpreter (Job::command_string, shim_nodes.cpp) runs what comes out, and ifhip_shim_expand_command_string hands the same expansion to tests.
 #pragma once
 #include <cstdint>
 #include <string>

@@ -1,4 +1,4 @@
-// shim_errors.hpp -- the error categories of the ABI shim (abi_shim.cpp): imageflow's ErrorCategory with its exit and HTTP maps, and
+// shim_errors.hpp -- the error categories of the ABI shim (abi_shim.cpp, shim_*.cpp): imageflow's ErrorCategory with its exit and HTTP maps, and
 // the exception every refusal of a job travels in.  Standard library only, so that the JSON reader (shim_json.hpp) builds
 // without the GPU runtime.
 #pragma once

@@ -1,5 +1,6 @@
 // shim_job.hpp -- what a job of the ABI shim (abi_shim.cpp) works on: frames in HBM, the limits, the io table, the context,
-// the records of a job's result and the parsed resample hints.  (The interpreter itself, `Job`, is still defined in abi_shim.cpp.)
+// the records of a job's result, the parsed resample hints, and the interpreter itself: `Job`, declared here with its members
+// in shim_interp.cpp, shim_decode.cpp, shim_nodes.cpp and shim_encode.cpp.
 #pragma once
 #include <atomic>
 #include <chrono>
@@ -172,11 +173,13 @@ struct imageflow_context {
     void set_error(int cat, const std::string& m) { if (err_cat == ifshim::kOk) { err_cat = cat; err_msg = m; } }   // first error sticks
 };
 
+namespace ifhip { struct WebpParsed; }           // webp_read.hpp: the walk of a WebP input (Job::walk_webp)
+
 namespace ifshim {
 
 // ---- the job interpreter ---------------------------------------------------------------------------------------
 struct EncodeRecord { int32_t io_id; uint32_t w, h; const char* mime; const char* ext; };
-struct DecodeRecord { int32_t io_id; uint32_t w, h; const char* mime; const char* ext; };
+using DecodeRecord = EncodeRecord;
 struct NodePerf { const char* name; uint64_t wall_ns; float gpu_ms; hipEvent_t e0, e1; };   // s::NodePerf (imageflow_types/src/lib.rs:1999-2002); e0/e1: read at the job's end
 struct ResampleHints {                                                        // s::ResampleHints (lib.rs:925-933), parsed
     bool has_sharpen = false;
@@ -186,6 +189,150 @@ struct ResampleHints {                                                        //
     uint32_t bg = 0;
     enum When { kDefault, kSizeDiffers, kSizeDiffersOrSharpen, kAlways } resample_when = kDefault;
     enum SWhen { kSAlways, kSDown, kSUp, kSSizeDiffers } sharpen_when = kSAlways;
+};
+
+// One job of a context: the state every stage shares, and the members that cross the files they are defined in --
+// shim_interp.cpp (the core, run_node, the graph walk, the animation loop), shim_decode.cpp, shim_nodes.cpp, shim_encode.cpp.
+struct Job {
+    imageflow_context* c;
+    std::vector<EncodeRecord> encodes;
+    std::vector<DecodeRecord> decodes;
+    std::vector<NodePerf> perf;
+    Security sec;
+    std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
+    bool lazy_decode = false;                                        // the decode node being run has exactly one consumer
+    struct GifSource { bool seen; int repeat; uint32_t delay; bool user_input; } gif_source{false, -1, 0u, false};   // of the first GIF the job decoded
+
+    // one executed primitive: wall clock as the reference's per-node cost (execution_engine.rs:506-538) plus the time
+    // the device spent on it (hipEvents on the stream every node of this interpreter launches on)
+    // A node's performance record: wall time on the host and, between two hipEvents on the job's stream, the device's time.
+    // The node does NOT wait for the device when it ends -- its launches stay in flight while the host prepares the next
+    // node's; the events are read once, at the job's end (settle_perf).  (Until round 5 every node ended in
+    // hipEventSynchronize: 4 host/device round trips per job and, under the runtime's default spinning wait, one busy host
+    // core per job in flight -- profiles/r5_abi_jobs_host_cpu.txt.)
+    struct Timed {
+        Job* j; const char* name; std::chrono::steady_clock::time_point t0; hipEvent_t e0 = nullptr, e1 = nullptr;
+        Timed(Job* job, const char* n);
+        ~Timed();
+    };
+
+    // ---- animated GIFs (EXTENSION ifhip_shim_context_set_gif_animation) ---------------------------------------------------------------
+    // The reference re-runs the job for every frame of an animated source (GifDecoder::has_more_frames -> ctx.set_more_frames,
+    // codecs/gif/mod.rs:207-305, flow/nodes/codecs_and_pointer.rs:168) and GifEncoder::write_frame appends frame frame_ix to one
+    // file (:429-521).  Here: the source's screens are decoded ONCE (ifhip::gif_decode_all_parsed_device: one replay for all of
+    // them), run_framewise runs once per frame with the animated decode node yielding screen k, every "gif" encode node
+    // collects its frame k into one device block, and behind the last frame the block is coded in ONE call
+    // (ifhip_gif_encode_animation_device) -- an animation's frames are a ready-made batch.  Every other encoder takes frame 0.
+    struct AnimSource {
+        uint8_t* d = nullptr;                    // n screens, h * stride bytes each
+        uint32_t w = 0, h = 0, stride = 0;
+        ~AnimSource() { job_free(d); }
+    };
+    struct AnimCollect {
+        uint8_t* d = nullptr;                    // n frames, h * stride bytes each
+        ifhip_gif_enc_stage* stage = nullptr;
+        uint32_t w = 0, h = 0, stride = 0;
+        bool alpha = false;
+        ~AnimCollect() { job_free(d); if (stage) { quiesce(); ifhip_gif_enc_stage_destroy(stage); } }
+    };
+    struct Anim {
+        bool active = false, in_decode_node = false;
+        uint32_t n = 0, k = 0;
+        int repeat = 0;
+        uint64_t pixels = 0;                     // decoded screens + collected frames so far (check_total_pixels)
+        std::vector<uint32_t> delays;
+        std::vector<uint8_t> user_input;
+        std::map<int32_t, std::unique_ptr<AnimSource>> sources;
+        std::map<int32_t, std::unique_ptr<AnimCollect>> collects;
+    } anim;
+
+    // shim_interp.cpp
+    void poll_cancel();
+    void settle_perf(bool read);
+    ~Job();
+    FramePtr new_frame(uint32_t w, uint32_t h, bool alpha, uint32_t fill_color32 = 0, bool zero = true, int matte_canvas = -1);
+    uint8_t* dev(const FramePtr& f);
+    FramePtr clone(const FramePtr& in, bool clone_node = false);
+    Io& input(int32_t id);
+    Io& output(int32_t id);
+    FramePtr run_node(const std::string& name, const JVal& p, FramePtr in, FramePtr canvas, bool in_shared);
+    static void node_of(const JVal& n, std::string* name, const JVal** params);
+    static bool mutates_input(const std::string& nm);
+    void add_animation_pixels(uint64_t pixels_per_frame);
+    uint32_t animated_frames_of(const JVal& params);
+    std::vector<std::pair<int32_t, uint32_t>> animation_plan(const JVal& fw);
+    void decode_animation_source(int32_t io_id, bool first);
+    FramePtr animated_screen(int32_t io_id);
+    void run_job(const JVal& fw);
+    void run_framewise(const JVal& fw);
+
+    // shim_decode.cpp
+    static bool is_png(const Io& in);
+    static bool is_webp(const Io& in);
+    static bool is_gif(const Io& in);
+    static void walk_webp(const Io& in, ifhip::WebpParsed* P, bool lossy_decoder);
+    static int exif_flag(const Io& in);
+    void image_size(int32_t io_id, uint32_t* w, uint32_t* h, bool rotated = false);
+    bool color_plan_for(int32_t io_id, const Io& in, const char* what, const char* reference_line, const uint8_t* icc, size_t icc_len,
+                        const uint32_t* gama_chrm, ifhip_color_plan* plan);
+    void convert_to_srgb(const FramePtr& f, const ifhip_color_plan& plan);
+    FramePtr decode_png(int32_t io_id, Io& in);
+    FramePtr decode_webp(int32_t io_id, Io& in);
+    FramePtr decode_gif(int32_t io_id, Io& in);
+    FramePtr decode(int32_t io_id, uint32_t hint_w, uint32_t hint_h, bool luma_spatial, bool luma_srgb);
+    // one file through a decoder's device part on the job's stream: queue(d_status) launches it; -> the file's status word, waited for
+    template <typename Queue>
+    uint32_t decoded_status(const char* label, Queue queue) {
+        uint32_t* d_status = nullptr;
+        hip_check(job_malloc(reinterpret_cast<void**>(&d_status), 16), "hipMalloc(status)");
+        struct Guard { void* p; ~Guard() { job_free(p); } } guard{d_status};
+        poll_cancel();
+        check(queue(d_status));
+        uint32_t status = 0;
+        hip_check(hipMemcpyAsync(&status, d_status, 4, hipMemcpyDeviceToHost, t_job_stream), "download(status)");
+        hip_check(static_cast<hipError_t>(ifhip::wait_stream(t_job_stream)), label);
+        return status;
+    }
+
+    // shim_nodes.cpp
+    static ResampleHints parse_hints(const JVal* hints, const char* node);
+    void draw_image_exact(const FramePtr& canvas, const FramePtr& in, uint32_t x, uint32_t y, uint32_t w, uint32_t h, bool compose, const ResampleHints& hi);
+    FramePtr resample(const FramePtr& in, uint32_t w, uint32_t h, const JVal* hints_json);
+    FramePtr constrain(const FramePtr& in, const JVal& p);
+    FramePtr crop_frame(const FramePtr& in, uint32_t x1, uint32_t y1, uint32_t x2, uint32_t y2);
+    FramePtr crop_whitespace(const FramePtr& in, uint32_t threshold, float percent_padding, bool in_shared);
+    FramePtr round_corners(const FramePtr& in, int mode, const float radii[4], uint32_t color);
+    FramePtr white_balance(const FramePtr& in, float threshold);
+    FramePtr expand_frame(const FramePtr& in, uint32_t l, uint32_t t2, uint32_t r, uint32_t b, uint32_t color, bool color_is_keyword_transparent);
+    FramePtr command_string(const JVal& p, FramePtr in, bool in_shared = false);
+    FramePtr copy_into_canvas(const FramePtr& in, const FramePtr& canvas, uint32_t fx, uint32_t fy, uint32_t w, uint32_t h, uint32_t x, uint32_t y);
+    FramePtr transposed(const FramePtr& in);
+    FramePtr flip(const FramePtr& in, bool vertical);
+    FramePtr apply_orientation(const FramePtr& in, int64_t flag);
+    FramePtr decode_oriented(int32_t io_id, uint32_t hint_w, uint32_t hint_h, bool luma_spatial, bool luma_srgb);
+    FramePtr color_matrix(const FramePtr& in, const float m[25]);
+    FramePtr color_filter(const FramePtr& in, const JVal& p);
+    FramePtr watermark(const FramePtr& canvas, const JVal& p);
+    FramePtr node_decode(const JVal& p);
+    FramePtr node_round_image_corners(const JVal& p, const FramePtr& in);
+    FramePtr node_crop_whitespace(const JVal& p, const FramePtr& in, bool in_shared);
+    FramePtr node_fill_rect(const std::string& name, const JVal& p, const FramePtr& in);
+    FramePtr node_region(const std::string& name, const JVal& p, const FramePtr& in, bool in_shared);
+    FramePtr node_color_matrix_srgb(const JVal& p, const FramePtr& in);
+
+    // shim_encode.cpp
+    void write_png(const FramePtr& f, int color_type, int level, Io& o, int32_t io_id);
+    void encode(FramePtr f, int32_t io_id, const JVal* preset, bool shared);
+    void encode_jpeg(FramePtr f, Io& o, int32_t io_id, const JVal* preset, const JVal* classic, bool moz, bool shared);
+    void encode_png(FramePtr f, Io& o, int32_t io_id, const JVal* png, bool shared);
+    void encode_pngquant(const FramePtr& f, Io& o, int32_t io_id, const JVal* pq);
+    void encode_webp_lossless(const FramePtr& f, Io& o, int32_t io_id);
+    void encode_gif(const FramePtr& f, Io& o, int32_t io_id);
+    void encode_webp_lossy(const FramePtr& f, Io& o, int32_t io_id, const JVal* preset);
+    void encode_raw(const FramePtr& f, Io& o, int32_t io_id);
+    void check_encode_node(const JVal& n);
+    void collect_frame(const FramePtr& f, int32_t io_id);
+    void write_animations();
 };
 
 }  // namespace ifshim

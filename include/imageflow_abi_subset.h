@@ -17,7 +17,8 @@
  * byte-identical to libjpeg-turbo's file for the same pixels at 4:2:0); every other preset writes the raw BGRA container
  * EXTENSION (this library has no deflate / GIF / WebP coder): 8 bytes "IFBGRA1\0", u32le w, h, stride,
  * alpha_meaningful, then h rows of `stride` bytes.
- * Implementation: imageflow_amd/csrc/abi_shim.cpp.
+ * Implementation: imageflow_amd/csrc/abi_shim.cpp (these entry points) and, for the jobs, shim_job.hpp with
+ * shim_interp.cpp, shim_decode.cpp, shim_nodes.cpp and shim_encode.cpp beside it.
  */
 #ifndef IMAGEFLOW_ABI_SUBSET_H
 #define IMAGEFLOW_ABI_SUBSET_H

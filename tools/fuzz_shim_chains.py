@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Differential fuzz of the job interpreter behind the libimageflow C ABI (csrc/abi_shim.cpp) against the Python node mirrors
+"""Differential fuzz of the job interpreter behind the libimageflow C ABI (csrc/shim_interp.cpp and the stages beside it) against the Python node mirrors
 (imageflow_amd/flow/nodes/*.py) on the GPU (round 6).
 
 Two independent statements of the reference's node semantics exist in this repository: the C++ interpreter a job's JSON
