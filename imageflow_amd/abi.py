@@ -84,6 +84,13 @@ def _bind():
     L.ifhip_shim_context_set_gif_animation.restype = C.c_bool
     L.ifhip_shim_context_set_device_jpeg_options.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_device_jpeg_options.restype = C.c_bool
+    L.ifhip_shim_context_set_encoder_selection.argtypes = [vp, C.c_int]
+    L.ifhip_shim_context_set_encoder_selection.restype = C.c_bool
+    L.ifhip_shim_querystring_encoder_preset.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t, szp]
+    L.ifhip_shim_querystring_encoder_preset.restype = C.c_int
+    L.ifhip_shim_resolve_encoder_preset.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_uint32, C.c_int, C.c_uint32, C.c_uint32, C.c_char_p,
+                                                    C.c_size_t, szp]
+    L.ifhip_shim_resolve_encoder_preset.restype = C.c_int
     L.imageflow_context_memory_allocate.argtypes = [vp, C.c_size_t, C.c_char_p, C.c_int32]
     L.imageflow_context_memory_allocate.restype = vp
     L.imageflow_context_memory_free.argtypes = [vp, vp, C.c_char_p, C.c_int32]
@@ -103,6 +110,46 @@ def unpack_raw_bgra(buf):
     assert buf[:8] == RAW_MAGIC, buf[:8]
     w, h, stride, alpha = struct.unpack("<IIII", buf[8:24])
     return np.frombuffer(buf, np.uint8, h * stride, 24).reshape(h, stride), w, h, bool(alpha)
+
+
+SELECT_REFUSED, SELECT_INVALID, SELECT_INVALID_JSON = 2, 3, 4        # include/imageflow_hip_encoder_select.h IFHIP_SELECT_*
+SOURCE_KINDS = {None: 0, "raw": 0, "jpeg": 1, "png": 2, "gif": 3, "webp": 4}   # IFHIP_SELECT_SOURCE_*
+
+
+class EncoderSelectError(ValueError):
+    """A refusal of the two host-only entry points below: .status is IFHIP_SELECT_REFUSED (ActionNotSupported), _INVALID
+    (InvalidArgument) or _INVALID_JSON (InvalidJson); the message is the library's."""
+
+    def __init__(self, status, message):
+        self.status = status
+        super().__init__(message)
+
+
+def _select_call(f, *args):
+    L = _bind()
+    needed = C.c_size_t()
+    buf = C.create_string_buffer(4096)
+    rc = f(*args, buf, len(buf), C.byref(needed))
+    if rc == 0 and needed.value > len(buf):
+        buf = C.create_string_buffer(needed.value)
+        rc = f(*args, buf, len(buf), C.byref(needed))
+    if rc != 0:
+        raise EncoderSelectError(rc, (L.ifhip_last_error_message() or b"").decode("utf-8", "replace"))
+    return json.loads(buf.value.decode())
+
+
+def querystring_encoder_preset(value):
+    """The EncoderPreset ({"auto": ..} or {"format": ..}) the reference's querystring layer makes of a querystring's output
+    keys (ifhip_shim_querystring_encoder_preset; host only)."""
+    return _select_call(_bind().ifhip_shim_querystring_encoder_preset, value.encode())
+
+
+def resolve_encoder_preset(preset, source=None, source_lossless=False, source_frames=1, alpha_meaningful=False, w=1, h=1):
+    """What an `auto` / `format` preset comes to for a source ("jpeg" | "png" | "gif" | "webp" | None) and a final frame:
+    {"format", "coder", "params", "matte"} (ifhip_shim_resolve_encoder_preset; host only)."""
+    body = preset if isinstance(preset, (bytes, bytearray)) else json.dumps(preset).encode()
+    return _select_call(_bind().ifhip_shim_resolve_encoder_preset, body, len(body), SOURCE_KINDS[source], int(bool(source_lossless)), source_frames,
+                        int(bool(alpha_meaningful)), w, h)
 
 
 class Context:
@@ -196,13 +243,22 @@ class Context:
     def set_gif_animation(self, on):
         """EXTENSION, off by default: with the GIF encoder on as well, a job whose `decode` reads a GIF of more than one frame
         (no select_frame told) and whose "gif" `encode` lies downstream runs once per frame and writes ONE animated GIF;
-        every other encoder of the job takes frame 0.  Every other job is what it is with the switch off."""
+        every other encoder of the job takes frame 0.  Every other job is what it is with the switch off.  With encoder
+        selection on, an `auto` / `format` encode that comes to GIF counts as a "gif" encode, GIF encoder switch or not."""
         return self.L.ifhip_shim_context_set_gif_animation(self.p, 1 if on else 0)
 
     def set_device_jpeg_options(self, on):
         """EXTENSION, off by default: entropy-code the libjpeg_turbo preset's progressive / optimize_huffman_coding files on the
         device instead of by the host writer (the same bytes; only the file leaves the device)."""
         return self.L.ifhip_shim_context_set_device_jpeg_options(self.p, 1 if on else 0)
+
+    def set_encoder_selection(self, on):
+        """EXTENSION, off by default: `encode` with the preset {"auto": ..} or {"format": ..} is resolved as the reference
+        resolves it (format, coder and quality from its tables, against the job's first input and the final frame) and written
+        as a real file -- JPEG, PNG, palette PNG, WebP or GIF -- instead of the raw BGRA container; `command_string` reads the
+        output keys of its querystring (format, qp, qp.dpr, lossless, accept.*, quality, jpeg.*, webp.*, png.*) instead of
+        refusing them, and a string without one keeps the source's format."""
+        return self.L.ifhip_shim_context_set_encoder_selection(self.p, 1 if on else 0)
 
     @property
     def device(self):

@@ -333,6 +333,14 @@ bool ifhip_shim_context_set_color_management(struct imageflow_context* c, int on
 }
 // EXTENSION: the libjpeg_turbo preset's progressive / optimize_huffman_coding files are entropy-coded on the device
 // (ifhip_jpeg_encode_flags_batch_device) instead of by the host writer; off by default.  The files are the same bytes.
+// EXTENSION: the presets `auto` and `format` of `encode`, and the output keys of a command_string's querystring, come to the
+// coder the reference would pick (see Job::encode_selected, csrc/encoder_select.cpp); off by default, where both presets stay
+// the raw-container tap and the keys stay refused.
+bool ifhip_shim_context_set_encoder_selection(struct imageflow_context* c, int on) {
+    CTX_OR_ABORT(c);
+    c->encoder_selection.store(on != 0, std::memory_order_relaxed);
+    return true;
+}
 bool ifhip_shim_context_set_device_jpeg_options(struct imageflow_context* c, int on) {
     CTX_OR_ABORT(c);
     c->device_jpeg_options.store(on != 0, std::memory_order_relaxed);

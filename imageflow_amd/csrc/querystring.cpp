@@ -224,8 +224,24 @@ const char* const kKeys[] = {"width", "w", "height", "h", "maxwidth", "maxheight
                              "up.filter", "down.filter", "up.colorspace", "down.colorspace", "watermark_red_dot", "ignoreicc",
                              "decoder.min_precise_scaling_ratio", "autorotate", "quality", "jpeg.quality", "format", "s.roundcorners",
                              "a.balancewhite", "trim.threshold", "trim.percentpadding"};
+// the output keys read only under `encoder_selection` (parsing.rs:589-626); `quality`, `jpeg.quality` and `format` are in kKeys
+const char* const kOutputKeys[] = {"thumbnail", "qp", "qp.dpr", "qp.dppx", "lossless", "accept.webp", "accept.avif", "accept.jxl", "accept.color_profiles",
+                                   "jpeg.progressive", "jpeg.turbo", "jpeg.li", "webp.quality", "webp.lossless", "png.quality", "png.min_quality",
+                                   "png.quantization_speed", "png.libpng", "png.max_deflate", "png.lossless"};
+bool parse_u8(const std::string& s, uint8_t* out) {      // `str::parse::<u8>`: an optional '+', digits, at most 255
+    size_t i = (!s.empty() && s[0] == '+') ? 1 : 0;
+    if (i == s.size()) return false;
+    int v = 0;
+    for (; i < s.size(); ++i) {
+        if (!std::isdigit(static_cast<unsigned char>(s[i]))) return false;
+        v = v * 10 + (s[i] - '0');
+        if (v > 255) return false;
+    }
+    *out = static_cast<uint8_t>(v);
+    return true;
+}
 
-void parse(const std::string& q, Ir4Instructions* out) {
+void parse(const std::string& q, Ir4Instructions* out, bool encoder_selection) {
     Ir4Instructions i;
     // Url::from_str would end the query at a '#': what follows is the fragment, and every key in it would be dropped in silence
     if (q.find('#') != std::string::npos) throw QsErr{kQsRefused, "ActionNotSupported: querystring holds a raw '#' (a fragment starts there); write %23"};
@@ -241,6 +257,9 @@ void parse(const std::string& q, Ir4Instructions* out) {
         std::string v = form_decode(kv.substr(eq + 1));
         bool known = false;
         for (const char* name : kKeys) known = known || k == name;
+        bool output_key = encoder_selection && (k == "quality" || k == "jpeg.quality" || k == "format");
+        if (encoder_selection) for (const char* name : kOutputKeys) output_key = output_key || k == name;
+        if (output_key) { m[k] = trim_ws(v); continue; }                                   // read below, as the reference reads them
         if (!known) {
             char buf[160];
             std::snprintf(buf, sizeof buf, "ActionNotSupported: querystring key '%.100s'", k.c_str());
@@ -413,6 +432,71 @@ void parse(const std::string& q, Ir4Instructions* out) {
     f32_of("decoder.min_precise_scaling_ratio", &i.min_precise_scaling_ratio);
     if (const std::string* v = val("bgcolor")) { uint32_t col = 0; if (parse_color(*v, &col)) i.bgcolor.set(col); }
     bool_of("watermark_red_dot", &i.watermark_red_dot);
+    if (encoder_selection) {
+        // Format-specific tuning and format selection (:589-626)
+        Ir4Output& o = i.out;
+        o.parsed = true;
+        auto i32_of = [&](const char* key, Opt<int32_t>* t) { int32_t n = 0; if (const std::string* v = val(key)) if (parse_i32(*v, &n)) t->set(n); };
+        auto u8_of = [&](const char* key, Opt<uint8_t>* t) { uint8_t n = 0; if (const std::string* v = val(key)) if (parse_u8(*v, &n)) t->set(n); };
+        auto bool_keep_of = [&](const char* key, int* t) {                                  // parse_bool_keep (:848-856)
+            bool b = false;
+            if (const std::string* v = val(key)) {
+                if (parse_bool(*v, &b)) *t = b ? Ir4Output::kBkTrue : Ir4Output::kBkFalse;
+                else if (ieq(*v, "keep") || ieq(*v, "preserve")) *t = Ir4Output::kBkKeep;
+            }
+        };
+        i32_of("jpeg.quality", &o.jpeg_quality);
+        bool_of("jpeg.progressive", &o.jpeg_progressive);
+        bool_of("jpeg.turbo", &o.jpeg_turbo);
+        bool_of("jpeg.li", &o.jpeg_li);
+        f32_of("webp.quality", &o.webp_quality);
+        bool_keep_of("webp.lossless", &o.webp_lossless);
+        bool_keep_of("png.lossless", &o.png_lossless);
+        u8_of("png.min_quality", &o.png_min_quality);
+        u8_of("png.quality", &o.png_quality);
+        u8_of("png.quantization_speed", &o.png_quantization_speed);
+        bool_of("png.libpng", &o.png_libpng);
+        bool_of("png.max_deflate", &o.png_max_deflate);
+        bool_of("accept.jxl", &o.accept_jxl);
+        bool_of("accept.webp", &o.accept_webp);
+        bool_of("accept.avif", &o.accept_avif);
+        bool_of("accept.color_profiles", &o.accept_color_profiles);
+        for (const char* key : {"format", "thumbnail"}) {                                  // OutputFormatStrings (:50-66, 1134-1154): 15 spellings, any case
+            if (o.format != Ir4Output::kFormatUnset) break;
+            const std::string* v = val(key);
+            if (!v) continue;
+            static const struct { const char* name; int format; } kNames[] = {
+                {"jpg", Ir4Output::kJpeg}, {"jpe", Ir4Output::kJpeg}, {"jif", Ir4Output::kJpeg}, {"jfif", Ir4Output::kJpeg}, {"jfi", Ir4Output::kJpeg},
+                {"exif", Ir4Output::kJpeg}, {"jpeg", Ir4Output::kJpeg}, {"png", Ir4Output::kPng}, {"gif", Ir4Output::kGif}, {"webp", Ir4Output::kWebp},
+                {"avif", Ir4Output::kAvif}, {"jxl", Ir4Output::kJxl}, {"jpegxl", Ir4Output::kJxl}, {"auto", Ir4Output::kAuto}, {"keep", Ir4Output::kKeep}};
+            for (const auto& n : kNames) if (ieq(*v, n.name)) { o.format = n.format; break; }
+        }
+        bool_keep_of("lossless", &o.lossless);
+        i32_of("quality", &o.quality);
+        if (const std::string* v = val("qp")) {                                            // parse_quality_profile (:910-925), QualityProfile::parse
+            static const struct { const char* name; int qp; } kNames[] = {
+                {"lowest", Ir4Output::kLowest}, {"low", Ir4Output::kLow}, {"medium-low", Ir4Output::kMediumLow}, {"mediumlow", Ir4Output::kMediumLow},
+                {"medium", Ir4Output::kMedium}, {"good", Ir4Output::kGood}, {"medium-high", Ir4Output::kGood}, {"mediumhigh", Ir4Output::kGood},
+                {"high", Ir4Output::kHigh}, {"highest", Ir4Output::kHighest}, {"lossless", Ir4Output::kLossless}};
+            float f = 0.f;
+            if (ieq(*v, "quality")) { if (o.quality.some) { o.qp = Ir4Output::kPercent; o.qp_percent = static_cast<float>(o.quality.v); } }
+            else {
+                for (const auto& n : kNames) if (o.qp == Ir4Output::kQpUnset && ieq(*v, n.name)) o.qp = n.qp;
+                if (o.qp == Ir4Output::kQpUnset && parse_f32(*v, &f)) { o.qp = Ir4Output::kPercent; o.qp_percent = std::fmin(100.f, std::fmax(0.f, f)); }   // (a NaN is 0)
+            }
+        }
+        for (const char* key : {"qp.dpr", "qp.dppx"}) {                                    // parse_qp_dpr (:881-896): no finiteness check
+            if (o.qp_dpr.some) break;
+            const std::string* v = val(key);
+            if (!v) continue;
+            if (ieq(*v, "dpr") || ieq(*v, "dppx") || ieq(*v, "zoom")) { if (i.zoom.some) o.qp_dpr.set(i.zoom.v); continue; }
+            std::string t = *v;
+            while (!t.empty() && t.back() == 'x') t.pop_back();
+            float f = 0.f;
+            if (parse_f32(t, &f)) o.qp_dpr.set(f);
+        }
+        i.format_jpeg = i.jpeg_out = o.format == Ir4Output::kJpeg;                         // the white background of format=jpg (layout.rs:492-503)
+    }
     // the reference parses `autorotate` and never reads it: its decoder always applies the EXIF orientation, as this one does
     if (i.autorotate.some && !i.autorotate.v)
         throw QsErr{kQsRefused, "ActionNotSupported: querystring autorotate=false (the decoder always applies the EXIF orientation, as the reference's does)"};
@@ -617,9 +701,9 @@ void expand(const Ir4Instructions& i, int32_t sw, int32_t sh, int32_t rw, int32_
 
 }  // namespace
 
-int parse_querystring(const std::string& text, Ir4Instructions* out, std::string* error) {
+int parse_querystring(const std::string& text, Ir4Instructions* out, std::string* error, bool encoder_selection) {
     try {
-        parse(text, out);
+        parse(text, out, encoder_selection);
         return kQsOk;
     } catch (const QsErr& e) {
         if (error) *error = e.text;

@@ -12,7 +12,25 @@ namespace ifhip {
 
 enum QsStatus : int { kQsOk = 0, kQsLayoutError = 1, kQsRefused = 2, kQsInvalid = 3 };
 
+// The encoder half of Instructions as the reference reads it (ir4/parsing.rs:589-626), filled only where the parser is told
+// that the caller selects its encoder as the reference does (parse_querystring's `encoder_selection`).
+struct Ir4Output {
+    enum Format : int { kFormatUnset = -1, kKeep, kJpeg, kPng, kGif, kWebp, kAvif, kJxl, kAuto };   // OutputFormat (:1346-1355)
+    enum BoolKeep : int { kBkUnset = -1, kBkKeep, kBkTrue, kBkFalse };
+    enum Qp : int { kQpUnset = -1, kLowest, kLow, kMediumLow, kMedium, kGood, kHigh, kHighest, kLossless, kPercent };
+    bool parsed = false;
+    int format = kFormatUnset;                         // `format`, else `thumbnail`
+    Opt<int32_t> quality, jpeg_quality;
+    Opt<bool> jpeg_progressive, jpeg_turbo, jpeg_li, png_libpng, png_max_deflate, accept_webp, accept_avif, accept_jxl, accept_color_profiles;
+    Opt<float> webp_quality, qp_dpr;
+    Opt<uint8_t> png_quality, png_min_quality, png_quantization_speed;
+    int lossless = kBkUnset, webp_lossless = kBkUnset, png_lossless = kBkUnset;
+    int qp = kQpUnset;
+    float qp_percent = 0.f;
+};
+
 struct Ir4Instructions : Ir4LayoutParams {             // ir4/parsing.rs:1236-1337, the keys this library honours
+    Ir4Output out;
     Opt<int32_t> rotate;
     bool has_flip = false, flip_h = false, flip_v = false, has_sflip = false, sflip_h = false, sflip_v = false;
     Opt<uint32_t> bgcolor;                             // Color32: 0xAARRGGBB
@@ -36,7 +54,10 @@ struct Ir4Instructions : Ir4LayoutParams {             // ir4/parsing.rs:1236-13
 // The text of a querystring -> Instructions (Instructions::delete_from_map, ir4/parsing.rs:481-635).  kQsRefused: a key this
 // library does not honour (the reference would warn and go on; a drop-in that cannot warn refuses); kQsInvalid: a filter name
 // or a size no value of the reference's could mean.  *error: "ActionNotSupported: ..." / "InvalidNodeParams: ...".
-int parse_querystring(const std::string& text, Ir4Instructions* out, std::string* error);
+// encoder_selection: the output keys (`format` / `thumbnail` in all their spellings, `qp`, `qp.dpr` / `qp.dppx`, `lossless`,
+// `accept.*`, `quality`, `jpeg.*`, `webp.*`, `png.*`) are read with the reference's parsers (:589-626, 848-925, 1346-1385) into
+// out->out instead of refused; false: the string is read as it always was.
+int parse_querystring(const std::string& text, Ir4Instructions* out, std::string* error, bool encoder_selection = false);
 
 // Instructions + the frame they meet -> {"decoder_commands": [...], "steps": [...], "canvas": [w, h]}: the nodes in the JSON form
 // v1/execute takes, without decode and encode.  watermarks: the JSON text of command_string.watermarks (an array), or null.

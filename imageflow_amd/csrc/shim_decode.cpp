@@ -214,6 +214,31 @@ void Job::walk_webp(const Io& in, ifhip::WebpParsed* P, bool lossy_decoder) {
     if (rc == IFHIP_METHOD_NOT_IMPLEMENTED) raise(kImageTypeNotSupported, "%s", ifhip_last_error_message());
     check(rc);
 }
+// What get_unscaled_unrotated_image_info tells build_auto_encoder_details about an input (codecs/auto.rs:1059-1079): the
+// format, `lossless` and `multiple_frames`.  A PNG is lossless unless it has a palette (libpng_decoder.rs:49), a WebP where it
+// has a VP8L image chunk, a GIF animates with more than one frame; the raw BGRA container (and anything unknown) is no source.
+ifsel::Source Job::source_facts(int32_t io_id) {
+    ifsel::Source s;
+    auto it = c->io.find(io_id);
+    if (it == c->io.end() || it->second.is_output) return s;
+    const Io& in = it->second;
+    if (in.in_len >= kRawHeader && std::memcmp(in.in, kRawMagic, 8) == 0) return s;
+    if (is_png(in)) {
+        s.kind = ifsel::kSourcePng;
+        s.lossless = !(in.in_len > 25 && in.in[25] == 3);                      // IHDR's colour type
+    } else if (is_gif(in)) {
+        s.kind = ifsel::kSourceGif;
+        uint32_t n = 0;
+        s.animated = ifhip_gif_frame_count(in.in, in.in_len, &n, nullptr, nullptr, 0) == IFHIP_OK && n > 1u;
+    } else if (is_webp(in)) {
+        s.kind = ifsel::kSourceWebp;
+        ifhip::WebpParsed P;
+        s.lossless = ifhip::parse_webp(in.in, in.in_len, &P) == IFHIP_OK && P.lossless;
+    } else if (in.in_len >= 2 && in.in[0] == 0xFF && in.in[1] == 0xD8) {
+        s.kind = ifsel::kSourceJpeg;
+    }
+    return s;
+}
 // MzDec::get_exif_rotation_flag (mozjpeg_decoder.rs:290-292): the EXIF orientation tag of a JPEG input, -1 = none
 // (a PNG has none: LibPngDecoder::get_exif_rotation_flag is None, libpng_decoder.rs:54-56)
 int Job::exif_flag(const Io& in) {

@@ -130,16 +130,22 @@ void Job::write_png(const FramePtr& f, int color_type, int level, Io& o, int32_t
 // EncoderPreset::WebPLossless is written as a real lossless WebP by the device coder (csrc/webp_encode.hip).
 // EXTENSION: every other preset writes the raw BGRA container (lodepng / lossy WebP coders are out of scope) -- "gif" too,
 // unless the context's GIF encoder is switched on (ifhip_shim_context_set_gif_encoder): then it is a GIF89a file of the device coder.
+// EXTENSION (ifhip_shim_context_set_encoder_selection): EncoderPreset::Auto and ::Format are resolved to one of those coders
+// (encode_selected, below); without the switch they are among the presets that write the raw container.
 // `shared`: other consumers still read this frame -- the matte is then applied to a private copy.
 void Job::encode(FramePtr f, int32_t io_id, const JVal* preset, bool shared) {
     Timed t(this, "primitive_encoder");
     Io& o = output(io_id);
     if (o.out_state == OutState::Taken) raise(kArgumentInvalid, "InvalidArgument: Output buffer for io_id %d has already been taken", io_id);
     poll_cancel();
+    const bool selection = c->encoder_selection.load(std::memory_order_relaxed) && ifsel::names_selection(preset);
     if (anim.active) {                                                           // every frame to the "gif" nodes, frame 0 to every other encoder
-        if (preset && preset->t == JVal::Str && preset->s == "gif") { collect_frame(f, io_id); return; }
+        // (an `auto` / `format` preset that comes to GIF is a "gif" node: Job::animation_plan decided it before the first frame)
+        const bool named_gif = preset && preset->t == JVal::Str && preset->s == "gif" && c->gif_encoder.load(std::memory_order_relaxed);
+        if (named_gif || (selection && anim.selected_gif.count(io_id))) { collect_frame(f, io_id); return; }
         if (anim.k > 0) return;
     }
+    if (selection) return encode_selected(f, o, io_id, preset, shared);
     const int coder = encode_coder(preset);
     // EncoderPreset::Mozjpeg {quality, progressive, matte} -> MozjpegEncoder::create (codecs/mozjpeg.rs:37-59): mozjpeg's own
     // defaults.  Of those the trellis quantisation is built (csrc/jpeg_trellis.hip, this project's restatement of
@@ -345,9 +351,46 @@ void Job::encode_raw(const FramePtr& f, Io& o, int32_t io_id) {
     encodes.push_back({io_id, f->w, f->h, "application/x-imageflow-bgra", "ifbgra"});
 }
 
+// EXTENSION (ifhip_shim_context_set_encoder_selection): EncoderPreset::Auto / ::Format -> create_encoder_auto (codecs/auto.rs:
+// 368-566): the preset is resolved against the job's source (Job::find_source) and this frame (csrc/encoder_select.cpp), and the
+// coder that comes out writes the file with the parameters of its named preset.  A resolved preset never writes the raw
+// container, and it does not ask for the GIF or lossy WebP switches.  `jpegli` is the mozjpeg route; webp_m, jpeg_xyb and
+// color_profiles have nothing to act on here (DESIGN "Encoder selection").
+void Job::encode_selected(FramePtr f, Io& o, int32_t io_id, const JVal* preset, bool shared) {
+    const ifsel::Resolved r = ifsel::resolve(ifsel::read_preset(*preset), has_source_io ? source_facts(source_io) : ifsel::Source(), f->alpha, f->w, f->h);
+    const std::string json = ifsel::resolved_json(r);
+    const JVal resolved = parse_json(reinterpret_cast<const uint8_t*>(json.data()), json.size());
+    const JVal* params = resolved.get("params");
+    auto named = [&](const char* name) { JVal v; v.t = JVal::Obj; v.o.emplace_back(name, *params); return v; };
+    switch (r.coder) {
+    case ifsel::kCoderMozjpeg: { const JVal p = named("mozjpeg"); return encode_jpeg(f, o, io_id, &p, &p.o[0].second, true, shared); }
+    case ifsel::kCoderLibjpegTurbo: { const JVal p = named("libjpeg_turbo"); return encode_jpeg(f, o, io_id, &p, &p.o[0].second, false, shared); }
+    case ifsel::kCoderLibpng: return encode_png(f, o, io_id, params, shared);
+    case ifsel::kCoderLodepng:                                                  // lode.rs:51-53, 98-104: the matte, then BGRA or BGRX by the frame's alpha
+        f = matted(f, r, shared);
+        return write_png(f, f->alpha ? IFHIP_PNG_RGBA : IFHIP_PNG_RGB, r.maximum_deflate == 1 ? 9 : -1, o, io_id);
+    case ifsel::kCoderPngquant: return encode_pngquant(matted(f, r, shared), o, io_id, params);   // pngquant.rs:74
+    case ifsel::kCoderWebpLossless: return encode_webp_lossless(matted(f, r, shared), o, io_id);  // webp.rs:292
+    case ifsel::kCoderWebpLossy: { const JVal p = named("webplossy"); return encode_webp_lossy(matted(f, r, shared), o, io_id, &p); }
+    default: return encode_gif(f, o, io_id);                                    // (GifEncoder::create takes no matte, auto.rs:392-395)
+    }
+}
+// The preset's matte before a coder that takes one, as encode_jpeg and encode_png treat theirs: Bitmap::apply_matte
+// (bitmaps.rs:528-541) in place -- on a private copy where other consumers still read the frame -- and an opaque matte ends
+// the alpha's meaning.
+FramePtr Job::matted(FramePtr f, const ifsel::Resolved& r, bool shared) {
+    if (!r.has_matte || !f->alpha) return f;
+    if (shared) f = clone(f);
+    check(ifhip_apply_matte_batch_device(dev(f), f->bytes(), 1, f->w, f->h, f->stride, 1, r.matte, t_job_stream));
+    if ((r.matte >> 24) == 0xFFu) f->alpha = false;
+    return f;
+}
+
 void Job::check_encode_node(const JVal& n) {
     if (n.t != JVal::Obj || n.o.size() != 1 || n.o[0].first != "encode") return;
     const JVal* preset = n.o[0].second.get("preset");
+    // (serde refuses the message before any node runs: a missing required field, a wrong type, an unknown variant)
+    if (c->encoder_selection.load(std::memory_order_relaxed) && ifsel::names_selection(preset)) (void)ifsel::read_preset(*preset);
     if (encode_coder(preset) == IFHIP_ENCODE_CODER_MOZJPEG) check_mozjpeg_preset(preset);
     if (names_webplossy(preset) && c->webp_lossy_encoder.load(std::memory_order_relaxed)) (void)check_webplossy_preset(preset);
 }

@@ -225,9 +225,35 @@ uint32_t Job::animated_frames_of(const JVal& params) {
 // The animated decodes of a job that have a "gif" encode node downstream: io_id -> frame count; empty: the job does not animate.
 std::vector<std::pair<int32_t, uint32_t>> Job::animation_plan(const JVal& fw) {
     std::vector<std::pair<int32_t, uint32_t>> found;
-    auto is_gif_encode = [](const std::string& name, const JVal& p) {
+    const bool gif_on = c->gif_encoder.load(std::memory_order_relaxed), selection = c->encoder_selection.load(std::memory_order_relaxed);
+    // With encoder selection on, an `auto` / `format` encode -- a node's preset, or what a command_string's querystring makes
+    // (one without a decode of its own) -- that comes to GIF is a "gif" node too.  The GIF outcomes are `format: gif`, `keep` on a
+    // GIF source and auto-selection on an animated source, which returns GIF before it looks at the frame (auto.rs:1154-1159):
+    // all known here, before the first frame, from the preset and the job's source (Job::find_source).  *selected_io: the
+    // output of such an encode, for the caller to mark once an animated decode is known to feed it.
+    auto is_gif_encode = [&](const std::string& name, const JVal& p, int32_t* selected_io, bool* is_selected) {
+        *is_selected = false;
         const JVal* preset = p.get("preset");
-        return name == "encode" && preset && preset->t == JVal::Str && preset->s == "gif";
+        if (name == "encode" && preset && preset->t == JVal::Str && preset->s == "gif") return gif_on;
+        if (!selection) return false;
+        const ifsel::Source src = has_source_io ? source_facts(source_io) : ifsel::Source();
+        int64_t io_id = 0;
+        JVal made;
+        if (name == "encode" && ifsel::names_selection(preset)) io_id = want_int(p, "io_id", "encode");
+        else if (name == "command_string" && p.get("encode") && p.get("encode")->t == JVal::Num && !(p.get("decode") && p.get("decode")->t == JVal::Num)) {
+            const JVal* value = p.get("value");
+            ifhip::Ir4Instructions qs;
+            std::string err;
+            if (!value || value->t != JVal::Str || ifhip::parse_querystring(value->s, &qs, &err, true) != ifhip::kQsOk) return false;   // (the node itself answers)
+            const std::string json = ifsel::preset_json_of(qs.out);
+            made = parse_json(reinterpret_cast<const uint8_t*>(json.data()), json.size());
+            preset = &made;
+            io_id = want_int(p, "encode", "command_string");
+        } else return false;
+        if (!ifsel::resolves_to_gif_without_frame(ifsel::read_preset(*preset), src)) return false;
+        *selected_io = static_cast<int32_t>(io_id);
+        *is_selected = true;
+        return true;
     };
     auto add = [&](const JVal& p, uint32_t n) {
         const int32_t id = static_cast<int32_t>(p.get("io_id")->n);
@@ -236,6 +262,8 @@ std::vector<std::pair<int32_t, uint32_t>> Job::animation_plan(const JVal& fw) {
     };
     std::string name;
     const JVal* params;
+    int32_t selected_io = 0;
+    bool is_selected = false;
     if (const JVal* steps = fw.get("steps")) {
         if (steps->t != JVal::Arr) return found;
         for (size_t i = 0; i < steps->a.size(); ++i) {
@@ -247,7 +275,9 @@ std::vector<std::pair<int32_t, uint32_t>> Job::animation_plan(const JVal& fw) {
             for (size_t j = i + 1; j < steps->a.size(); ++j) {                       // downstream: up to the next node that starts a frame of its own
                 node_of(steps->a[j], &name, &params);
                 if (name == "decode" || name == "create_canvas") break;
-                if (is_gif_encode(name, *params)) { add(*source, n); break; }
+                if (!is_gif_encode(name, *params, &selected_io, &is_selected)) continue;   // (every one of them: a selected encode is marked as it is found)
+                add(*source, n);
+                if (is_selected) anim.selected_gif[selected_io] = true;
             }
         }
         return found;
@@ -264,7 +294,8 @@ std::vector<std::pair<int32_t, uint32_t>> Job::animation_plan(const JVal& fw) {
     }
     for (const auto& kv : by_id) {
         node_of(*kv.second, &name, &params);
-        if (!is_gif_encode(name, *params)) continue;
+        if (!is_gif_encode(name, *params, &selected_io, &is_selected)) continue;
+        bool animated_ancestor = false;
         std::vector<int64_t> todo{kv.first};
         std::map<int64_t, bool> seen;
         while (!todo.empty()) {                                                      // every ancestor, over input and canvas edges
@@ -273,12 +304,38 @@ std::vector<std::pair<int32_t, uint32_t>> Job::animation_plan(const JVal& fw) {
             if (seen[id] || !by_id.count(id)) continue;
             seen[id] = true;
             node_of(*by_id[id], &name, &params);
-            if (name == "decode") if (const uint32_t n = animated_frames_of(*params)) add(*params, n);
+            if (name == "decode") if (const uint32_t n = animated_frames_of(*params)) { add(*params, n); animated_ancestor = true; }
             auto range = parents.equal_range(id);
             for (auto it = range.first; it != range.second; ++it) todo.push_back(it->second);
         }
+        if (is_selected && animated_ancestor) anim.selected_gif[selected_io] = true;   // (a selected encode a still source feeds takes frame 0, as in steps)
     }
     return found;
+}
+// The input an `auto` / `format` encode takes its cues from (the first of the reference's decoder_io_ids, auto.rs:1055-1066),
+// found ONCE per job, before any node runs: the first node in step order -- of a graph, the node of the lowest id -- that
+// decodes an input: a `decode`, or a `command_string` with a decode of its own.  A watermark's input is never it.
+void Job::find_source(const JVal& fw) {
+    auto decodes_io = [&](const JVal& n) {
+        std::string name;
+        const JVal* p;
+        node_of(n, &name, &p);
+        const JVal* id = name == "decode" ? p->get("io_id") : name == "command_string" ? p->get("decode") : nullptr;
+        if (!id || id->t != JVal::Num) return false;
+        has_source_io = true;
+        source_io = static_cast<int32_t>(id->n);
+        return true;
+    };
+    if (const JVal* steps = fw.get("steps")) {
+        if (steps->t == JVal::Arr) for (const JVal& n : steps->a) if (decodes_io(n)) return;
+        return;
+    }
+    const JVal* graph = fw.get("graph");
+    const JVal* nodes = graph ? graph->get("nodes") : nullptr;
+    if (!nodes || nodes->t != JVal::Obj) return;
+    std::map<int64_t, const JVal*> by_id;
+    for (const auto& kv : nodes->o) by_id[std::atoll(kv.first.c_str())] = &kv.second;
+    for (const auto& kv : by_id) if (decodes_io(*kv.second)) return;
 }
 // every screen of one animated source, decoded and composed once
 void Job::decode_animation_source(int32_t io_id, bool first) {
@@ -318,7 +375,10 @@ FramePtr Job::animated_screen(int32_t io_id) {
 }
 // a job: once, or -- where the animation path applies -- once per frame of the animated sources
 void Job::run_job(const JVal& fw) {
-    if (!c->gif_animation.load(std::memory_order_relaxed) || !c->gif_encoder.load(std::memory_order_relaxed)) return run_framewise(fw);
+    if (c->encoder_selection.load(std::memory_order_relaxed)) find_source(fw);
+    // (the "gif" preset collects frames where the GIF encoder is on, an `auto` / `format` preset where encoder selection is)
+    if (!c->gif_animation.load(std::memory_order_relaxed) || !(c->gif_encoder.load(std::memory_order_relaxed) || c->encoder_selection.load(std::memory_order_relaxed)))
+        return run_framewise(fw);
     const std::vector<std::pair<int32_t, uint32_t>> plan = animation_plan(fw);
     if (plan.empty()) return run_framewise(fw);
     for (const auto& p : plan)                                                       // (mod.rs:253-258: a decoder that has run out of frames while the job goes on)

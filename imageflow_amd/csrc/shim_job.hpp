@@ -17,6 +17,7 @@
 #include "../../include/imageflow_abi_subset.h"
 #include "../../include/imageflow_hip.h"
 #include "common.hpp"           // the library's per-job memory cache and thread stream (devmem.cpp)
+#include "encoder_select.hpp"   // which coder the presets `auto` and `format` come to (encoder_select.cpp; host only)
 #include "shim_json.hpp"
 #include "shim_runtime.hpp"
 
@@ -164,6 +165,7 @@ struct imageflow_context {
     std::atomic<bool> webp_lossy_intra4{false};          // ... with IFHIP_VP8_ENC_INTRA4 (the switch's value 2)
     std::atomic<uint32_t> webp_lossless_flags{0};        // EXTENSION ifhip_shim_context_set_webp_lossless_flags: the stage flags of the "webplossless" preset's coder
     std::atomic<bool> webp_lossy_encoder{false};         // EXTENSION ifhip_shim_context_set_webp_lossy_encoder: the "webplossy" preset writes a lossy WebP on the device
+    std::atomic<bool> encoder_selection{false};          // EXTENSION ifhip_shim_context_set_encoder_selection: the presets `auto` / `format` and the querystring's output keys pick a coder
     std::atomic<bool> color_management{false};           // EXTENSION ifhip_shim_context_set_color_management: every input is converted to sRGB
     bool cancellation_requested() {
         if (cancel.load(std::memory_order_relaxed)) return true;
@@ -202,6 +204,8 @@ struct Job {
     std::chrono::steady_clock::time_point t_start = std::chrono::steady_clock::now();
     bool lazy_decode = false;                                        // the decode node being run has exactly one consumer
     struct GifSource { bool seen; int repeat; uint32_t delay; bool user_input; } gif_source{false, -1, 0u, false};   // of the first GIF the job decoded
+    bool has_source_io = false;                                      // the job's source (find_source, once per job): what an `auto` / `format` encode takes its cues from
+    int32_t source_io = 0;
 
     // one executed primitive: wall clock as the reference's per-node cost (execution_engine.rs:506-538) plus the time
     // the device spent on it (hipEvents on the stream every node of this interpreter launches on)
@@ -244,6 +248,7 @@ struct Job {
         std::vector<uint8_t> user_input;
         std::map<int32_t, std::unique_ptr<AnimSource>> sources;
         std::map<int32_t, std::unique_ptr<AnimCollect>> collects;
+        std::map<int32_t, bool> selected_gif;    // the outputs whose `auto` / `format` encode comes to GIF (decided before the first frame)
     } anim;
 
     // shim_interp.cpp
@@ -263,6 +268,7 @@ struct Job {
     std::vector<std::pair<int32_t, uint32_t>> animation_plan(const JVal& fw);
     void decode_animation_source(int32_t io_id, bool first);
     FramePtr animated_screen(int32_t io_id);
+    void find_source(const JVal& fw);
     void run_job(const JVal& fw);
     void run_framewise(const JVal& fw);
 
@@ -280,6 +286,7 @@ struct Job {
     FramePtr decode_webp(int32_t io_id, Io& in);
     FramePtr decode_gif(int32_t io_id, Io& in);
     FramePtr decode(int32_t io_id, uint32_t hint_w, uint32_t hint_h, bool luma_spatial, bool luma_srgb);
+    ifsel::Source source_facts(int32_t io_id);
     // one file through a decoder's device part on the job's stream: queue(d_status) launches it; -> the file's status word, waited for
     template <typename Queue>
     uint32_t decoded_status(const char* label, Queue queue) {
@@ -330,6 +337,8 @@ struct Job {
     void encode_gif(const FramePtr& f, Io& o, int32_t io_id);
     void encode_webp_lossy(const FramePtr& f, Io& o, int32_t io_id, const JVal* preset);
     void encode_raw(const FramePtr& f, Io& o, int32_t io_id);
+    void encode_selected(FramePtr f, Io& o, int32_t io_id, const JVal* preset, bool shared);
+    FramePtr matted(FramePtr f, const ifsel::Resolved& r, bool shared);
     void check_encode_node(const JVal& n);
     void collect_frame(const FramePtr& f, int32_t io_id);
     void write_animations();

@@ -276,7 +276,9 @@ FramePtr Job::command_string(const JVal& p, FramePtr in, bool in_shared) {
         if (rc == ifhip::kQsRefused) raise(kActionNotSupported, "%s", err.c_str());
         if (rc != ifhip::kQsOk) raise(err.rfind("InvalidJson", 0) == 0 ? kInvalidJson : kArgumentInvalid, "%s", err.c_str());
     };
-    answer(ifhip::parse_querystring(value->s, &qs, &err));
+    // (with the context's encoder selection on, the output keys are read as the reference reads them instead of refused)
+    const bool selection = c->encoder_selection.load(std::memory_order_relaxed);
+    answer(ifhip::parse_querystring(value->s, &qs, &err, selection));
     std::string marks;
     if (const JVal* wm = p.get("watermarks")) if (!wm->is_null()) to_json(*wm, &marks);
     auto expansion = [&](uint32_t w, uint32_t h, uint32_t ref_w, uint32_t ref_h) {
@@ -345,8 +347,15 @@ FramePtr Job::command_string(const JVal& p, FramePtr in, bool in_shared) {
         // (trellis / scan search) is not built, so bytes and sizes differ from the reference's default for the same string
         // (README "Known differences", DESIGN "Encode").  One that names neither keeps this shim's labelled extension, the raw
         // BGRA container -- no key is accepted and then dropped.
+        // With the context's encoder selection on (ifhip_shim_context_set_encoder_selection) none of that applies: the output
+        // keys make the preset calculate_encoder_preset makes (encoder.rs:31-68) -- `auto` under format=auto or a `qp`, else
+        // `format`, `keep` where no format is named -- and Job::encode resolves it as the reference does.
         const int q = qs.jpeg_quality >= 0 ? qs.jpeg_quality : qs.quality;
-        if (qs.jpeg_out || q >= 0) {
+        if (selection) {
+            const std::string json = ifsel::preset_json_of(qs.out);
+            const JVal preset = parse_json(reinterpret_cast<const uint8_t*>(json.data()), json.size());
+            encode(out, static_cast<int32_t>(want_int(p, "encode", "command_string")), &preset, false);
+        } else if (qs.jpeg_out || q >= 0) {
             JVal qv; qv.t = JVal::Num; qv.n = q >= 0 ? q : 90;
             JVal classic; classic.t = JVal::Obj; classic.o.emplace_back("quality", qv);
             JVal preset; preset.t = JVal::Obj; preset.o.emplace_back("libjpeg_turbo", classic);

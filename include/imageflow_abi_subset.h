@@ -162,7 +162,8 @@ IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_gif_encoder(struct imageflow_cont
  * the decoded screens and the collected frames together may hold security.max_total_file_pixels pixels at the most (the
  * reference's check_total_pixels, codecs/gif/mod.rs:103-118; default 400 000 000, imageflow_types/src/lib.rs:1212-1235): a job
  * over it is refused as SizeLimitExceeded before anything is allocated.  Every other job is byte for byte what it is with
- * the switch off. */
+ * the switch off.  (With ifhip_shim_context_set_encoder_selection on, an `auto` / `format` encode that comes to GIF counts as
+ * a "gif" node, with or without the GIF encoder's switch.) */
 IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_gif_animation(struct imageflow_context *context, int on);
 /* EXTENSION.  Device coding of the libjpeg_turbo preset's options, off by default: with on != 0 an encode with
  * "progressive" and / or "optimize_huffman_coding" is entropy-coded on the device (ifhip_jpeg_encode_flags_batch_device:
@@ -171,6 +172,21 @@ IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_gif_animation(struct imageflow_co
  * geometry is refused.  The files are byte-identical either way; ifhip_shim_device_coded_files counts those coded on the
  * device.  Off, such encodes go to the host writer as before.  Returns true. */
 IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_device_jpeg_options(struct imageflow_context *context, int on);
+/* EXTENSION.  Encoder selection, off by default: with on != 0 an `encode` whose preset is {"auto": ..} or {"format": ..} is
+ * resolved as the reference resolves it (codecs/auto.rs: build_auto_encoder_details, format_auto_select, create_encoder_auto,
+ * with its quality tables) against the job's source (the first decode of its steps, or the decode node of the lowest id) and the final frame, and written as a real file by the
+ * coder that comes out: mozjpeg, libjpeg_turbo, libpng, pngquant, lodepng (a truecolour PNG of the device PNG coder, RGBA
+ * where the frame's alpha is meaningful), webp_lossless, webp_lossy (with the 4x4 modes where the lossy WebP encoder's switch
+ * has the value 2) or gif -- whatever the GIF and lossy WebP encoder switches say, whose named presets keep their meaning.
+ * The preset's matte is applied before every coder (on a private copy of a shared frame); the record carries the resolved
+ * format's mime type and extension.  A preset serde would not read is InvalidJson before the first node runs.
+ * `command_string` then reads the output keys of its querystring (format / thumbnail, qp, qp.dpr / qp.dppx, lossless, accept.*,
+ * quality, jpeg.*, webp.*, png.*) with the reference's parsers and encodes through the preset they make
+ * (ifhip_shim_querystring_encoder_preset, imageflow_hip_encoder_select.h); a string without an output key keeps the source's
+ * format.  With ifhip_shim_context_set_gif_animation on as well, an auto / format encode that comes to GIF collects the frames
+ * of an animated source as a "gif" encode node does.  Differences from the reference: imageflow_hip_encoder_select.h and
+ * DESIGN "Encoder selection".  Off, every job is byte for byte what it was.  Returns true. */
+IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_encoder_selection(struct imageflow_context *context, int on);
 
 /* The layout arithmetic behind the `constrain` and `watermark` nodes, callable on its own (no GPU, no context):
  * imageflow_riapi::ir4::process_constraint (imageflow_riapi/src/ir4/layout.rs:334-412) for a source of source_w x source_h

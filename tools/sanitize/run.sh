@@ -63,6 +63,10 @@ ASAN_OPTIONS=detect_leaks=0 ./gif_fuzz case_*.gif
 # the querystring layer (Instructions parser, colour reader, Ir4Layout, watermark splitter): untrusted text, plain host code
 g++ $SAN $INC -o querystring_fuzz "$ROOT/tools/sanitize/querystring_fuzz.cpp" "$ROOT/imageflow_amd/csrc/querystring.cpp" "$ROOT/imageflow_amd/csrc/layout.cpp" "$ROOT/tools/sanitize/stubs.cpp"
 ./querystring_fuzz
+# encoder selection (the querystring's output keys, serde's readers of the presets `auto` / `format`, the quality tables and the resolution): plain host code
+g++ $SAN -ffp-contract=off $INC -o encoder_select_fuzz "$ROOT/tools/sanitize/encoder_select_fuzz.cpp" "$ROOT/imageflow_amd/csrc/encoder_select.cpp" "$ROOT/imageflow_amd/csrc/querystring.cpp" \
+  "$ROOT/imageflow_amd/csrc/layout.cpp" "$ROOT/imageflow_amd/csrc/shim_json.cpp" "$ROOT/tools/sanitize/stubs.cpp"
+./encoder_select_fuzz
 # the whole library host-only (every translation unit, device blobs replaced by empty stand-ins) behind the libimageflow
 # ABI subset: damaged JSON jobs
 mkdir -p lib && : > fatbin_stubs.c
