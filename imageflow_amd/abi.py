@@ -74,6 +74,10 @@ def _bind():
     L.ifhip_shim_context_set_color_management.restype = C.c_bool
     L.ifhip_shim_context_set_webp_lossy_decoder.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_webp_lossy_decoder.restype = C.c_bool
+    L.ifhip_shim_context_set_device_progressive_decoder.argtypes = [vp, C.c_int]
+    L.ifhip_shim_context_set_device_progressive_decoder.restype = C.c_bool
+    L.ifhip_shim_device_progressive_decodes.argtypes = [vp, C.POINTER(C.c_int64)]
+    L.ifhip_shim_device_progressive_decodes.restype = C.c_int64
     L.ifhip_shim_context_set_webp_lossy_encoder.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_webp_lossy_encoder.restype = C.c_bool
     L.ifhip_shim_context_set_webp_lossless_flags.argtypes = [vp, C.c_uint32]
@@ -224,6 +228,16 @@ class Context:
         libwebp's pixels -- `decode`, `watermark`, `command_string` and v1/get_image_info take them -- instead of being
         ImageTypeNotSupported."""
         return self.L.ifhip_shim_context_set_webp_lossy_decoder(self.p, 1 if on else 0)
+
+    def set_device_progressive_decoder(self, on):
+        """EXTENSION, off by default: progressive JPEG inputs are entropy-decoded on the device; a file its front end refuses,
+        or one whose status word is not 0, goes to the host reader as ever.  Outputs are the same bytes either way."""
+        return self.L.ifhip_shim_context_set_device_progressive_decoder(self.p, 1 if on else 0)
+
+    def device_progressive_decodes(self):
+        """-> (decodes of this context that took the device path, decodes that fell back to the host reader)"""
+        back = C.c_int64()
+        return int(self.L.ifhip_shim_device_progressive_decodes(self.p, C.byref(back))), int(back.value)
 
     def set_webp_lossy_encoder(self, on, intra4=False):
         """EXTENSION, off by default: `encode` with the preset {"webplossy": {"quality": q}} writes a lossy WebP file on the device

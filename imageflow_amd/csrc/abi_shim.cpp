@@ -311,6 +311,18 @@ bool ifhip_shim_context_set_webp_lossy_decoder(struct imageflow_context* c, int 
     c->webp_lossy_decoder.store(on != 0, std::memory_order_relaxed);
     return true;
 }
+// EXTENSION: progressive JPEG inputs are entropy-decoded on the device (see Job::decode_jpeg); off by default, where they are
+// decoded by the host reader as ever.  The getter: decodes that took the device path, and (*fell_back) those that came back.
+bool ifhip_shim_context_set_device_progressive_decoder(struct imageflow_context* c, int on) {
+    CTX_OR_ABORT(c);
+    c->device_progressive_decoder.store(on != 0, std::memory_order_relaxed);
+    return true;
+}
+int64_t ifhip_shim_device_progressive_decodes(struct imageflow_context* c, int64_t* fell_back) {
+    CTX_OR_ABORT(c);
+    if (fell_back) *fell_back = c->progressive_fallbacks.load(std::memory_order_relaxed);
+    return c->progressive_device_decodes.load(std::memory_order_relaxed);
+}
 // EXTENSION: the "webplossy" preset of `encode` writes a lossy WebP on the device (see Job::encode_webp_lossy); off by default,
 // where the preset stays the raw-container tap it has always been.  2: on, with the sixteen 4x4 luma modes (IFHIP_VP8_ENC_INTRA4).
 bool ifhip_shim_context_set_webp_lossy_encoder(struct imageflow_context* c, int on) {

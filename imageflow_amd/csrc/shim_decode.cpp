@@ -14,6 +14,7 @@
 #include <utility>
 #include <vector>
 
+#include "../../include/imageflow_hip_jpeg_progressive.h"   // the device entropy decoder of progressive files (jpeg_progressive_decode.hip)
 #include "color_profile.hpp"   // a colour profile as a conversion plan (color_profile.cpp; the kernel: color_profile.hip)
 #include "png_read.hpp"         // the PNG chunk walk and the device decode of a walked file (png_read.cpp, png_decode.hip)
 #include "gif_read.hpp"         // the container walk and the device decode of a GIF (gif_read.cpp, gif_decode.hip)
@@ -168,7 +169,7 @@ DecodeCoalescer& coalescer_for_device() {
 }
 
 // Progressive / multi-scan files: entropy decoding on the host (csrc/jpeg_read.cpp), planes uploaded, everything else as usual
-std::shared_ptr<DecodedBatch> decode_on_host(Job& j, const Io& in) {
+std::shared_ptr<DecodedBatch> decode_on_host(Job& j, const Io& in, bool polled = false) {
     auto b = std::make_shared<DecodedBatch>();
     uint16_t qt[192];
     int progressive = 0;
@@ -181,7 +182,7 @@ std::shared_ptr<DecodedBatch> decode_on_host(Job& j, const Io& in) {
         b->per_image[k] = static_cast<size_t>(b->bw[k]) * b->bh[k] * 64u;
         host[k].resize(std::max<size_t>(b->per_image[k], 64u));
     }
-    j.poll_cancel();
+    if (!polled) j.poll_cancel();                                  // (polled: the device path's poll was this decode's)
     check(ifhip_jpeg_read_coefficients_host(in.in, in.in_len, host[0].data(), host[1].data(), host[2].data(), qt));
     for (int k = 0; k < 3; ++k) {
         hip_check(job_malloc(reinterpret_cast<void**>(&b->coef[k]), host[k].size() * 2u), "hipMalloc(coefficients)");
@@ -189,6 +190,39 @@ std::shared_ptr<DecodedBatch> decode_on_host(Job& j, const Io& in) {
     }
     hip_check(job_malloc(reinterpret_cast<void**>(&b->d_qt), sizeof qt), "hipMalloc(qt)");
     hip_check(static_cast<hipError_t>(ifhip::copy_to_device(b->d_qt, qt, sizeof qt)), "upload(qt)");
+    return b;
+}
+
+// EXTENSION (ifhip_shim_context_set_device_progressive_decoder): a progressive file's scans on the device -- prepare on this
+// job's thread, one upload, the batch call with n = 1 on the job's stream (csrc/jpeg_progressive_decode.hip); the planes never
+// leave HBM.  nullptr: the front end refuses the file (*polled stays false), or its status word is not 0 (*polled: the
+// decoder's cancellation point has been passed) -- the caller asks the host reader, whose verdict stands.
+std::shared_ptr<DecodedBatch> decode_progressive_on_device(Job& j, const Io& in, bool* polled) {
+    ifhip_jpeg_progressive_prepared* p = nullptr;
+    if (ifhip_jpeg_progressive_prepare(&p, in.in, in.in_len) != IFHIP_OK) return nullptr;
+    struct Guard { ifhip_jpeg_progressive_prepared* p; ~Guard() { ifhip_jpeg_progressive_prepared_destroy(p); } } guard{p};
+    auto b = std::make_shared<DecodedBatch>();
+    uint16_t qt[192];
+    check(ifhip_jpeg_progressive_prepared_info(p, &b->w, &b->h, &b->ncomp, b->hs, b->vs, b->bw, b->bh, qt, nullptr, nullptr, nullptr));
+    size_t bytes[3];
+    for (int k = 0; k < 3; ++k) {
+        b->per_image[k] = static_cast<size_t>(b->bw[k]) * b->bh[k] * 64u;
+        bytes[k] = b->per_image[k] * 2u;
+        hip_check(job_malloc(reinterpret_cast<void**>(&b->coef[k]), std::max<size_t>(b->per_image[k], 64u) * 2u), "hipMalloc(coefficients)");
+        if (k >= b->ncomp) hip_check(static_cast<hipError_t>(ifhip::zero_device(b->coef[k], 128u)), "clear(coefficients)");   // (as the host path uploads them)
+    }
+    hip_check(job_malloc(reinterpret_cast<void**>(&b->d_qt), sizeof qt + 16u), "hipMalloc(qt)");       // the tables, then the status word
+    uint32_t* d_status = reinterpret_cast<uint32_t*>(reinterpret_cast<uint8_t*>(b->d_qt) + sizeof qt);
+    hip_check(static_cast<hipError_t>(ifhip::copy_to_device(b->d_qt, qt, sizeof qt)), "upload(qt)");
+    j.poll_cancel();                                               // the decoder's cancellation point, as decode_on_host's
+    *polled = true;
+    const ifhip_jpeg_progressive_prepared* files[1] = {p};
+    int16_t* c0[1] = {b->coef[0]}, *c1[1] = {b->ncomp > 1 ? b->coef[1] : nullptr}, *c2[1] = {b->ncomp > 2 ? b->coef[2] : nullptr};
+    check(ifhip_jpeg_progressive_decode_batch_device(files, 1, c0, c1, c2, bytes, d_status, t_job_stream));
+    uint32_t word = 0;
+    hip_check(hipMemcpyAsync(&word, d_status, sizeof word, hipMemcpyDeviceToHost, t_job_stream), "download(status)");
+    hip_check(static_cast<hipError_t>(ifhip::wait_stream(t_job_stream)), "download(status)");
+    if (word) return nullptr;                                      // (the planes go back to the cache with `b`)
     return b;
 }
 
@@ -480,7 +514,12 @@ FramePtr Job::decode(int32_t io_id, uint32_t hint_w, uint32_t hint_h, bool luma_
     if (prc == IFHIP_METHOD_NOT_IMPLEMENTED) {
         // not a single-scan baseline file: progressive (what the reference's mozjpeg preset writes) or multi-scan -- the scans
         // are decoded on the host as MzDec does (libjpeg's jdphuff.c), the pixel stage behind them stays on the GPU
-        rq.batch = decode_on_host(*this, in);
+        bool polled = false;
+        if (c->device_progressive_decoder.load(std::memory_order_relaxed)) {
+            rq.batch = decode_progressive_on_device(*this, in, &polled);
+            (rq.batch ? c->progressive_device_decodes : c->progressive_fallbacks).fetch_add(1, std::memory_order_relaxed);
+        }
+        if (!rq.batch) rq.batch = decode_on_host(*this, in, polled);
         rq.index = 0; rq.batch_size = 1;
     } else {
         check(prc);

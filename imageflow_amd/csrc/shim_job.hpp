@@ -162,6 +162,9 @@ struct imageflow_context {
     std::atomic<bool> gif_animation{false};              // EXTENSION ifhip_shim_context_set_gif_animation: animated GIFs run once per frame into one file
     std::atomic<bool> gif_encoder{false};                // EXTENSION ifhip_shim_context_set_gif_encoder: the "gif" preset writes a GIF on the device
     std::atomic<bool> webp_lossy_decoder{false};         // EXTENSION ifhip_shim_context_set_webp_lossy_decoder: lossy WebP inputs are decoded on the device
+    std::atomic<bool> device_progressive_decoder{false}; // EXTENSION ifhip_shim_context_set_device_progressive_decoder: progressive JPEG scans are entropy-decoded on the device
+    std::atomic<int64_t> progressive_device_decodes{0};  // ... decodes of this context that took that path,
+    std::atomic<int64_t> progressive_fallbacks{0};       // ... and those that went back to the host reader (a refused script, a nonzero status word)
     std::atomic<bool> webp_lossy_intra4{false};          // ... with IFHIP_VP8_ENC_INTRA4 (the switch's value 2)
     std::atomic<uint32_t> webp_lossless_flags{0};        // EXTENSION ifhip_shim_context_set_webp_lossless_flags: the stage flags of the "webplossless" preset's coder
     std::atomic<bool> webp_lossy_encoder{false};         // EXTENSION ifhip_shim_context_set_webp_lossy_encoder: the "webplossy" preset writes a lossy WebP on the device

@@ -134,6 +134,17 @@ IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_color_management(struct imageflow
  * default, where a lossy file stays ImageTypeNotSupported.  max_decode_size, the ICCP policy, webp_decoder_hints and EXIF
  * are treated as for a lossless file; animated WebP and libwebp's decode-time rescaler stay refused.  Returns true. */
 IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_webp_lossy_decoder(struct imageflow_context *context, int on);
+/* EXTENSION: progressive (SOF2) JPEG inputs are entropy-decoded on the device (include/imageflow_hip_jpeg_progressive.h: the
+ * file is prepared on the job's thread, uploaded once, and its coefficient planes never leave HBM) in `decode`, `watermark` and
+ * `command_string`.  Off by default, where such files are decoded by the host reader and every job is byte for byte what it
+ * was.  With it on a job's outputs are the same bytes: a file the front end refuses (a sequential multi-scan file, a
+ * progression libjpeg decodes with a warning) or whose status word is not 0 (damaged entropy data) goes to the host reader
+ * exactly as with the switch off, and that reader's answer -- planes or error -- stands.  Downscale hints, EXIF, the ICC
+ * policy, cancellation and the `performance` block are unchanged.  Returns true.
+ * ifhip_shim_device_progressive_decodes: how many decodes of this context's jobs took the device path; *fell_back (may be
+ * NULL): how many were sent back to the host reader.  Both stay 0 with the switch off. */
+IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_device_progressive_decoder(struct imageflow_context *context, int on);
+IMAGEFLOW_SHIM_API int64_t ifhip_shim_device_progressive_decodes(struct imageflow_context *context, int64_t *fell_back);
 /* EXTENSION: `encode` with the preset {"webplossy": {"quality": q}} writes a lossy WebP file on the device
  * (ifhip_webp_lossy_encode_batch_device: WebPEncoder::write_frame over WebPEncodeBGRA / WebPEncodeBGR, codecs/webp.rs) and reports
  * image/webp; off by default, where the preset writes the raw BGRA container as ever.  With it on, the bare string "webplossy" and a
