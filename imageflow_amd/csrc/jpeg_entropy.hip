@@ -6,7 +6,10 @@
 // (jpeg_kernels.hip) consumes, so a compressed file is the only thing that crosses PCIe.
 //
 // Host: jpeg_parse.cpp reads the markers (SOF0/SOF1, DHT, DQT, DRI, SOS), un-stuffs the scan and splits it at restart markers
-// into *segments* (independent bit streams with a known start state); this file derives the decode tables and assembles the batch.
+// into *segments* (independent bit streams with a known start state).  The rest of the host half is plain C++ that a host
+// compiler builds alone: jpeg_entropy_tables.hpp / .cpp (the entry formats both sides read, the decode tables of a file),
+// jpeg_entropy_plan.hpp / .cpp (what is prepared of a file, the layout of a batch's table block) and jpeg_scan_report.cpp (the
+// host diagnostic).  This file keeps the kernels, the device side of the two handles, the uploads and the launches.
 // Device: the self-synchronising parallel decode (Klein & Wiseman; Weissenberger & Schmidt, ICPP 2018):
 //   * the stream is cut into sub-sequences of 1024 bits, one lane each;
 //   * round 0 decodes every sub-sequence speculatively from state (block 0 of the MCU, coefficient 0); because Huffman
@@ -22,74 +25,17 @@
 // Coefficient-exact against oracle/jpeg_oracle.c jo_jpeg_read_coefficients (itself pinned to libjpeg-turbo).
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
-#include <stdexcept>
 #include <string>
 #include <thread>
-#include <cstdio>
 #include <vector>
 
 #include "hip_entry.hpp"
-#include "jpeg_parse.hpp"
+#include "jpeg_entropy_plan.hpp"
 
 namespace ifhip {
-
-constexpr uint32_t kLutBits = 9;          // (kSubBits, the bits of a sub-sequence: jpeg_parse.hpp, the un-stuffer pads to it)
-
-// Huffman tables in the form every pass reads.  Everything a pass needs from a symbol sits in one 32-bit entry, found
-// with ONE lookup by the next kLutBits bits of the stream -- or two for the 2 % of the symbols whose code is longer:
-//   bits 0-7   bits to skip (code length + magnitude bits); 0 = the code is longer than the lookup
-//   bits 8-15  zigzag advance: DC 1; AC coefficient run + 1; ZRL 16; EOB 64 (reaching 64 ends the block)
-//   bits 16-23 code length (32: no such code), bits 24-31 the symbol.
-// A first-level entry with skip 0 points into the image's second level (`pool`): bits 16-31 the offset of a sub-table
-// indexed by the n bits that follow the first kLutBits (n = longest code with this prefix - kLutBits), bits 8-15 hold
-// 32 - n.  jdhuff.c's slow path (the serial "first l with code_l <= maxcode[l]" search) survives only for sub-tables
-// that did not fit the pool (first-level entry 0): it reads SearchTab from global memory and no real file gets there.
-constexpr uint32_t kLutEntries = 1u << kLutBits;
-constexpr uint32_t kPoolEntries = 768;
-static_assert(kLutBits >= 8u && kLutBits <= 11u, "first-level lookup: the pair entries assume a code + magnitude of < 32 bits behind it");
-static_assert(kPoolEntries >= 128u && kPoolEntries <= 65535u, "a first-level pointer holds the pool offset in 16 bits; one sub-table is up to 128 entries");
-struct FastTabs {                                    // one image: [comp][dc, ac] and their shared second level
-    uint32_t lut[6][kLutEntries];
-    uint32_t pool[kPoolEntries];
-};
-struct SearchTab {                                   // jdhuff.c jpeg_make_d_derived_tbl, global memory only
-    int32_t maxcode[18];                             // largest code of each length (monotone, see derive_search_table)
-    int32_t valoff[18];                              // huffval index of the first code of each length minus that code
-    uint8_t val[256];
-};
-__host__ __device__ inline uint32_t fast_entry(bool ac, uint32_t len, uint32_t sym) {
-    const uint32_t sz = sym & 15u, r = sym >> 4;
-    const uint32_t adv = ac ? (sz ? r + 1u : (r == 15u ? 16u : 64u)) : 1u;
-    return (sym << 24) | (len << 16) | (adv << 8) | (len + sz);
-}
-// A bit pattern no code starts with (corrupt data, or a speculative decode off the symbol grid): 16 bits are skipped as
-// symbol 0, the length field says 32 (a bit no real length has) and the write pass reports it.
-// The synchronisation rounds only track the decoder state, and at q85 a symbol is ~6 bits: their tables (`ptabs`) carry in
-// bits 16-31 the skip and zigzag advance of this symbol AND the next one where the next code still lies inside the lookup
-// window (both AC, same table; 31 % fewer table reads on 4K q85 files), else a copy of bits 0-15.  The pair applies when
-// the first symbol neither ends the block nor the sub-sequence.
-__host__ __device__ inline uint32_t pair_entry(uint32_t first, uint32_t both) { return (first & 0xffffu) | (both << 16); }
-__host__ __device__ inline uint32_t invalid_entry(bool ac) { return (32u << 16) | ((ac ? 64u : 1u) << 8) | 16u; }
-
-
-struct EntropyGeom {
-    uint32_t ncomp, blocks_per_mcu, mcus_w, mcus_h;
-    uint32_t bw[3], bh[3];
-    uint8_t kcomp[kMaxBlocksInMcu], kdx[kMaxBlocksInMcu], kdy[kMaxBlocksInMcu];   // block k of an MCU: component and offset inside the MCU
-    uint32_t kcomp_packed;                           // kcomp as 2-bit fields: the per-symbol lookup is a shift, not a load
-    uint32_t hs[3], vs[3];
-};
-
-struct Segment {                                     // an independently decodable run: (image, restart interval)
-    uint32_t first_sub, n_sub;
-    uint32_t bit_end;                                // absolute bit index one past the segment's data
-    uint32_t n_blocks;                               // blocks it must produce
-    uint32_t image, first_mcu;
-};
 
 struct EntropyArgs {
     EntropyGeom g;
@@ -175,28 +121,6 @@ struct Reader {
         next = stream_word(lds_words, at);
     }
 };
-
-// Entry of a symbol whose code is longer than the first-level lookup (e = that lookup's entry, skip field 0).
-// kPairs: 0 plain entries, 1 pair entries everywhere (ptabs), 2 pair entries in the AC tables only (ctabs)
-template <int kPairs = 0, typename Tabs>
-__device__ __forceinline__ uint32_t long_entry(const Tabs* T, const SearchTab* S, uint32_t slot, uint32_t e, uint32_t bits) {
-    if (e != 0u) return T->pool[(e >> 16) + ((bits << kLutBits) >> ((e >> 8) & 255u))];
-    // jdhuff.c's slow path "l = min{l : code_l <= maxcode[l]}" without its dependent chain: all candidate lengths are
-    // compared at once (the host stores a monotone maxcode, see derive_search_table)
-    const SearchTab* t = S + slot;
-    const bool ac = (slot & 1u) != 0u;
-    uint32_t l = kLutBits + 1u;
-#pragma unroll
-    for (uint32_t k = kLutBits + 1u; k <= 16u; ++k)
-        l += static_cast<int32_t>(bits >> (32u - k)) > t->maxcode[k] ? 1u : 0u;
-    uint32_t r = invalid_entry(ac);
-    if (l <= 16u) {
-        const int32_t code = static_cast<int32_t>(bits >> (32u - l));
-        const uint32_t sym = t->val[(code + t->valoff[l]) & 255];
-        if (ac || sym <= 11u) r = fast_entry(ac, l, sym);
-    }
-    return (kPairs == 1 || (kPairs == 2 && ac)) ? pair_entry(r, r) : r;
-}
 
 // ---- synchronisation and count passes: the lean walker ----------------------------------------------------------
 // These passes need the decoder STATE only (bit position, block-in-MCU, zigzag index), not the coefficients.  A dense
@@ -318,9 +242,8 @@ __device__ __forceinline__ void stage_fast_tables(const FastTabs* gtabs, FastTab
     for (uint32_t i = threadIdx.x; i < sizeof(FastTabs) / 4u; i += kWg) dst[i] = src[i];
 }
 
-
-constexpr uint32_t kSyncLanes = 1024;               // sub-sequences per workgroup in these passes
-constexpr uint32_t kSyncCols = kSyncLanes + 1u;                     // a walk stops within 31 bits of its end and looks 3 words ahead
+// (kSyncLanes, kWarmLanes, kOwnSubs, kInnerRounds, kChunkSubs, kFlagWords: jpeg_entropy_tables.hpp, the host sizes a batch by them)
+constexpr uint32_t kSyncCols = kSyncLanes + 1u;                    // a walk stops within 31 bits of its end and looks 3 words ahead
 constexpr uint32_t kFastStageDwords = kSyncCols * kColPitch;
 
 // One synchronisation launch.  Inside the workgroup the fixpoint iteration runs in LDS: in every iteration the
@@ -330,22 +253,8 @@ constexpr uint32_t kFastStageDwords = kSyncCols * kColPitch;
 // lane costs as much as a full one -- so the iteration COMPACTS them: sub-sequence states live in LDS (one packed word:
 // relative bit position | block-in-MCU << 21 | zigzag index << 25), the lanes that need a decode enter a work list
 // through a ballot / prefix count, and lane k decodes the k-th entry.  An iteration then costs what its dense waves cost.
-// (No cap below the workgroup's own length: the loop ends as soon as nothing is pending, and a chain of corrections that
-// is cut short costs a host round trip, more launches and a REPEATED count + write pass.  With a cap of 24 that was half of
-// all 64-file decodes of BASELINE cfg4's files -- noise files re-synchronise with p ~ 0.4 per sub-sequence, 430 000
-// sub-sequences: the longest chain of a batch is ~ ln 430 000 / ln (1 / 0.6) = 25 -- round 6, profiles/r6_entropy_rounds.txt.)
-constexpr uint32_t kInnerRounds = 1024;
 constexpr uint32_t kWaveWalkMax = 16;                          // at most this many pending sub-sequences: one wave per walk
-// The first kWarmLanes lanes of a workgroup decode the sub-sequences IN FRONT of its own range in round 0 and discard the
-// result: the workgroup's first own sub-sequence then starts from a state that has had kWarmLanes sub-sequences to
-// synchronise (one fails to with probability ~0.4), so corrections across workgroup boundaries -- a whole extra launch
-// of lone walks -- all but disappear.  Later rounds run without them.
-constexpr uint32_t kWarmLanes = 16;
-constexpr uint32_t kOwnSubs = kSyncLanes - kWarmLanes;                         // sub-sequences a workgroup owns
-static_assert(kWarmLanes < kSyncLanes && kSyncLanes % 64u == 0u && kSyncLanes <= 1024u, "whole waves, one workgroup");
-constexpr uint32_t kNever = 0xffffffffu;
-constexpr uint32_t kFlagWords = 18;                                             // changed[16], errors, unsettled
-constexpr uint32_t kChunkSubs = 512;                                            // sub-sequences per workgroup of the write pass                                       // no decode yet (no real state packs to this)
+constexpr uint32_t kNever = 0xffffffffu;                       // no decode yet (no real state packs to this)
 static_assert((kSyncLanes + 2u) * kSubBits < (1u << 21), "packed state: 21 bits of relative position");
 
 __device__ __forceinline__ uint32_t pack_state(uint32_t p_rel, uint32_t cz) { return p_rel | ((cz >> 8) << 21) | ((cz & 255u) << 25); }
@@ -730,122 +639,6 @@ __global__ void __launch_bounds__(kWriteLanes) entropy_write_kernel(const Entrop
 
 using namespace ifhip;
 
-// ==================================================================================================================
-// host: decode tables (the parser and the un-stuffer: jpeg_parse.cpp)
-// ==================================================================================================================
-namespace {
-
-void derive_search_table(const HuffSpec& h, SearchTab* t) {
-    std::memset(t, 0, sizeof *t);
-    std::memcpy(t->val, h.vals, 256);
-    int32_t code = 0;
-    int k = 0;
-    for (int l = 1; l <= 16; ++l) {
-        t->valoff[l] = k - code;
-        k += h.bits[l];
-        code += h.bits[l];
-        // Largest code of this length.  A length without codes gets the previous bound extended by a 1 bit instead of
-        // jdhuff's -1: the serial search "first l with code_l <= maxcode[l]" is unchanged (it only ever reaches l when
-        // code_(l-1) > maxcode[l-1], and then code_l > (maxcode[l-1] << 1 | 1) as well), and "code_l > maxcode[l]" becomes
-        // monotone in l, which lets the kernel count the lengths in parallel.
-        t->maxcode[l] = h.bits[l] ? code - 1 : (l > 1 ? (t->maxcode[l - 1] < 0 ? -1 : ((t->maxcode[l - 1] << 1) | 1)) : -1);
-        code <<= 1;
-    }
-    t->maxcode[17] = 0x7fffffff;
-}
-// First level of one table into F->lut[slot], its second level appended to the image's pool (*pool_used entries taken).
-void derive_fast_table(const HuffSpec& h, bool ac, FastTabs* F, uint32_t slot, uint32_t* pool_used, uint32_t pool_limit) {
-    uint32_t* lut = F->lut[slot];
-    for (uint32_t i = 0; i < kLutEntries; ++i) lut[i] = invalid_entry(ac);
-    // a DC symbol is a magnitude category, at most 11 in baseline JPEG: larger ones decode as "no such code"
-    auto entry = [&](uint32_t l, uint32_t sym) { return (!ac && sym > 11u) ? invalid_entry(ac) : fast_entry(ac, l, sym); };
-    struct LongCode { uint32_t code; uint8_t len, sym; };
-    std::vector<LongCode> longs;
-    uint8_t maxlen[kLutEntries] = {};
-    uint32_t code = 0;
-    int k = 0;
-    for (uint32_t l = 1; l <= 16u; ++l) {
-        for (int i = 0; i < h.bits[l]; ++i, ++k, ++code) {
-            if (l <= kLutBits) {
-                const uint32_t first = code << (kLutBits - l);
-                for (uint32_t f = 0; f < (1u << (kLutBits - l)); ++f)
-                    if (first + f < kLutEntries) lut[first + f] = entry(l, h.vals[k & 255]);
-            } else {
-                const uint32_t prefix = code >> (l - kLutBits);
-                if (prefix >= kLutEntries) continue;                 // over-subscribed table: the pattern cannot occur
-                maxlen[prefix] = static_cast<uint8_t>(l);            // lengths ascend
-                longs.push_back(LongCode{code, static_cast<uint8_t>(l), h.vals[k & 255]});
-            }
-        }
-        code <<= 1;
-    }
-    for (uint32_t prefix = 0; prefix < kLutEntries; ++prefix) {
-        if (!maxlen[prefix]) continue;
-        const uint32_t n = maxlen[prefix] - kLutBits, size = 1u << n;
-        if (*pool_used + size > pool_limit) { lut[prefix] = 0u; continue; }          // left to the serial search
-        for (uint32_t i = 0; i < size; ++i) F->pool[*pool_used + i] = invalid_entry(ac);
-        lut[prefix] = (*pool_used << 16) | ((32u - n) << 8);
-        *pool_used += size;
-    }
-    for (const LongCode& lc : longs) {
-        const uint32_t prefix = lc.code >> (lc.len - kLutBits);
-        if (lut[prefix] == 0u) continue;
-        const uint32_t n = maxlen[prefix] - kLutBits, rem = lc.len - kLutBits, off = lut[prefix] >> 16;
-        const uint32_t sub = (lc.code & ((1u << rem) - 1u)) << (n - rem);
-        for (uint32_t f = 0; f < (1u << (n - rem)); ++f) F->pool[off + sub + f] = entry(lc.len, lc.sym);
-    }
-}
-// The pair form of an image's tables (see pair_entry): same first-level pointers and pool layout, every entry carries its
-// own skip / advance twice unless the next AC code is visible in the rest of the lookup window.
-void derive_pair_tables(const FastTabs& F, int ncomp, FastTabs* Pt) {
-    for (uint32_t i = 0; i < kPoolEntries; ++i) Pt->pool[i] = pair_entry(F.pool[i], F.pool[i]);
-    for (uint32_t slot = 0; slot < 6u; ++slot)
-        for (uint32_t i = 0; i < kLutEntries; ++i) {
-            const uint32_t e = F.lut[slot][i];
-            uint32_t out = (e & 255u) ? pair_entry(e, e) : e;                        // skip 0: pointer into the pool / serial search
-            const uint32_t skip1 = e & 255u, adv1 = (e >> 8) & 255u;
-            if ((slot & 1u) && slot < 2u * static_cast<uint32_t>(ncomp) && skip1 != 0u && skip1 < kLutBits && adv1 < 64u) {
-                const uint32_t e2 = F.lut[slot][(i << skip1) & (kLutEntries - 1u)];   // the window behind the first symbol
-                const uint32_t len2 = (e2 >> 16) & 255u;
-                if ((e2 & 255u) != 0u && len2 <= kLutBits - skip1)                   // a whole code (never the 32 of "no such code")
-                    out = pair_entry(e, (skip1 + (e2 & 255u)) | ((adv1 + ((e2 >> 8) & 255u)) << 8));
-            }
-            Pt->lut[slot][i] = out;
-        }
-}
-// The count pass's form: pair entries in the AC tables, the DC tables (and their parts of the pool) as they are.
-void derive_count_tables(const FastTabs& F, const FastTabs& Pt, FastTabs* Ct) {
-    *Ct = Pt;
-    for (uint32_t slot = 0; slot < 6u; slot += 2u)
-        for (uint32_t i = 0; i < kLutEntries; ++i) {
-            const uint32_t e = F.lut[slot][i];
-            Ct->lut[slot][i] = e;
-            if ((e & 255u) == 0u && e != 0u) {
-                const uint32_t off = e >> 16, size = 1u << (32u - ((e >> 8) & 255u));
-                for (uint32_t k = 0; k < size && off + k < kPoolEntries; ++k) Ct->pool[off + k] = F.pool[off + k];
-            }
-        }
-}
-// The six tables of one image; components that name the same table share its second level.
-void derive_image_tables(const ParsedJpeg& P, FastTabs* F, SearchTab* S6, uint32_t pool_limit, uint32_t* pool_used_out = nullptr) {
-    std::memset(F, 0, sizeof *F);
-    std::memset(S6, 0, 6u * sizeof *S6);
-    uint32_t pool_used = 0;
-    for (int c = 0; c < P.ncomp; ++c)
-        for (uint32_t ac = 0; ac < 2u; ++ac) {
-            const uint32_t slot = 2u * static_cast<uint32_t>(c) + ac;
-            const uint8_t id = ac ? P.ta[c] : P.td[c];
-            derive_search_table(ac ? P.ac[id] : P.dc[id], &S6[slot]);
-            int same = -1;
-            for (int o = 0; o < c; ++o) if ((ac ? P.ta[o] : P.td[o]) == id) same = o;
-            if (same >= 0) std::memcpy(F->lut[slot], F->lut[2u * static_cast<uint32_t>(same) + ac], sizeof F->lut[slot]);
-            else derive_fast_table(ac ? P.ac[id] : P.dc[id], ac != 0u, F, slot, &pool_used, pool_limit);
-        }
-    if (pool_used_out) *pool_used_out = pool_used;
-}
-
-}  // namespace
-
 struct ifhip_jpeg_entropy {
     int device = -1;
     uint32_t n_images = 0;
@@ -875,16 +668,10 @@ static int dev_alloc(ifhip_jpeg_entropy* e, T** out, size_t count, const T* init
 // big-endian words (every segment padded to 1 024 bits) in PINNED memory, its decode tables derived.  A batch is then
 // assembled from n of these with no further pass over the data: n asynchronous uploads.  (A service that runs one job per
 // thread prepares each job's file on that job's thread -- imageflow_abi/src/lib.rs:20-27 -- and hands the handles of
-// whatever is waiting to ONE device call.)
-struct ifhip_jpeg_prepared {
-    ParsedJpeg P;
-    uint16_t qt[192];
-    ScanSegments seg;                                // per restart segment, and the sub-sequences of them all
+// whatever is waiting to ONE device call.)  The host part (PreparedHost, jpeg_entropy_plan.hpp) is what a batch is planned from.
+struct ifhip_jpeg_prepared : PreparedHost {
     uint32_t* words = nullptr;                       // pinned (devmem cache)
     size_t n_words = 0;
-    FastTabs ftabs, ptabs, ctabs;
-    SearchTab stabs[6];
-    uint32_t pool_limit = kPoolEntries;
     // ifhip_jpeg_prepared_upload: the words on the device already, queued on the owner's stream; `uploaded` marks the copy's end
     // (the event stays with a recycled handle, the block does not)
     uint32_t* d_words = nullptr;
@@ -932,40 +719,17 @@ void give_prepared(ifhip_jpeg_prepared* p) {
 struct GivePrepared { void operator()(ifhip_jpeg_prepared* p) const { give_prepared(p); } };
 }  // namespace
 
-static uint32_t test_hook_u32(const char* name, uint32_t dflt, uint32_t hi) {
-    // test hooks: the rarely taken paths (serial code search for sub-tables that overflow the pool; further rounds after an
-    // unsettled count pass) are forced by shrinking the pool / the iterations per launch
-    const char* v = debug_switch(name);
-    return v ? std::min<uint32_t>(static_cast<uint32_t>(std::strtoul(v, nullptr, 10)), hi) : dflt;
-}
-
 static int prepare_impl(ifhip_jpeg_prepared** out, const uint8_t* file, size_t len, uint32_t index_for_messages) {
     std::unique_ptr<ifhip_jpeg_prepared, GivePrepared> R(take_prepared());
-    ParsedJpeg& P = R->P;
-    P = ParsedJpeg();
-    if (int rc = parse_jpeg(file, len, &P)) return rc;
-    jpeg::report_quant_tables(P, P, R->qt);
-    std::memset(&R->ftabs, 0, sizeof R->ftabs); std::memset(&R->ptabs, 0, sizeof R->ptabs); std::memset(&R->ctabs, 0, sizeof R->ctabs);   // (a recycled handle)
-    std::memset(R->stabs, 0, sizeof R->stabs);
-    R->pool_limit = test_hook_u32("ent_test_pool", kPoolEntries, kPoolEntries);
-    derive_image_tables(P, &R->ftabs, R->stabs, R->pool_limit);
-    derive_pair_tables(R->ftabs, P.ncomp, &R->ptabs);
-    derive_count_tables(R->ftabs, R->ptabs, &R->ctabs);
-    const uint32_t total_mcus = P.mcus_w * P.mcus_h;
+    if (int rc = prepare_tables(R.get(), file, len, test_hook_u32("ent_test_pool", kPoolEntries, kPoolEntries))) return rc;
     void* pinned = nullptr;
     size_t pinned_bytes = 4096;                                          // powers of two: few size classes in the pinned cache, whatever the files
-    const size_t bound = packed_scan_bound(len, P);
+    const size_t bound = packed_scan_bound(len, R->P);
     while (pinned_bytes < bound) pinned_bytes *= 2;
     if (cached_host_malloc(&pinned, pinned_bytes) != 0)
         return fail(IFHIP_ALLOCATION_FAILED, "AllocationFailed: %zu bytes of pinned staging", pinned_bytes);
     R->words = static_cast<uint32_t*>(pinned);                           // (R owns it from here: every return below releases it)
-    const uint32_t mcu0 = unstuff_scan_packed(file, len, P, reinterpret_cast<uint8_t*>(pinned), pinned_bytes, &R->seg);
-    const uint64_t subs = R->seg.n_sub;
-    if (subs * kSubBits + 4096 >= (1ull << 32)) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: more than 512 MB of scan data");
-    if (mcu0 < total_mcus)
-        return fail(IFHIP_INVALID_ARGUMENT, "ImageMalformed: scan of image %u ends after %u of %u MCUs", index_for_messages, mcu0, total_mcus);
-    R->n_words = static_cast<size_t>(subs) * kSubWords;
-    for (size_t q = 0; q < R->n_words; ++q) R->words[q] = __builtin_bswap32(R->words[q]);   // stream order bytes -> big-endian words
+    if (int rc = prepare_scan(R.get(), file, len, R->words, pinned_bytes, index_for_messages, &R->n_words)) return rc;
     *out = R.release();
     return IFHIP_OK;
 }
@@ -975,101 +739,30 @@ static int create_prepared_impl(ifhip_jpeg_entropy** out, ifhip_jpeg_prepared* c
     if (int arc = require_gfx950(&e->device)) return arc;
     e->n_images = n_images;
     e->qt.assign(static_cast<size_t>(n_images) * 192u, 0);
-    // The batch's tables -- segments, sub-sequence -> segment, three look-up tables and six search tables per image -- are laid
-    // out in ONE pinned staging block and go to ONE device block in one copy (they were six allocations and six uploads, each
-    // with its own wait for the stream: most of the 1.9 ms a 16-file batch spent here, profiles/r5_abi_jobs_cliff_7_decode_batches.txt).
-    size_t n_segs = 0;
-    uint64_t subs_in_batch = 0;
-    for (uint32_t img = 0; img < n_images; ++img) { n_segs += prep[img]->seg.nsub.size(); subs_in_batch += prep[img]->seg.n_sub; }
-    if (subs_in_batch * kSubBits + 4096 >= (1ull << 32)) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: batch holds more than 512 MB of scan data");
-    auto aligned = [](size_t v) { return (v + 255u) & ~static_cast<size_t>(255u); };
-    const size_t o_segs = 0, o_sub = aligned(o_segs + std::max<size_t>(n_segs, 1) * sizeof(Segment)),
-                 o_ftabs = aligned(o_sub + std::max<size_t>(subs_in_batch, 1) * sizeof(uint32_t)), o_ptabs = aligned(o_ftabs + n_images * sizeof(FastTabs)),
-                 o_ctabs = aligned(o_ptabs + n_images * sizeof(FastTabs)), o_stabs = aligned(o_ctabs + n_images * sizeof(FastTabs)),
-                 o_order = aligned(o_stabs + static_cast<size_t>(n_images) * 6u * sizeof(SearchTab)),
-                 table_bytes = aligned(o_order + ((subs_in_batch + kOwnSubs - 1u) / kOwnSubs + 1u) * sizeof(uint32_t));
+    // The batch's tables are laid out (plan_batch / fill_batch_tables, jpeg_entropy_plan.cpp) in ONE pinned staging block and go
+    // to ONE device block in one copy (they were six allocations and six uploads, each with its own wait for the stream: most of
+    // the 1.9 ms a 16-file batch spent here, profiles/r5_abi_jobs_cliff_7_decode_batches.txt).
+    const std::vector<const PreparedHost*> host(prep, prep + n_images);
+    BatchPlan plan;
+    if (int prc = plan_batch(host.data(), n_images, &plan)) return prc;
+    const size_t table_bytes = plan.table_bytes, n_words = plan.n_words;
     size_t stage_bytes = 4096;                                           // powers of two: few size classes in the pinned cache
     while (stage_bytes < table_bytes) stage_bytes *= 2;
     if (cached_host_malloc(reinterpret_cast<void**>(&e->h_tables), stage_bytes) != 0)
         return fail(IFHIP_ALLOCATION_FAILED, "AllocationFailed: %zu bytes of pinned staging", stage_bytes);
     uint8_t* const stage = e->h_tables;
-    Segment* const segs = reinterpret_cast<Segment*>(stage + o_segs);
-    uint32_t* const sub_seg = reinterpret_cast<uint32_t*>(stage + o_sub);
-    FastTabs* const ftabs = reinterpret_cast<FastTabs*>(stage + o_ftabs);
-    FastTabs* const ptabs = reinterpret_cast<FastTabs*>(stage + o_ptabs);
-    FastTabs* const ctabs = reinterpret_cast<FastTabs*>(stage + o_ctabs);
-    SearchTab* const stabs = reinterpret_cast<SearchTab*>(stage + o_stabs);
-    uint32_t* const wg_order = reinterpret_cast<uint32_t*>(stage + o_order);
-    std::vector<uint32_t> first_sub_of(n_images);
-    uint64_t total_subs = 0;
-    size_t seg_count = 0;
-    for (uint32_t img = 0; img < n_images; ++img) {
-        const ifhip_jpeg_prepared& R = *prep[img];
-        const ParsedJpeg& P = R.P;
-        if (img == 0) e->first = P;
-        else {
-            const ParsedJpeg& F = e->first;
-            bool same = P.width == F.width && P.height == F.height && P.ncomp == F.ncomp;
-            for (int c = 0; c < P.ncomp && same; ++c) same = P.hs[c] == F.hs[c] && P.vs[c] == F.vs[c];
-            if (!same) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: image %u differs in size or sampling from image 0 (one batch = one geometry)", img);
-        }
-        std::memcpy(&e->qt[static_cast<size_t>(img) * 192u], R.qt, sizeof R.qt);
-        std::memcpy(&ftabs[img], &R.ftabs, sizeof(FastTabs)); std::memcpy(&ptabs[img], &R.ptabs, sizeof(FastTabs)); std::memcpy(&ctabs[img], &R.ctabs, sizeof(FastTabs));
-        std::memcpy(&stabs[static_cast<size_t>(img) * 6u], R.stabs, sizeof R.stabs);
-        first_sub_of[img] = static_cast<uint32_t>(total_subs);
-        for (size_t k = 0; k < R.seg.nsub.size(); ++k) {
-            Segment sg;
-            std::memset(&sg, 0, sizeof sg);
-            sg.image = img;
-            sg.first_mcu = R.seg.mcu0[k];
-            sg.n_blocks = R.seg.mcus[k] * P.blocks_per_mcu;
-            sg.first_sub = static_cast<uint32_t>(total_subs);
-            sg.n_sub = R.seg.nsub[k];
-            sg.bit_end = static_cast<uint32_t>(total_subs * kSubBits + R.seg.bits[k]);
-            for (uint32_t q = 0; q < sg.n_sub; ++q) sub_seg[total_subs + q] = static_cast<uint32_t>(seg_count);
-            total_subs += sg.n_sub;
-            segs[seg_count++] = sg;
-        }
-    }
-    const size_t n_words = static_cast<size_t>(total_subs) * kSubWords + 64u;  // + lookahead slack behind the last segment
-    {   // dispatch order of the synchronisation launch (see entropy_round_kernel): blocks of the smallest scans first, an image's
-        // blocks in their own order
-        const uint32_t n_wg = static_cast<uint32_t>((total_subs + kOwnSubs - 1u) / kOwnSubs);
-        std::vector<uint32_t> key(n_wg);
-        uint32_t img = 0;
-        for (uint32_t w = 0; w < n_wg; ++w) {
-            const uint64_t s0 = static_cast<uint64_t>(w) * kOwnSubs;
-            while (img + 1u < n_images && first_sub_of[img + 1u] <= s0) ++img;
-            key[w] = static_cast<uint32_t>(prep[img]->seg.n_sub);
-            wg_order[w] = w;
-        }
-        std::stable_sort(wg_order, wg_order + n_wg, [&](uint32_t x, uint32_t y) { return key[x] < key[y]; });
-    }
-    const ParsedJpeg& F = e->first;
+    fill_batch_tables(host.data(), n_images, plan, stage);
+    e->first = prep[0]->P;
+    for (uint32_t img = 0; img < n_images; ++img) std::memcpy(&e->qt[static_cast<size_t>(img) * 192u], prep[img]->qt, sizeof prep[img]->qt);
     EntropyArgs& a = e->a;
     std::memset(&a, 0, sizeof a);
-    a.g.ncomp = static_cast<uint32_t>(F.ncomp); a.g.blocks_per_mcu = F.blocks_per_mcu; a.g.mcus_w = F.mcus_w; a.g.mcus_h = F.mcus_h;
-    uint32_t k = 0;
-    for (int c = 0; c < F.ncomp; ++c) {
-        a.g.bw[c] = F.bw[c]; a.g.bh[c] = F.bh[c]; a.g.hs[c] = F.hs[c]; a.g.vs[c] = F.vs[c];
-        for (uint32_t dy = 0; dy < F.vs[c]; ++dy)
-            for (uint32_t dx = 0; dx < F.hs[c]; ++dx, ++k) {
-                a.g.kcomp[k] = static_cast<uint8_t>(c); a.g.kdx[k] = static_cast<uint8_t>(dx); a.g.kdy[k] = static_cast<uint8_t>(dy);
-                a.g.kcomp_packed |= static_cast<uint32_t>(c) << (2u * k);
-            }
-    }
+    a.g = plan.g;
     a.inner_rounds = std::max<uint32_t>(1u, test_hook_u32("ent_test_inner", kInnerRounds, kInnerRounds));
-    a.n_sub = static_cast<uint32_t>(total_subs);
-    a.n_seg = static_cast<uint32_t>(seg_count);
-    a.uniform_tables = 1u;                           // batches of small files put many images into one workgroup: with
-    for (uint32_t img = 1; img < n_images && a.uniform_tables; ++img)     // identical tables they all use the LDS copy
-        if (std::memcmp(&ftabs[img], &ftabs[0], sizeof(FastTabs)) != 0 ||
-            std::memcmp(&stabs[static_cast<size_t>(img) * 6u], &stabs[0], 6u * sizeof(SearchTab)) != 0) a.uniform_tables = 0u;
+    a.n_sub = plan.total_subs;
+    a.n_seg = static_cast<uint32_t>(plan.n_segs);
+    a.uniform_tables = plan.uniform_tables;
     int rc;
-    uint32_t *d_words = nullptr, *d_sub = nullptr;
-    Segment* d_segs = nullptr;
-    FastTabs *d_ftabs = nullptr, *d_ptabs = nullptr, *d_ctabs = nullptr;
-    SearchTab* d_stabs = nullptr;
+    uint32_t* d_words = nullptr;
     if ((rc = dev_alloc<uint32_t>(e.get(), &d_words, n_words))) return rc;
     // From here on copies into `d_words` FROM the callers' pinned buffers may be queued on the thread's stream.  On any failure
     // below `e` is destroyed and its blocks go back to the cache -- inside an ABI job without a device-wide wait (QuiescedScope)
@@ -1084,7 +777,7 @@ static int create_prepared_impl(ifhip_jpeg_entropy** out, ifhip_jpeg_prepared* c
         for (uint32_t img = 0; img < n_images; ++img) {
             const ifhip_jpeg_prepared& R = *prep[img];
             if (!R.n_words) continue;
-            uint32_t* const dst = d_words + static_cast<size_t>(first_sub_of[img]) * kSubWords;
+            uint32_t* const dst = d_words + static_cast<size_t>(plan.first_sub_of[img]) * kSubWords;
             if (R.d_words && R.d_device == e->device) {              // its owner queued the upload already (ifhip_jpeg_prepared_upload): behind that copy, device to device
                 HIP_TRY(hipStreamWaitEvent(st, R.uploaded, 0));
                 HIP_TRY(hipMemcpyAsync(dst, R.d_words, R.n_words * sizeof(uint32_t), hipMemcpyDeviceToDevice, st));
@@ -1097,11 +790,11 @@ static int create_prepared_impl(ifhip_jpeg_entropy** out, ifhip_jpeg_prepared* c
     uint8_t* d_tables = nullptr;
     if ((rc = dev_alloc<uint8_t>(e.get(), &d_tables, table_bytes))) return rc;
     HIP_TRY(hipMemcpyAsync(d_tables, stage, table_bytes, hipMemcpyHostToDevice, drain.st));      // (the wait: StreamDrain, on every way out)
-    d_segs = reinterpret_cast<Segment*>(d_tables + o_segs); d_sub = reinterpret_cast<uint32_t*>(d_tables + o_sub);
-    d_ftabs = reinterpret_cast<FastTabs*>(d_tables + o_ftabs); d_ptabs = reinterpret_cast<FastTabs*>(d_tables + o_ptabs);
-    d_ctabs = reinterpret_cast<FastTabs*>(d_tables + o_ctabs); d_stabs = reinterpret_cast<SearchTab*>(d_tables + o_stabs);
-    a.wg_order = reinterpret_cast<const uint32_t*>(d_tables + o_order);
-    a.words = d_words; a.segs = d_segs; a.sub_seg = d_sub; a.ftabs = d_ftabs; a.ptabs = d_ptabs; a.ctabs = d_ctabs; a.stabs = d_stabs;
+    a.words = d_words;
+    a.segs = reinterpret_cast<const Segment*>(d_tables + plan.o_segs); a.sub_seg = reinterpret_cast<const uint32_t*>(d_tables + plan.o_sub);
+    a.ftabs = reinterpret_cast<const FastTabs*>(d_tables + plan.o_ftabs); a.ptabs = reinterpret_cast<const FastTabs*>(d_tables + plan.o_ptabs);
+    a.ctabs = reinterpret_cast<const FastTabs*>(d_tables + plan.o_ctabs); a.stabs = reinterpret_cast<const SearchTab*>(d_tables + plan.o_stabs);
+    a.wg_order = reinterpret_cast<const uint32_t*>(d_tables + plan.o_order);
     for (int b = 0; b < 2; ++b) {
         if ((rc = dev_alloc<uint32_t>(e.get(), &a.exit_p[b], a.n_sub))) return rc;
         if ((rc = dev_alloc<uint32_t>(e.get(), &a.exit_cz[b], a.n_sub))) return rc;
@@ -1166,9 +859,7 @@ int ifhip_jpeg_entropy_prepare(ifhip_jpeg_prepared** out, const uint8_t* jpeg, s
     if (!out) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null out-pointer");
     *out = nullptr;
     if (!jpeg) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null file");
-    try { return prepare_impl(out, jpeg, len, 0); }
-    catch (const std::bad_alloc&) { return fail(IFHIP_ALLOCATION_FAILED, "AllocationFailed: host memory while preparing the scan"); }
-    catch (const std::exception& ex) { return fail(IFHIP_INVALID_STATE, "InvalidState: %s", ex.what()); }
+    return c_entry(" while preparing the scan", [&] { return prepare_impl(out, jpeg, len, 0); });
 }
 void ifhip_jpeg_prepared_destroy(ifhip_jpeg_prepared* p) { give_prepared(p); }
 int ifhip_jpeg_prepared_upload(ifhip_jpeg_prepared* p, void* hip_stream) {
@@ -1202,162 +893,14 @@ int ifhip_jpeg_entropy_create_prepared(ifhip_jpeg_entropy** out, ifhip_jpeg_prep
     *out = nullptr;
     if (!prepared || n_images == 0) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: empty batch");
     for (uint32_t i = 0; i < n_images; ++i) if (!prepared[i]) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null prepared file %u", i);
-    try { return create_prepared_impl(out, prepared, n_images); }
-    catch (const std::bad_alloc&) { return fail(IFHIP_ALLOCATION_FAILED, "AllocationFailed: host memory while assembling the batch"); }
-    catch (const std::exception& ex) { return fail(IFHIP_INVALID_STATE, "InvalidState: %s", ex.what()); }
+    return c_entry(" while assembling the batch", [&] { return create_prepared_impl(out, prepared, n_images); });
 }
 
 void ifhip_jpeg_entropy_destroy(ifhip_jpeg_entropy* e) { delete e; }
 
 int ifhip_jpeg_entropy_create(ifhip_jpeg_entropy** out, const uint8_t* const* files, const size_t* lengths, uint32_t n_images) {
-    try {                                                   // nothing C++ crosses the C ABI
-        return entropy_create_impl(out, files, lengths, n_images);
-    } catch (const std::bad_alloc&) {
-        if (out) *out = nullptr;
-        return fail(IFHIP_ALLOCATION_FAILED, "AllocationFailed: host memory while preparing the batch");
-    } catch (const std::exception& ex) {
-        if (out) *out = nullptr;
-        return fail(IFHIP_INVALID_STATE, "InvalidState: %s", ex.what());
-    }
-}
-
-// ---- diagnostic (host only, no GPU): the tables and the scan layout of one file, checked against each other ------------
-// Everything the kernels rely on that can be checked without them: the two-level tables decode the scan to exactly the
-// blocks the geometry asks for (and to the DC values returned in dc_last: the caller compares them with a serial decoder's),
-// and a walk with the pair tables / the count tables passes through the same state at every sub-sequence boundary as the
-// plain walk -- the property that lets the synchronisation rounds, the count pass and the write pass hand states to
-// each other.  Host mirrors of long_entry / walk (same entry formats, same rules); nothing here produces coefficients.
-namespace {
-struct HostStream {
-    const std::vector<uint8_t>& b;
-    uint32_t peek(uint64_t p) const {                                // 32 bits behind bit position p, zero behind the end
-        uint64_t v = 0;
-        const size_t at = static_cast<size_t>(p >> 3);
-        for (size_t i = 0; i < 5; ++i) v = (v << 8) | (at + i < b.size() ? b[at + i] : 0u);
-        return static_cast<uint32_t>((v << (p & 7u)) >> 8);
-    }
-};
-uint32_t host_long_entry(const FastTabs& T, const SearchTab* S6, uint32_t slot, uint32_t e, uint32_t bits, int pairs) {
-    if (e != 0u) return T.pool[(e >> 16) + ((bits << kLutBits) >> ((e >> 8) & 255u))];
-    const SearchTab& t = S6[slot];
-    const bool ac = (slot & 1u) != 0u;
-    uint32_t l = kLutBits + 1u;
-    for (uint32_t k = kLutBits + 1u; k <= 16u; ++k) l += static_cast<int32_t>(bits >> (32u - k)) > t.maxcode[k] ? 1u : 0u;
-    uint32_t r = invalid_entry(ac);
-    if (l <= 16u) {
-        const uint32_t sym = t.val[(static_cast<int32_t>(bits >> (32u - l)) + t.valoff[l]) & 255];
-        if (ac || sym <= 11u) r = fast_entry(ac, l, sym);
-    }
-    return (pairs == 1 || (pairs == 2 && ac)) ? pair_entry(r, r) : r;
-}
-struct HostState { uint64_t p; uint32_t c, z; };
-struct HostCounts { uint64_t reads = 0, blocks = 0; int32_t dc[3] = {0, 0, 0}; bool bad = false; };
-// mirror of walk(): from state s to the first symbol boundary at or behind `end` (or until `max_blocks` blocks started)
-HostState host_walk(const EntropyGeom& g, const HostStream& in, const FastTabs& T, const SearchTab* S6, int pairs, HostState s, uint64_t end,
-                    uint64_t max_blocks, HostCounts* n) {
-    while (s.p < end) {
-        const uint32_t comp = (g.kcomp_packed >> (2u * s.c)) & 3u, slot = comp * 2u + (s.z ? 1u : 0u);
-        if (s.z == 0u && n->blocks >= max_blocks) break;             // pad bits behind the last block
-        const uint32_t bits = in.peek(s.p);
-        uint32_t e = T.lut[slot][bits >> (32u - kLutBits)];
-        if ((e & 255u) == 0u) e = host_long_entry(T, S6, slot, e, bits, pairs);
-        ++n->reads;
-        if (s.z == 0u) {
-            ++n->blocks;
-            if (pairs != 1) {                                        // DC entries are plain in the plain and the count tables
-                const uint32_t len = (e >> 16) & 255u, sz = (e >> 24) & 15u;
-                if (len > 16u) n->bad = true;
-                else if (sz) {
-                    const uint32_t v = (bits << len) >> (32u - sz);
-                    n->dc[comp] += static_cast<int32_t>(v) - ((v >> (sz - 1u)) ? 0 : static_cast<int32_t>((1u << sz) - 1u));
-                }
-            }
-        }
-        bool both = false;
-        if (pairs == 1 || (pairs == 2 && s.z != 0u)) both = s.z + ((e >> 8) & 255u) < 64u && s.p + (e & 255u) < end;
-        if (pairs == 0 && ((e >> 21) & 1u)) n->bad = true;
-        if (both) e >>= 16;
-        s.p += e & 255u;
-        s.z += (e >> 8) & 255u;
-        if (s.z >= 64u) { s.z = 0u; s.c = s.c + 1u == g.blocks_per_mcu ? 0u : s.c + 1u; }
-    }
-    return s;
-}
-}  // namespace
-
-int ifhip_jpeg_debug_scan_report(const uint8_t* jpeg, size_t len, ifhip_jpeg_scan_report* out) {
-    if (!jpeg || !out) return fail(IFHIP_INVALID_ARGUMENT, "InvalidArgument: null pointer");
-    try {
-        std::memset(out, 0, sizeof *out);
-        ParsedJpeg P;
-        if (int rc = parse_jpeg(jpeg, len, &P)) return rc;
-        auto F = std::make_unique<FastTabs>(), Pt = std::make_unique<FastTabs>(), Ct = std::make_unique<FastTabs>();
-        SearchTab S6[6];
-        const uint32_t pool_limit = test_hook_u32("ent_test_pool", kPoolEntries, kPoolEntries);
-        derive_image_tables(P, F.get(), S6, pool_limit, &out->pool_entries_used);
-        derive_pair_tables(*F, P.ncomp, Pt.get());
-        derive_count_tables(*F, *Pt, Ct.get());
-        out->pool_entries = kPoolEntries;
-        for (uint32_t slot = 0; slot < 2u * static_cast<uint32_t>(P.ncomp); ++slot)
-            for (uint32_t i = 0; i < kLutEntries; ++i) {
-                if (F->lut[slot][i] == 0u) ++out->prefixes_left_to_search;
-                if ((slot & 1u) && (Pt->lut[slot][i] >> 16) != (Pt->lut[slot][i] & 0xffffu)) ++out->pair_entries;
-            }
-        EntropyGeom g;
-        std::memset(&g, 0, sizeof g);
-        g.blocks_per_mcu = P.blocks_per_mcu;
-        uint32_t k = 0;
-        for (int c = 0; c < P.ncomp; ++c)
-            for (uint32_t b = 0; b < static_cast<uint32_t>(P.hs[c]) * P.vs[c]; ++b, ++k) g.kcomp_packed |= static_cast<uint32_t>(c) << (2u * k);
-        std::vector<std::vector<uint8_t>> seg_bytes;
-        ScanSegments seg, packed_seg;
-        const uint32_t covered = unstuff_scan(jpeg, len, P, &seg_bytes, &seg);
-        {   // the product's un-stuffer (straight into the staging block) against the walk above: same segments, same bytes, and
-            // -- under the sanitizer build, tools/sanitize -- never a byte beyond the bound the staging block is sized by
-            const size_t bound = packed_scan_bound(len, P);
-            std::unique_ptr<uint8_t[]> packed(new uint8_t[bound]);
-            const uint32_t p_covered = unstuff_scan_packed(jpeg, len, P, packed.get(), bound, &packed_seg);
-            bool same = p_covered == covered && packed_seg.mcu0 == seg.mcu0 && packed_seg.mcus == seg.mcus && packed_seg.bits.size() == seg_bytes.size();
-            for (size_t k = 0; same && k < seg_bytes.size(); ++k)
-                same = packed_seg.bits[k] == seg_bytes[k].size() * 8u &&
-                       std::memcmp(packed.get() + static_cast<size_t>(packed_seg.first_word[k]) * 4u, seg_bytes[k].data(), seg_bytes[k].size()) == 0;
-            if (!same) return fail(IFHIP_INVALID_STATE, "InvalidState: the packed un-stuffer disagrees with the per-segment walk");
-        }
-        out->segments = static_cast<uint32_t>(seg_bytes.size());
-        out->scan_complete = covered == P.mcus_w * P.mcus_h ? 1u : 0u;
-        for (size_t sgi = 0; sgi < seg_bytes.size(); ++sgi) {
-            const HostStream in{seg_bytes[sgi]};
-            const uint64_t bit_end = static_cast<uint64_t>(seg_bytes[sgi].size()) * 8u, want = static_cast<uint64_t>(seg.mcus[sgi]) * P.blocks_per_mcu;
-            const uint64_t n_sub = std::max<uint64_t>(1u, (bit_end + kSubBits - 1u) / kSubBits);
-            out->sub_sequences += static_cast<uint32_t>(n_sub);
-            HostCounts plain, paired, counted;
-            HostState s{0u, 0u, 0u};
-            for (uint64_t t = 0; t < n_sub; ++t) {                   // every sub-sequence from its true entry state, three ways
-                const uint64_t end = std::min<uint64_t>((t + 1u) * kSubBits, bit_end);
-                const HostState a0 = host_walk(g, in, *F, S6, 0, s, end, want, &plain);
-                const HostState a1 = host_walk(g, in, *Pt, S6, 1, s, end, want, &paired);
-                const HostState a2 = host_walk(g, in, *Ct, S6, 2, s, end, want, &counted);
-                if (a1.p != a0.p || a1.c != a0.c || a1.z != a0.z) ++out->pair_walk_mismatches;
-                if (a2.p != a0.p || a2.c != a0.c || a2.z != a0.z) ++out->count_walk_mismatches;
-                s = a0;
-            }
-            out->symbols += plain.reads;
-            out->table_reads_with_pairs += paired.reads;
-            out->blocks += plain.blocks;
-            if (plain.blocks != want) ++out->segments_with_wrong_block_count;
-            if (plain.bad) ++out->segments_with_invalid_codes;
-            for (int c = 0; c < 3; ++c) {
-                if (counted.dc[c] != plain.dc[c]) ++out->count_walk_mismatches;
-                out->dc_sum[c] += plain.dc[c];                       // (per segment the predictor restarts at 0: sums of the last segment
-                if (sgi + 1 == seg_bytes.size()) out->dc_last_segment[c] = plain.dc[c];        // give the last block's DC value)
-            }
-        }
-        return IFHIP_OK;
-    } catch (const std::bad_alloc&) {
-        return fail(IFHIP_ALLOCATION_FAILED, "AllocationFailed: host memory");
-    } catch (const std::exception& ex) {
-        return fail(IFHIP_INVALID_STATE, "InvalidState: %s", ex.what());
-    }
+    // (*out is null on every failure: entropy_create_impl clears it first and create_prepared_impl sets it as its last step)
+    return c_entry(" while preparing the batch", [&] { return entropy_create_impl(out, files, lengths, n_images); });
 }
 
 int ifhip_jpeg_entropy_info(const ifhip_jpeg_entropy* e, uint32_t* width, uint32_t* height, int* n_components, uint8_t* h_samp3,

@@ -1,5 +1,6 @@
-// jpeg_parse.hpp -- what the entropy stage (jpeg_entropy.hip) takes from the host front end of a baseline file (jpeg_parse.cpp):
-// the parsed headers and the scan's bytes, un-stuffed and cut at the restart markers.
+// jpeg_parse.hpp -- what the entropy stage (jpeg_entropy.hip; its host half: jpeg_entropy_tables.cpp, jpeg_entropy_plan.cpp,
+// jpeg_scan_report.cpp) takes from the host front end of a baseline file (jpeg_parse.cpp): the parsed headers and the scan's
+// bytes, un-stuffed and cut at the restart markers.
 #pragma once
 #include <vector>
 

@@ -11,18 +11,11 @@ INC="-I$ROOT/imageflow_amd/csrc -I$ROOT/include"
 SAN="-O1 -g -fsanitize=address,undefined -fno-sanitize-recover=undefined -std=c++17"
 g++ $SAN $INC -o writer_fuzz "$ROOT/tools/sanitize/writer_fuzz.cpp" "$ROOT/imageflow_amd/csrc/jpeg_write.cpp" "$ROOT/tools/sanitize/stubs.cpp"
 ./writer_fuzz
-# the JPEG front end (marker walk, parser, un-stuffing, EXIF, ICC: plain host code) and the entropy file's host half (tables,
-# host walkers): host-only compile of the .hip source; the device blob it would embed is an empty stand-in
+# the JPEG front end (marker walk, parser, un-stuffing, EXIF, ICC) and the entropy stage's host half (decode tables, host
+# walkers of the scan report): plain host code, one g++ line
 g++ $SAN $INC -c "$ROOT/imageflow_amd/csrc/jpeg_parse.cpp" -o jpeg_parse.o
-/opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 --cuda-host-only $SAN $INC -c "$ROOT/imageflow_amd/csrc/jpeg_entropy.hip" -o entropy_host.o 2>/dev/null
-SYM=$(nm entropy_host.o | awk '/__hip_fatbin_/ {print $2; exit}')
-printf '__attribute__((section(".hip_fatbin"))) const char %s[64] = {0};\n' "$SYM" > fatbin_stub.c
-gcc -c fatbin_stub.c -o fatbin_stub.o
-g++ $SAN $INC -c "$ROOT/tools/sanitize/parser_fuzz.cpp" -o parser_fuzz.o
 g++ $SAN -c "$ROOT/tools/sanitize/stubs.cpp" -o stubs.o
-# (the handles' memory comes from the library's cache: devmem.cpp, host-only like the rest; debug_switch lives in weights.cpp)
-/opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 --cuda-host-only $SAN $INC -c "$ROOT/imageflow_amd/csrc/devmem.cpp" -o devmem_host.o 2>/dev/null
-/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o parser_fuzz parser_fuzz.o jpeg_parse.o entropy_host.o devmem_host.o stubs.o fatbin_stub.o -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lpthread
+g++ $SAN $INC -o parser_fuzz "$ROOT/tools/sanitize/parser_fuzz.cpp" jpeg_parse.o "$ROOT/imageflow_amd/csrc/jpeg_entropy_tables.cpp" "$ROOT/imageflow_amd/csrc/jpeg_scan_report.cpp" stubs.o
 python3 - "$ROOT" <<'PY'
 import sys, numpy as np
 z = np.load(sys.argv[1] + "/tests/golden/jpeg_entropy_cases.npz")
@@ -33,7 +26,7 @@ ASAN_OPTIONS=detect_leaks=0 ./parser_fuzz case_*.jpg
 # the WebP decoder's host side: container walk, prepare and the token loop on mutated copies of the tests' files
 /opt/rocm/bin/hipcc -x hip --offload-arch=gfx950 --cuda-host-only $SAN $INC -c "$ROOT/imageflow_amd/csrc/webp_read.cpp" -o webp_read_host.o 2>/dev/null
 g++ $SAN -fno-sanitize=vptr $INC -c "$ROOT/tools/sanitize/webp_fuzz.cpp" -o webp_fuzz.o      # (vptr: g++ and the clang runtime that links disagree on it)
-/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o webp_fuzz webp_fuzz.o webp_read_host.o jpeg_parse.o entropy_host.o devmem_host.o stubs.o fatbin_stub.o -L/opt/rocm/lib -lamdhip64 -Wl,-rpath,/opt/rocm/lib -lpthread
+/opt/rocm/lib/llvm/bin/clang++ -fsanitize=address,undefined -o webp_fuzz webp_fuzz.o webp_read_host.o jpeg_parse.o stubs.o -lpthread
 (cd "$ROOT" && python3 - <<'PY'
 from tests import webp_decode_fixtures as X
 files = X.good_files()
