@@ -72,6 +72,10 @@ def _bind():
     L.ifhip_shim_context_device.restype = C.c_int
     L.ifhip_shim_context_set_color_management.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_color_management.restype = C.c_bool
+    L.ifhip_shim_context_set_color_profile_kinds.argtypes = [vp, C.c_uint32]
+    L.ifhip_shim_context_set_color_profile_kinds.restype = C.c_bool
+    L.ifhip_shim_color_links_built.argtypes = [vp]
+    L.ifhip_shim_color_links_built.restype = C.c_int64
     L.ifhip_shim_context_set_webp_lossy_decoder.argtypes = [vp, C.c_int]
     L.ifhip_shim_context_set_webp_lossy_decoder.restype = C.c_bool
     L.ifhip_shim_context_set_device_progressive_decoder.argtypes = [vp, C.c_int]
@@ -222,6 +226,15 @@ class Context:
         behind its decode, instead of refusing the job (the decoder command "convert_color_profile" does it for one input;
         "discard_color_profile" wins over both)."""
         return self.L.ifhip_shim_context_set_color_management(self.p, 1 if on else 0)
+
+    def set_color_profile_kinds(self, gray=False, lut=False):
+        """EXTENSION, both off by default: where colour management acts, also convert grey frames with a GRAY profile (`gray`) and
+        frames with a LUT-based RGB profile (`lut`, A2B0) through a colour link, instead of refusing them."""
+        return self.L.ifhip_shim_context_set_color_profile_kinds(self.p, (1 if gray else 0) | (2 if lut else 0))
+
+    def color_links_built(self):
+        """Diagnostic: colour links this context's jobs built from profile bytes (a profile met again comes from the cache)."""
+        return self.L.ifhip_shim_color_links_built(self.p)
 
     def set_webp_lossy_decoder(self, on):
         """EXTENSION, off by default: lossy WebP inputs (`VP8 `, with or without `ALPH`) are decoded on the device to exactly

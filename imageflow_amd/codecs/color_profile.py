@@ -2,8 +2,10 @@
 (codecs/lcms2_transform.rs): a source's colour profile as a plan (csrc/color_profile.cpp) and the conversion of device-resident
 Bitmaps to sRGB in place (csrc/color_profile.hip, ifhip_color_transform_batch_device).
 
-Converted: RGB matrix/TRC ICC profiles (v2 / v4, XYZ connection space) and PNG gAMA + cHRM.  Not converted (a FlowError that
-names the case): GRAY and CMYK spaces, a Lab connection space, LUT-based profiles; PNG cICP is not read at all."""
+Converted by a plan: RGB matrix/TRC ICC profiles (v2 / v4, XYZ connection space) and PNG gAMA + cHRM.  Converted by a link
+(ColorLink below; csrc/color_link.cpp, csrc/color_link.hip): GRAY profiles with a tone curve on grey frames, and RGB profiles
+that carry A2B0 (lut8 / lut16 with an XYZ connection space, lutAToB with XYZ or Lab).  Not converted (a FlowError that names
+the case): CMYK, grey LUTs, lut8 / lut16 with a Lab connection space, D2B0; PNG cICP is not read at all."""
 import ctypes as C
 
 import numpy as np
@@ -38,6 +40,14 @@ def _bind():
     L.ifhip_color_plan_status_text.restype = C.c_char_p
     L.ifhip_color_transform_batch_device.argtypes = [C.c_void_p, C.c_size_t, _u32, _u32, _u32, _u32, C.POINTER(ColorPlan), C.c_void_p]
     L.ifhip_color_transform.argtypes = [C.c_void_p, _u32, _u32, _u32, C.POINTER(ColorPlan)]
+    vp = C.c_void_p
+    L.ifhip_color_link_from_icc.argtypes = [C.c_char_p, C.c_size_t, C.c_int, C.POINTER(vp)]
+    L.ifhip_color_link_free.argtypes = [vp]
+    L.ifhip_color_link_free.restype = None
+    L.ifhip_color_link_kind.argtypes = [vp]
+    L.ifhip_color_link_copy_nodes.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+    L.ifhip_color_link_transform.argtypes = [vp, _u32, _u32, _u32, vp]
+    L.ifhip_color_link_transform_batch_device.argtypes = [vp, C.c_size_t, _u32, _u32, _u32, _u32, vp, vp]
     L._color_profile_bound = True
     return L
 
@@ -92,4 +102,67 @@ def transform_to_srgb_host(rows, w, plan: ColorPlan):
     """Host-buffer drop-in (numpy): uint8 rows [h, stride], converted in place through the device."""
     assert rows.dtype == np.uint8 and rows.ndim == 2 and rows.flags.c_contiguous
     _native.check(_bind().ifhip_color_transform(rows.ctypes.data, w, rows.shape[0], rows.shape[1], C.byref(plan)))
+    return rows
+
+
+# ---- colour links: GRAY and LUT-based profiles (include/imageflow_hip_color_link.h) ------------------------------------------
+LINK_GRAY, LINK_RGB, LINK_GRID = 1, 2, 33
+
+
+class ColorLink:
+    """ifhip_color_link: a grey table (256 bytes) or an RGB device link (33^3 nodes) built from a profile's bytes; its device copy
+    is made by the first conversion that needs it.  close() (or the collector) frees it after a wait for the device."""
+
+    def __init__(self, handle):
+        self.p = handle
+
+    @property
+    def kind(self):
+        return _bind().ifhip_color_link_kind(self.p)
+
+    def nodes(self):
+        """uint8 [256] for a grey table; uint16 [33, 33, 33, 3] indexed [r][g][b] -> (R, G, B) for an RGB link"""
+        gray = self.kind == LINK_GRAY
+        out = np.zeros(256, np.uint8) if gray else np.zeros((LINK_GRID,) * 3 + (3,), np.uint16)
+        written = C.c_size_t(0)
+        _native.check(_bind().ifhip_color_link_copy_nodes(self.p, out.ctypes.data, out.nbytes, C.byref(written)))
+        assert written.value == out.nbytes
+        return out
+
+    def close(self):
+        if self.p:
+            _bind().ifhip_color_link_free(self.p)
+            self.p = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def try_link_from_icc(icc, frame_is_gray=False):
+    """-> (status, ColorLink or None, the message that names the case)"""
+    icc = bytes(icc)
+    handle = C.c_void_p()
+    status = _bind().ifhip_color_link_from_icc(icc, len(icc), 1 if frame_is_gray else 0, C.byref(handle))
+    return status, (ColorLink(handle) if status == PLANNED else None), ("" if status == PLANNED else _last_error())
+
+
+def link_from_icc(icc, frame_is_gray=False):
+    return _or_raise(*try_link_from_icc(icc, frame_is_gray))
+
+
+def link_to_srgb(b: Bitmap, link: ColorLink):
+    """Queue the conversion of every frame of the batch through the link on the current stream, in place; alpha bytes keep their
+    values; a grey table reads the B byte."""
+    with torch.cuda.device(b.data.device):
+        st = C.c_void_p(torch.cuda.current_stream(b.data.device).cuda_stream)
+        _native.check(_bind().ifhip_color_link_transform_batch_device(b.data.data_ptr(), b.image_bytes, b.n, b.w, b.h, b.stride, link.p, st))
+
+
+def link_to_srgb_host(rows, w, link: ColorLink):
+    """Host-buffer drop-in (numpy): uint8 rows [h, stride], converted in place through the device."""
+    assert rows.dtype == np.uint8 and rows.ndim == 2 and rows.flags.c_contiguous
+    _native.check(_bind().ifhip_color_link_transform(rows.ctypes.data, w, rows.shape[0], rows.shape[1], link.p))
     return rows

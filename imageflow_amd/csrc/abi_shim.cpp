@@ -343,6 +343,19 @@ bool ifhip_shim_context_set_color_management(struct imageflow_context* c, int on
     c->color_management.store(on != 0, std::memory_order_relaxed);
     return true;
 }
+// EXTENSION: GRAY profiles on grey frames and LUT-based RGB profiles are converted too, by a colour link (see Job::color_plan_for);
+// 0 by default.  Acts only where colour management acts.  An unknown bit is refused.  The getter: links built from profile
+// bytes by this context's jobs -- a profile met again is served from the context's cache.
+bool ifhip_shim_context_set_color_profile_kinds(struct imageflow_context* c, uint32_t flags) {
+    CTX_OR_ABORT(c);
+    if (flags & ~(IFHIP_COLOR_KIND_GRAY | IFHIP_COLOR_KIND_LUT)) return false;
+    c->color_profile_kinds.store(flags, std::memory_order_relaxed);
+    return true;
+}
+int64_t ifhip_shim_color_links_built(struct imageflow_context* c) {
+    CTX_OR_ABORT(c);
+    return c->color_links_built.load(std::memory_order_relaxed);
+}
 // EXTENSION: the libjpeg_turbo preset's progressive / optimize_huffman_coding files are entropy-coded on the device
 // (ifhip_jpeg_encode_flags_batch_device) instead of by the host writer; off by default.  The files are the same bytes.
 // EXTENSION: the presets `auto` and `format` of `encode`, and the output keys of a command_string's querystring, come to the

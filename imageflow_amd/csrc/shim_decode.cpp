@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/imageflow_hip_jpeg_progressive.h"   // the device entropy decoder of progressive files (jpeg_progressive_decode.hip)
+#include "color_link.hpp"      // a GRAY or LUT-based profile as a link (color_link.cpp; the kernels: color_link.hip)
 #include "color_profile.hpp"   // a colour profile as a conversion plan (color_profile.cpp; the kernel: color_profile.hip)
 #include "png_read.hpp"         // the PNG chunk walk and the device decode of a walked file (png_read.cpp, png_decode.hip)
 #include "gif_read.hpp"         // the container walk and the device decode of a GIF (gif_read.cpp, gif_decode.hip)
@@ -336,32 +337,82 @@ void Job::image_size(int32_t io_id, uint32_t* w, uint32_t* h, bool rotated) {
 // the refusal; a malformed one is ErrorKind::ColorProfileError (category ImageMalformed, errors.rs:241), which
 // ignore_color_profile_errors swallows as the reference does for every failure of its transform
 // (mozjpeg_decoder.rs:409-415, libpng_decoder.rs:376-382): the samples stay as they are.
-bool Job::color_plan_for(int32_t io_id, const Io& in, const char* what, const char* reference_line, const uint8_t* icc, size_t icc_len,
-                    const uint32_t* gama_chrm, ifhip_color_plan* plan) {
+void Job::color_plan_for(int32_t io_id, const Io& in, const char* what, const char* reference_line, const uint8_t* icc, size_t icc_len,
+                         const uint32_t* gama_chrm, bool frame_is_gray, ColorRoute* route) {
     if (!c->color_management.load(std::memory_order_relaxed) && !in.told_convert_profile)
         raise(kActionNotSupported, "ActionNotSupported: io_id %d %s; this build has no colour management%s%s%s.  Tell the decoder "
               "\"discard_color_profile\" to decode the samples as they are, or keep the file on the reference.  (Conversion to sRGB on the device is an "
               "extension that is off by default: ifhip_shim_context_set_color_management, or the decoder command \"convert_color_profile\", switches it on.)",
               io_id, what, reference_line ? " (the reference converts such frames to sRGB, " : "", reference_line ? reference_line : "", reference_line ? ")" : "");
     ifhip::ColorPlanResult r;
-    if (icc) r = ifhip::color_plan_from_icc(icc, icc_len, plan);
+    if (icc) r = ifhip::color_plan_from_icc(icc, icc_len, &route->plan);
     else {
         double xy[8];
         for (int k = 0; k < 8; ++k) xy[k] = gama_chrm[1 + k] / 100000.0;
-        r = ifhip::color_plan_from_gamma_primaries(gama_chrm[0] / 100000.0, xy, plan);
+        r = ifhip::color_plan_from_gamma_primaries(gama_chrm[0] / 100000.0, xy, &route->plan);
     }
-    if (r.status == IFHIP_COLOR_PLANNED) return true;
-    if (r.status == IFHIP_COLOR_NOT_CONVERTIBLE)
+    if (r.status == IFHIP_COLOR_PLANNED) { route->convert = true; return; }
+    // EXTENSION ifhip_shim_context_set_color_profile_kinds: the second route, for what the planner turns away.  The profile's
+    // colour space picks the flag: GRAY profiles (a table) under _GRAY, everything else that may carry A2B0 under _LUT
+    const uint32_t kinds = c->color_profile_kinds.load(std::memory_order_relaxed);
+    const bool gray_space = icc && icc_len >= 20u && std::memcmp(icc + 16, "GRAY", 4) == 0;
+    const bool linked = icc && r.status == IFHIP_COLOR_NOT_CONVERTIBLE && (kinds & (gray_space ? IFHIP_COLOR_KIND_GRAY : IFHIP_COLOR_KIND_LUT)) != 0u;
+    if (linked) {
+        const char* reason = "";
+        int status = r.status;
+        route->link = color_link_for(icc, icc_len, frame_is_gray, &status, &reason);
+        if (route->link) { route->convert = true; return; }
+        if (!std::strstr(reason, "without A2B0")) { r.status = status; r.reason = reason; }     // (a matrix/TRC profile: the planner's own reason stands)
+    }
+    if (r.status == IFHIP_COLOR_NOT_CONVERTIBLE) {
+        if (linked)
+            raise(kActionNotSupported, "ActionNotSupported: io_id %d %s, and the profile is %s: %s (matrix/TRC RGB profiles, gAMA + cHRM%s%s are converted; "
+                  "CMYK, %s%scurves that lift black on the matrix route are not).  Tell the decoder \"discard_color_profile\" to decode the samples as they are, or keep the "
+                  "file on the reference.", io_id, what, ifhip::color_plan_status_text(r.status), r.reason,
+                  (kinds & IFHIP_COLOR_KIND_GRAY) ? ", GRAY profiles with a tone curve" : "", (kinds & IFHIP_COLOR_KIND_LUT) ? ", RGB profiles with A2B0" : "",
+                  (kinds & IFHIP_COLOR_KIND_GRAY) ? "" : "GRAY, ", (kinds & IFHIP_COLOR_KIND_LUT) ? "" : "Lab and LUT-based profiles, ");
         raise(kActionNotSupported, "ActionNotSupported: io_id %d %s, and the profile is %s: %s (matrix/TRC RGB profiles and gAMA + cHRM are converted; GRAY, "
               "CMYK, Lab and LUT-based profiles and curves that lift black are not).  Tell the decoder \"discard_color_profile\" to decode the samples as they are, or keep the file on "
               "the reference.", io_id, what, ifhip::color_plan_status_text(r.status), r.reason);
-    if (in.told_ignore_profile_errors) return false;
+    }
+    if (in.told_ignore_profile_errors) return;
     raise(kImageMalformed, "ColorProfileError: the colour profile of io_id %d is %s: %s.  Tell the decoder \"ignore_color_profile_errors\" to decode the "
           "samples as they are.", io_id, ifhip::color_plan_status_text(r.status), r.reason);
 }
-// in place, on the job's stream, behind the decode that filled the frame; the plan is copied by the launch
-void Job::convert_to_srgb(const FramePtr& f, const ifhip_color_plan& plan) {
-    check(ifhip_color_transform_batch_device(dev(f), f->bytes(), 1, f->w, f->h, f->stride, &plan, t_job_stream));
+// The context's link for these profile bytes: from its cache, or built now (host only; the device copy is made by the first
+// launch).  Null: *status and *reason say why.
+std::shared_ptr<ifhip_color_link> Job::color_link_for(const uint8_t* icc, size_t icc_len, bool frame_is_gray, int* status, const char** reason) {
+    uint64_t hash = 1469598103934665603ull;                                     // FNV-1a
+    for (size_t i = 0; i < icc_len; ++i) hash = (hash ^ icc[i]) * 1099511628211ull;
+    ColorLinkCache& cache = c->color_links;
+    std::lock_guard<std::mutex> lock(cache.mu);
+    for (ColorLinkCache::Entry& e : cache.entries)
+        if (e.hash == hash && e.len == icc_len && e.gray == frame_is_gray) { e.used = ++cache.clock; *status = IFHIP_COLOR_PLANNED; return e.link; }
+    ifhip_color_link* raw = nullptr;
+    *status = ifhip_color_link_from_icc(icc, icc_len, frame_is_gray ? 1 : 0, &raw);
+    if (*status != IFHIP_COLOR_PLANNED || !raw) {                               // the builder once more for its reason: it gives up before it samples
+        ifhip::ColorLink none;
+        const ifhip::ColorPlanResult r = ifhip::color_link_from_icc(icc, icc_len, frame_is_gray, &none);
+        *status = r.status == IFHIP_COLOR_PLANNED ? IFHIP_COLOR_MALFORMED : r.status;
+        *reason = r.status == IFHIP_COLOR_PLANNED ? "the link could not be allocated" : r.reason;
+        return nullptr;
+    }
+    c->color_links_built.fetch_add(1, std::memory_order_relaxed);
+    std::shared_ptr<ifhip_color_link> link(raw, ifhip_color_link_free);
+    if (cache.entries.size() >= ColorLinkCache::kMax) {
+        size_t oldest = 0;
+        for (size_t i = 1; i < cache.entries.size(); ++i)
+            if (cache.entries[i].used < cache.entries[oldest].used) oldest = i;
+        cache.entries.erase(cache.entries.begin() + static_cast<std::ptrdiff_t>(oldest));
+    }
+    cache.entries.push_back({hash, icc_len, frame_is_gray, link, ++cache.clock});
+    return link;
+}
+// in place, on the job's stream, behind the decode that filled the frame; the plan is copied by the launch, the link outlives
+// it (the cache's share, and ifhip_color_link_free's wait for the device)
+void Job::convert_to_srgb(const FramePtr& f, const ColorRoute& route) {
+    if (route.link) check(ifhip_color_link_transform_batch_device(dev(f), f->bytes(), 1, f->w, f->h, f->stride, route.link.get(), t_job_stream));
+    else check(ifhip_color_transform_batch_device(dev(f), f->bytes(), 1, f->w, f->h, f->stride, &route.plan, t_job_stream));
 }
 
 // LibPngDecoder::read_frame (codecs/libpng_decoder.rs:82-104 -> c_components/lib/codec_png_wrapper.c:131-246) on the device:
@@ -374,14 +425,14 @@ FramePtr Job::decode_png(int32_t io_id, Io& in) {
     // The colour policy of the JPEG path below (DESIGN 8 "Colour management"): the reference transforms a frame whose iCCP,
     // or gAMA + cHRM, is not sRGB (libpng_decoder.rs:340-383); so does this build once switched on, else it refuses -- never
     // other colours.
-    ifhip_color_plan color_plan;
-    bool convert = false;
+    ColorRoute route;
     if (!in.told_discard_profile && P.color_kind == 2) {
         static const uint8_t kNoProfile = 0;                                      // an iCCP that did not inflate: zero bytes of profile, malformed
         uint32_t gama_chrm[9] = {P.gama};
         std::memcpy(gama_chrm + 1, P.chrm, sizeof P.chrm);
-        convert = color_plan_for(io_id, in, P.has_iccp ? "carries an embedded ICC profile that is not sRGB" : "carries gAMA and cHRM chunks that do not describe sRGB",
-                                 "codecs/libpng_decoder.rs:376", P.has_iccp ? (P.icc.empty() ? &kNoProfile : P.icc.data()) : nullptr, P.icc.size(), gama_chrm, &color_plan);
+        color_plan_for(io_id, in, P.has_iccp ? "carries an embedded ICC profile that is not sRGB" : "carries gAMA and cHRM chunks that do not describe sRGB",
+                       "codecs/libpng_decoder.rs:376", P.has_iccp ? (P.icc.empty() ? &kNoProfile : P.icc.data()) : nullptr, P.icc.size(), gama_chrm,
+                       P.color_type == 0u || P.color_type == 4u, &route);
     }
     if (P.inflated > 0x7FFF0000ull) raise(kImageMalformed, "ImageMalformed: LibPNG error: the image data of io_id %d would inflate beyond 2^31 bytes", io_id);
     FramePtr f = new_frame(P.w, P.h, P.alpha_used, 0, true);                      // (max_frame_size inside)
@@ -389,7 +440,7 @@ FramePtr Job::decode_png(int32_t io_id, Io& in) {
     const size_t bytes = f->bytes();
     const uint32_t status = decoded_status("decode(png)", [&](uint32_t* d_status) { return ifhip::png_decode_parsed_device(&parsed, 1, &f->d, &bytes, &f->stride, d_status, t_job_stream); });
     if (status) raise(kImageMalformed, "ImageMalformed: LibPNG error: %s (io_id %d, status %u)", ifhip::png_status_text(status), io_id, status);
-    if (convert) convert_to_srgb(f, color_plan);
+    if (route.convert) convert_to_srgb(f, route);
     decodes.push_back({io_id, P.w, P.h, "image/png", "png"});
     return f;
 }
@@ -402,9 +453,9 @@ FramePtr Job::decode_webp(int32_t io_id, Io& in) {
     ifhip::WebpParsed P;
     walk_webp(in, &P, c->webp_lossy_decoder.load(std::memory_order_relaxed));
     check_size(sec.max_decode_size, "max_decode_size", P.w, P.h);                 // on the header, before anything is staged
-    ifhip_color_plan color_plan;
-    const bool convert = !in.told_discard_profile && P.color_kind == 2 &&
-                         color_plan_for(io_id, in, "carries an embedded ICC profile that is not sRGB", nullptr, P.icc, P.icc_len, nullptr, &color_plan);
+    ColorRoute route;
+    if (!in.told_discard_profile && P.color_kind == 2)
+        color_plan_for(io_id, in, "carries an embedded ICC profile that is not sRGB", nullptr, P.icc, P.icc_len, nullptr, false, &route);
     if (in.told_webp && (in.told_webp_w != P.w || in.told_webp_h != P.h))
         raise(kActionNotSupported, "ActionNotSupported: webp_decoder_hints %ux%u for io_id %d (%ux%u): libwebp's decode-time rescaler is not built "
               "(the reference shrinks during the decode, codecs/webp.rs:181-188); decode at full size and resample", in.told_webp_w, in.told_webp_h, io_id, P.w, P.h);
@@ -430,7 +481,7 @@ FramePtr Job::decode_webp(int32_t io_id, Io& in) {
         if (status) status_text = ifhip::webp_status_text(status);
     }
     if (status) raise(kImageMalformed, "ImageMalformed: libwebp decoding error %s (io_id %d, status %u)", status_text, io_id, status);
-    if (convert) convert_to_srgb(f, color_plan);
+    if (route.convert) convert_to_srgb(f, route);
     decodes.push_back({io_id, P.w, P.h, "image/webp", "webp"});
     return f;
 }
@@ -495,8 +546,7 @@ FramePtr Job::decode(int32_t io_id, uint32_t hint_w, uint32_t hint_h, bool luma_
         image_size(io_id, &hw, &hh);
         check_size(sec.max_decode_size, "max_decode_size", hw, hh);
     }
-    ifhip_color_plan color_plan;
-    bool convert = false;
+    ColorRoute route;
     {   // MzDec::read_frame transforms the frame to sRGB whenever the file carries an ICC profile (mozjpeg_decoder.rs:370-420)
         // unless the decoder was told discard_color_profile (:88-91).  A profile that is not sRGB itself would come out with
         // other colours than the reference's: the job is refused -- loudly -- unless colour management is switched on, and
@@ -504,8 +554,14 @@ FramePtr Job::decode(int32_t io_id, uint32_t hint_w, uint32_t hint_h, bool luma_
         // to its rounding).
         int kind = 0;
         std::vector<uint8_t> icc;
-        if (!in.told_discard_profile && ifhip::jpeg_icc_profile(in.in, in.in_len, &kind, &icc) == IFHIP_OK && kind == 2)
-            convert = color_plan_for(io_id, in, "carries an embedded ICC profile that is not sRGB", "codecs/mozjpeg_decoder.rs:409", icc.data(), icc.size(), nullptr, &color_plan);
+        if (!in.told_discard_profile && ifhip::jpeg_icc_profile(in.in, in.in_len, &kind, &icc) == IFHIP_OK && kind == 2) {
+            uint32_t fw = 0, fh = 0, bw[3], bh[3];                                    // a one-component file is a grey frame (mozjpeg_decoder.rs:387-404)
+            int nc = 0, progressive = 0;
+            uint8_t hs3[3], vs3[3];
+            uint16_t qt[192];
+            const bool gray = ifhip_jpeg_frame_info(in.in, in.in_len, &fw, &fh, &nc, hs3, vs3, bw, bh, qt, &progressive) == IFHIP_OK && nc == 1;
+            color_plan_for(io_id, in, "carries an embedded ICC profile that is not sRGB", "codecs/mozjpeg_decoder.rs:409", icc.data(), icc.size(), nullptr, gray, &route);
+        }
     }
     // the entropy stage: this file, together with whatever other threads' jobs want decoded right now (DecodeCoalescer)
     DecodeRequest rq;
@@ -565,7 +621,7 @@ FramePtr Job::decode(int32_t io_id, uint32_t hint_w, uint32_t hint_h, bool luma_
     if (!lazy_decode) (void)dev(f);                                               // several consumers: one bitmap for all of them
     // a frame to convert never takes the fused decode + resample call, which forms no BGRA frame: its pixel stage runs now
     // (dev), then the conversion; whoever resamples it -- a node, a command_string, a watermark -- finds an ordinary frame
-    if (convert) convert_to_srgb(f, color_plan);
+    if (route.convert) convert_to_srgb(f, route);
     {   // Context::get_image_decodes reports get_unscaled_rotated_image_info (context.rs:519-538)
         const int flag = exif_flag(in);
         const bool swap = flag >= 5 && flag <= 8;

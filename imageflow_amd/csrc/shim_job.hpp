@@ -16,6 +16,7 @@
 
 #include "../../include/imageflow_abi_subset.h"
 #include "../../include/imageflow_hip.h"
+#include "../../include/imageflow_hip_color_link.h"
 #include "common.hpp"           // the library's per-job memory cache and thread stream (devmem.cpp)
 #include "encoder_select.hpp"   // which coder the presets `auto` and `format` come to (encoder_select.cpp; host only)
 #include "shim_json.hpp"
@@ -140,6 +141,19 @@ struct Response {
 };
 }  // namespace ifshim
 
+namespace ifshim {
+// The colour links of one context (csrc/color_link.hip), as the reference caches its lcms2 transforms by a hash of the profile
+// (codecs/lcms2_transform.rs:124-136).  At most kMax entries, the least recently used goes; a job keeps its links alive by the
+// shared pointers it holds.  Freed with the context.
+struct ColorLinkCache {
+    static constexpr size_t kMax = 8;
+    struct Entry { uint64_t hash; size_t len; bool gray; std::shared_ptr<ifhip_color_link> link; uint64_t used; };
+    std::mutex mu;
+    std::vector<Entry> entries;
+    uint64_t clock = 0;
+};
+}  // namespace ifshim
+
 struct imageflow_json_response {                 // opaque to callers; read through imageflow_json_response_read
     ifshim::Response r;
 };
@@ -170,6 +184,9 @@ struct imageflow_context {
     std::atomic<bool> webp_lossy_encoder{false};         // EXTENSION ifhip_shim_context_set_webp_lossy_encoder: the "webplossy" preset writes a lossy WebP on the device
     std::atomic<bool> encoder_selection{false};          // EXTENSION ifhip_shim_context_set_encoder_selection: the presets `auto` / `format` and the querystring's output keys pick a coder
     std::atomic<bool> color_management{false};           // EXTENSION ifhip_shim_context_set_color_management: every input is converted to sRGB
+    std::atomic<uint32_t> color_profile_kinds{0};        // EXTENSION ifhip_shim_context_set_color_profile_kinds: IFHIP_COLOR_KIND_GRAY | _LUT profiles are converted too
+    std::atomic<int64_t> color_links_built{0};           // ... links built from profile bytes by this context's jobs (a cached link is not built again)
+    ifshim::ColorLinkCache color_links;                  // ... the links, by a hash of the profile's bytes and the grey flag
     bool cancellation_requested() {
         if (cancel.load(std::memory_order_relaxed)) return true;
         if (poll_countdown.load(std::memory_order_relaxed) == INT64_MAX) return false;
@@ -282,9 +299,15 @@ struct Job {
     static void walk_webp(const Io& in, ifhip::WebpParsed* P, bool lossy_decoder);
     static int exif_flag(const Io& in);
     void image_size(int32_t io_id, uint32_t* w, uint32_t* h, bool rotated = false);
-    bool color_plan_for(int32_t io_id, const Io& in, const char* what, const char* reference_line, const uint8_t* icc, size_t icc_len,
-                        const uint32_t* gama_chrm, ifhip_color_plan* plan);
-    void convert_to_srgb(const FramePtr& f, const ifhip_color_plan& plan);
+    struct ColorRoute {                                              // how a decoded frame comes to sRGB: not at all, by a plan, or by a link
+        bool convert = false;
+        ifhip_color_plan plan;
+        std::shared_ptr<ifhip_color_link> link;                      // set: the link converts, the plan is not filled
+    };
+    void color_plan_for(int32_t io_id, const Io& in, const char* what, const char* reference_line, const uint8_t* icc, size_t icc_len,
+                        const uint32_t* gama_chrm, bool frame_is_gray, ColorRoute* route);
+    std::shared_ptr<ifhip_color_link> color_link_for(const uint8_t* icc, size_t icc_len, bool frame_is_gray, int* status, const char** reason);
+    void convert_to_srgb(const FramePtr& f, const ColorRoute& route);
     FramePtr decode_png(int32_t io_id, Io& in);
     FramePtr decode_webp(int32_t io_id, Io& in);
     FramePtr decode_gif(int32_t io_id, Io& in);

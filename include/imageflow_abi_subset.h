@@ -128,6 +128,21 @@ IMAGEFLOW_SHIM_API int ifhip_shim_context_device(struct imageflow_context *conte
  * cHRM.  Still refused, naming the case: GRAY / CMYK spaces, a Lab PCS, LUT-based profiles.  A malformed profile is a
  * ColorProfileError (ImageMalformed) unless the decoder was told "ignore_color_profile_errors".  Returns true. */
 IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_color_management(struct imageflow_context *context, int on);
+/* EXTENSION.  The profile kinds colour management converts beyond the above, 0 by default: IFHIP_COLOR_KIND_GRAY -- a GRAY
+ * profile (kTRC, XYZ PCS) on a grey frame (a one-component JPEG, PNG colour types 0 and 4), the reference's
+ * SourceProfile::IccProfileGray; IFHIP_COLOR_KIND_LUT -- an RGB profile that carries A2B0 (lut8 / lut16 with an XYZ PCS, lutAToB
+ * with an XYZ or Lab PCS).  Both go through a colour link (include/imageflow_hip_color_link.h), built once per profile and
+ * context.  The flags act only where colour management already acts for that input (the switch above, or the decoder command
+ * "convert_color_profile"); "discard_color_profile" wins as before.  With a flag set, a profile of that kind that is still not
+ * converted keeps the ActionNotSupported refusal, which names the case (perceptual intent and A2B0 only; no grey LUTs; lut8 /
+ * lut16 with a Lab PCS; CMYK); a malformed one is a ColorProfileError unless the decoder was told
+ * "ignore_color_profile_errors".  Returns false for an unknown bit.
+ * ifhip_shim_color_links_built: how many links this context's jobs built from profile bytes (diagnostic: a profile met again
+ * is served from the context's cache of a handful of links). */
+#define IFHIP_COLOR_KIND_GRAY 1u
+#define IFHIP_COLOR_KIND_LUT 2u
+IMAGEFLOW_SHIM_API bool ifhip_shim_context_set_color_profile_kinds(struct imageflow_context *context, uint32_t flags);
+IMAGEFLOW_SHIM_API int64_t ifhip_shim_color_links_built(struct imageflow_context *context);
 /* EXTENSION: lossy WebP inputs -- a still `VP8 ` chunk, with or without an `ALPH` chunk -- are decoded on the device, to
  * exactly what WebPDecode(MODE_BGRA) gives with libwebp's default options (csrc/vp8_read.cpp, csrc/vp8_decode.hip): `decode`,
  * `watermark`, `command_string` and v1/get_image_info then take such a file (bgra_32 where it has alpha, else bgr_32).  Off by
